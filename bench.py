@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: multi-channel float32 FIR, 257 taps, 4096 channels per GPU (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by the driver under torch.distributed.run, one rank per GPU, backend nccl = RCCL)
 
 A step = one pass of the hot path over one batch: llz_fir_filter_mc() on 4096 channels x 2^20 samples of
 synthetic PCM that is already resident in HBM (generated on the device).  Channels shard across ranks with no
 data-path collective (weak scaling: every GPU filters its own 4096 channels); the only exchange is the tap-table
 broadcast from rank 0 at setup.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time K steps, print the line.  --full adds
+everything else (parity against the CPU oracle, the device-to-device memcpy rate, the CPU baseline and the 'also'
+configurations).  --dump-outputs DIR writes a fixed sample of the last timed step's output as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -97,6 +101,36 @@ def kernel_source_sha():
     return h.hexdigest()
 
 
+DUMP_BYTES = 60 * 10 ** 6          # cap on the files --dump-outputs writes
+
+
+def dump_outputs(torch, y, out_dir):
+    """Write a fixed sample of the output batch y [channels, n] float32 (this rank's shard) to out_dir:
+    y_channels.npy  8 seeded channels over their full length (up to 32 MiB),
+    y_head.npy      every channel over its first samples (up to 16 MiB),
+    y_scatter.npy   up to 2^20 seeded (channel, sample) positions of the whole batch, flattened row-major.
+    The selection depends only on the batch shape, so runs with the same arguments write comparable files."""
+    channels, n = y.shape
+    rng = np.random.default_rng(SEED)
+    k = min(8, channels)
+    sel = np.sort(rng.choice(channels, size=k, replace=False))
+    cols = min(n, (32 << 20) // (4 * k))
+    head_rows = min(channels, (16 << 20) // 4)
+    head = min(n, max(1, (16 << 20) // (4 * head_rows)))
+    flat = np.sort(rng.choice(channels * n, size=min(1 << 20, channels * n), replace=False))
+    idx = torch.from_numpy(sel).to(y.device)
+    parts = {"y_channels": y.index_select(0, idx)[:, :cols],
+             "y_head": y[:head_rows, :head],
+             "y_scatter": y.reshape(-1)[torch.from_numpy(flat).to(y.device)]}
+    arrays = {name: t.to(torch.float32).cpu().numpy() for name, t in parts.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -106,13 +140,21 @@ def main():
     ap.add_argument("--samples", type=int, default=N_SAMPLES)
     ap.add_argument("--algo", type=int, default=0, help="0 auto (overlap-save), 1 time domain, 2 overlap-save, 3 time domain on the matrix cores, 4 / 5 overlap-save with\n"
                          "2048- / 4096-point transforms, 6 overlap-save with 8192-point transforms on pairs of waves")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--extra", action="store_true", help="(kept for old command lines: the extra configs now run by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: parity against the CPU oracle, the "
+                         "device memcpy rate, the CPU baseline and the 'also' configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--extra", action="store_true", help="(kept for old command lines: --full runs the extra configs)")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the channel-sharded resample / IIR configs (BASELINE configs 4 and 5) reported under 'also'")
+                    help="with --full: skip the configurations reported under 'also'")
     ap.add_argument("--dist-backend", default="nccl",
                     help="process-group backend; 'gloo' lets several ranks rehearse on ONE GPU (tables travel as CPU tensors)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    run_also = args.full and not args.no_also
 
     import torch
     import torch.distributed as dist
@@ -154,7 +196,7 @@ def main():
     # every coefficient table the run needs is designed on rank 0 (host C code) and broadcast HERE, before anything is timed
     # and outside every guarded block: setup collectives either work on all ranks or end the job
     tables = {"fir257": taps}
-    if not args.no_also:
+    if run_also:
         for t in (513, 1025, 2049, 3073):
             d = filters.fir_design("lpf", t, 0.1, 0.0, filters.KAISER) if rank == 0 else np.zeros(t)
             tables[f"fir{t}"] = shard.broadcast_table(d, src=0, device=comm_dev)
@@ -200,11 +242,13 @@ def main():
     for t in timers:
         L.llz_hip_timer_free(t)
     kern_ms = float(np.mean(launch_ms))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, y, args.dump_outputs)
 
     fir_algo = fir.algo
     # the box's own streaming rate for the same 16 GiB -> 16 GiB: a device-to-device memcpy on the same stream
     memcpy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         y.copy_(x)
         torch.cuda.synchronize()
         tm = L.llz_hip_timer_new()
@@ -226,7 +270,7 @@ def main():
     also = {}
     cpu = None
     orc = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import pyoracle
         orc = pyoracle.Oracle()
         keep = FLT_LEN - 1
@@ -314,18 +358,18 @@ def main():
                 "channels_per_gpu": channels, "scaling": "weak", "algorithm": algo})
         return res
 
-    if not args.no_also and fir_algo == 2:
+    if run_also and fir_algo == 2:
         also.update(run_block("long_fir", [f"fir_{t}taps_{channels}ch_per_gpu" for t in LONG], long_fir))
 
     # release the FIR batch before the other configs allocate theirs
     fir.close()
     del x, y
     torch.cuda.empty_cache()
-    if not args.no_also:
+    if run_also:
         for label, keys, fn in sharded_blocks(ctx):
             also.update(run_block(label, keys, fn))
             torch.cuda.empty_cache()
-    if not args.no_also and world == 1:
+    if run_also and world == 1:
         also.update(run_block("extra_paths", EXTRA_KEYS, lambda: extra_paths(ctx)))
         torch.cuda.empty_cache()
         if torch.cuda.device_count() > 1:
@@ -351,6 +395,7 @@ def main():
             "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic", "table_broadcast": shard.transport() if world > 1 else "single process",
+            "full": args.full,
             "config": {"workload": f"{channels}-ch float32 FIR, {FLT_LEN} taps (llz_fir_lpf_cof 0.1 KAISER), "
                                    f"{n} samples/ch per GPU, {algo_name}, channels sharded over {world} GPU(s)",
                        "channels_per_gpu": channels, "samples_per_channel": n, "taps": FLT_LEN,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the COMPILED REFERENCE (oracle/_ref/libllzref.so).
 
-Run in the build container only (needs /root/reference to build _ref):  python oracle/gen_golden.py
+Run where the reference tree is present (oracle/Makefile builds _ref from it):  python oracle/gen_golden.py [wav]
 The fixtures are data: seeded inputs and the outputs the reference's own C code produced for them
 (gcc 11.4 -O2, glibc 2.35).  The reference has no golden vectors of its own, so these
 are the pins for the oracle on the GPU box where the reference does not exist.
@@ -227,9 +227,38 @@ def main():
         d[f"fx_{frame_len}_{win}"], d[f"fX_{frame_len}_{win}"], d[f"fy_{frame_len}_{win}"] = x, X, y
     np.savez_compressed(os.path.join(OUT, "mdct.npz"), **d)
 
+    wav(r)
+
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden fixtures written to", OUT, "total bytes", tot)
 
 
+def wav(r):
+    """wav.npz: the reference's own WAV header reader and writer (libllzaudio/llz_wavfmt.c) on the images and headers of
+    tests/test_wav_pcm.py.  The images are stored with the results, so the test can tell a changed image from a changed
+    parser."""
+    import tempfile
+    from tests.test_wav_pcm import CASES, WAV_FIELDS, WRITER_CASES, case_id, make_wav
+
+    d = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "t.wav")
+        for case in CASES:
+            img, _pcm = make_wav(**{k: v for k, v in case.items() if k != "extra_before_fmt"})
+            with open(path, "wb") as f:
+                f.write(img)
+            got = r.wav_readheader(path)
+            d[f"read_{case_id(case)}_img"] = np.frombuffer(img, dtype=np.uint8)
+            d[f"read_{case_id(case)}"] = np.array([got[k] for k in WAV_FIELDS], dtype=np.int64)
+        for ch, rate, frames in WRITER_CASES:
+            d[f"write_{ch}_{rate}_{frames}"] = np.frombuffer(r.wav_writeheader(path, ch, rate, 2, frames)[:44], dtype=np.uint8)
+    np.savez_compressed(os.path.join(OUT, "wav.npz"), **d)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["wav"]:                 # only the WAV fixtures: python oracle/gen_golden.py wav
+        po.build()
+        os.makedirs(OUT, exist_ok=True)
+        wav(po.Ref())
+    else:
+        main()

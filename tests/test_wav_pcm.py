@@ -1,5 +1,5 @@
 """WAV container and PCM ingest: the oracle's restatement of libllzaudio/llz_wavfmt.c is pinned
-against the reference's own reader / writer (oracle/_ref, built from the reference's file where it lies), the product's
+against the reference's own reader / writer (their results recorded in tests/golden/wav.npz by oracle/gen_golden.py), the product's
 host parser against the oracle, and the device de-interleaver against the oracle's PCM functions."""
 import ctypes as C
 import os
@@ -33,6 +33,12 @@ CASES = [dict(channels=1, rate=48000, frames=100, seed=1),
          dict(channels=6, rate=96000, frames=57, seed=3, extra_before_fmt=chunk(b"JUNK", b"\0" * 12), fmt_extra=b"\0\0"),
          dict(channels=64, rate=16000, frames=40, seed=4, extra_before_fmt=chunk(b"bext", b"b" * 8),
               extra_before_data=chunk(b"fact", b"1234") + chunk(b"LIST", b"yy"))]
+WRITER_CASES = ((1, 44100, 216090 // 2), (2, 48000, 1000), (8, 16000, 12345))
+WAV_FIELDS = ("format", "channels", "samplerate", "bytes_per_sample", "block_align", "frames", "data_offset")
+
+
+def case_id(case):
+    return f"{case['channels']}ch"
 
 
 @pytest.fixture(scope="module")
@@ -40,28 +46,28 @@ def oracle():
     return po.Oracle()
 
 
-@pytest.mark.parametrize("case", CASES, ids=[f"{c['channels']}ch" for c in CASES])
-def test_oracle_wav_parse_matches_the_reference_reader(oracle, case, tmp_path):
+@pytest.fixture(scope="module")
+def ref_wav():
+    """the reference's own reader / writer results on these images (tests/golden/wav.npz, oracle/gen_golden.py)"""
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wav.npz"), allow_pickle=False)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[case_id(c) for c in CASES])
+def test_oracle_wav_parse_matches_the_reference_reader(oracle, ref_wav, case):
     """(a chunk in FRONT of "fmt " is left out here: the reference's skip loop never re-reads the chunk id after its fseek,
     llz_wavfmt.c:108-114, and spins forever on such a file; the restatement re-reads it -- those images are compared between
     oracle and product only)"""
-    if not po.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    case = {k: v for k, v in case.items() if k != "extra_before_fmt"}
-    img, _pcm = make_wav(**case)
-    path = tmp_path / "t.wav"
-    path.write_bytes(img)
-    ref = po.Ref().wav_readheader(str(path))
+    img, _pcm = make_wav(**{k: v for k, v in case.items() if k != "extra_before_fmt"})
+    assert img == ref_wav[f"read_{case_id(case)}_img"].tobytes(), "the image differs from the one the fixture was made on"
+    ref = dict(zip(WAV_FIELDS, (int(v) for v in ref_wav[f"read_{case_id(case)}"])))
     got = oracle.wav_parse(img)
     assert got == ref
 
 
-def test_oracle_wav_header_matches_the_reference_writer(oracle, tmp_path):
-    if not po.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    for ch, rate, frames in ((1, 44100, 216090 // 2), (2, 48000, 1000), (8, 16000, 12345)):
-        ref = po.Ref().wav_writeheader(str(tmp_path / "h.wav"), ch, rate, 2, frames)
-        assert oracle.wav_header(ch, rate, 2, frames) == ref[:44]
+def test_oracle_wav_header_matches_the_reference_writer(oracle, ref_wav):
+    for ch, rate, frames in WRITER_CASES:
+        ref = ref_wav[f"write_{ch}_{rate}_{frames}"].tobytes()
+        assert len(ref) == 44 and oracle.wav_header(ch, rate, 2, frames) == ref
 
 
 def test_oracle_wav_known_answers(oracle):

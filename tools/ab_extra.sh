@@ -1,7 +1,7 @@
 # A/B of whole-library builds on the secondary paths: time-domain 257-tap FIR (bench --algo 1) and bench --extra
 cd $GRAFT_REPO_ROOT
 for lib in "$@"; do
-  LLZ_LIB=$PWD/llzlab_amd/$lib python bench.py --steps 3 --warmup 1 --no-cpu --algo 1 --extra 2>/dev/null | python -c "
+  LLZ_LIB=$PWD/llzlab_amd/$lib python bench.py --full --steps 3 --warmup 1 --no-cpu --algo 1 --extra 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0])
 a=d['also']

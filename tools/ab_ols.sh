@@ -5,5 +5,5 @@ cd $GRAFT_REPO_ROOT
 for arm in "$@"; do
   lib=${arm%%:*}; var=${arm##*:}
   [ "$var" = "$lib" ] && var=""
-  LLZ_LIB=$PWD/llzlab_amd/$lib LLZ_TUNE=$var python bench.py --steps 10 --warmup 2 --no-cpu --no-also 2>/dev/null | show "$lib:$var"
+  LLZ_LIB=$PWD/llzlab_amd/$lib LLZ_TUNE=$var python bench.py --full --steps 10 --warmup 2 --no-cpu --no-also 2>/dev/null | show "$lib:$var"
 done

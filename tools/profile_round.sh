@@ -2,8 +2,8 @@
 # SAME command line the driver uses (default --steps/--warmup), the PMC traffic passes and SQ / matrix-pipe counter passes.
 # usage (from gpurun): bash tools/profile_round.sh r03
 R=$GRAFT_REPO_ROOT; TAG=${1:-r03}; O=$R/gpurun_out/profile_$TAG; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err &&
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu > $O/bench_under_rocprof.json 2> $O/stats.err &&
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err &&
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu > $O/bench_under_rocprof.json 2> $O/stats.err &&
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-also > $O/pmc_fetch.log 2>&1 &&
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --no-also > $O/pmc_write.log 2>&1 &&
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq1 -- python3 $R/bench.py --steps 5 --warmup 5 --no-cpu --no-also > $O/pmc_sq1.log 2>&1 &&
