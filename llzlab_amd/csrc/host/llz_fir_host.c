@@ -147,9 +147,7 @@ typedef struct {
     int device;                 /* the device the handle's buffers live on: every call binds it */
     int channels, frame_len, flt_len, algo;
     float *d_taps;              /* flt_len floats zero-padded to a multiple of 16 */
-    float *d_hfreq, *d_twid;    /* overlap-save tables (NULL for the time-domain algorithm) */
-    float *d_tw2k;              /* 2048-point overlap-save: W_2048^n, n < 1024 (d_hfreq: even | odd bins) */
-    float *d_tw4k;              /* 4096-point overlap-save on a whole wave (<= 3073 taps): W_4096^n, n < 2048 (d_hfreq: 4 planes) */
+    llzs_ols_tables ols;        /* overlap-save tables (all NULL for the time-domain algorithms) */
     float *d_hist[2];           /* [channels][flt_len-1], ping-pong */
     int cur;
     float *d_zero;              /* [channels][flt_len-1] zeros: flush input */
@@ -160,23 +158,65 @@ typedef struct {
 static void firm_destroy(firm_t *f)
 {
     if (!f) return;
-    llzs_free(f->d_taps); llzs_free(f->d_hfreq); llzs_free(f->d_twid); llzs_free(f->d_tw2k); llzs_free(f->d_tw4k);
+    llzs_free(f->d_taps); llzs_free(f->ols.hfreq); llzs_free(f->ols.twid); llzs_free(f->ols.tw2k); llzs_free(f->ols.tw4k);
     llzs_free(f->d_hist[0]); llzs_free(f->d_hist[1]); llzs_free(f->d_zero);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     f->tag = 0;
     free(f);
 }
 
-/* spectrum of the (float-rounded) taps, scaled by 1/N, as float pairs in natural bin order; and the 32x32
- * inter-pass twiddles W_N^(a*b).  Direct DFT in double: 257 x 1024 terms, setup time only. */
-static int firm_build_ols_tables(firm_t *f, const float *taps)
+/* The overlap-save sizes: algo, transform points, the taps the rung accepts, and auto_max: AUTO takes the first rung whose
+ * auto_max holds the filter (from 33 taps on; up to 32 the time domain).  auto_max is a crossover measured on 4096 ch x 2^20
+ * (tools/fir_crossover.py), not the rung's limit.  Beyond the last rung AUTO takes the matrix-core form of the time domain. */
+static const struct firm_ols_rung {
+    int algo, nfft, min_taps, max_taps, auto_max;
+} FIRM_OLS[] = {
+    /* time domain 6.0 / 6.4 / 7.9 / 9.5 ms at 9 / 17 / 33 / 63 taps, overlap-save 6.7 ms at any length up to 257; beyond 257
+     * taps the matrix-core time domain takes 23.7 ms (31.9 ms on the VALU) */
+    {LLZ_FIR_ALGO_OVERLAP_SAVE, 1024, 1, 257, 257},
+    /* 2048 points with 512 of overlap 7.8 ms up to 513 taps (10.6 ms with 1024 of overlap); 4096 points 8.0 / 7.9 / 8.3 / 9.6 /
+     * 11.3 / 14.7 / 19.5 ms with 512 / 768 / 1024 / 1536 / 2048 / 2560 / 3072 of overlap */
+    {LLZ_FIR_ALGO_OVERLAP_SAVE_2048, 2048, 2, 1025, 513},
+    /* 8192 points on pairs of waves: 9.1 / 10.9 / 10.9 / 11.3 / 13.8 ms with 1536 / 2304 / 2560 / 3072 / 4096 of overlap -> from
+     * 1026 taps on (4096 points: 9.4 / 11.2 / 14.4 / 19.2 ms with 1536 / 2048 / 2560 / 3072) */
+    {LLZ_FIR_ALGO_OVERLAP_SAVE_4096, 4096, 2, 3073, 1025},
+    {LLZ_FIR_ALGO_OVERLAP_SAVE_8192, 8192, 2, 6145, 6145},
+};
+#define FIRM_OLS_RUNGS ((int)(sizeof(FIRM_OLS) / sizeof(FIRM_OLS[0])))
+
+static const struct firm_ols_rung *firm_ols_rung(int algo)
 {
-    const int N = LLZS_OLS_NFFT;
-    float *hf = (float *)malloc(sizeof(float) * 2 * (size_t)N);
-    float *tw = (float *)malloc(sizeof(float) * 2 * 1024);
+    for (int i = 0; i < FIRM_OLS_RUNGS; i++)
+        if (FIRM_OLS[i].algo == algo) return &FIRM_OLS[i];
+    return NULL;
+}
+
+/* W_N^m = exp(-2 pi j m / N) as a float pair, from the cos / sin table of size N */
+static void firm_w(float *dst, const double *cs, int m)
+{
+    dst[0] = (float)cs[2 * m];
+    dst[1] = (float)(-cs[2 * m + 1]);
+}
+
+/* the tables of the N-point overlap-save (llzs_ols_tables): the spectrum of the (float-rounded) taps scaled by 1/N in
+ * P = N / 1024 planes, the 32 x 32 twiddles W_1024^(ab) = W_N^(P ab), W_2048^n (N = 2048, 4096) and W_4096^n (N = 4096, 8192),
+ * all from one quadrant-exact cos / sin table of size N.  Direct DFT in double (up to 6145 x 8192 terms), setup time only. */
+static int firm_build_ols_tables(firm_t *f, const float *taps, int N)
+{
+    const int P = N / 1024;
+    /* complex entries of hfreq, twid, tw2k, tw4k (0: the rung has no such table) */
+    const int count[4] = {N, 1024, (N == 2048 || N == 4096) ? 1024 : 0, N >= 4096 ? 2048 : 0};
+    float **dev[4] = {&f->ols.hfreq, &f->ols.twid, &f->ols.tw2k, &f->ols.tw4k};
+    float *host[4];
+    int rc = LLZ_OK;
+    for (int i = 0; i < 4; i++) {
+        host[i] = count[i] ? (float *)malloc(sizeof(float) * 2 * (size_t)count[i]) : NULL;
+        if (count[i] && !host[i]) rc = LLZ_ERR_NOMEM;
+    }
     double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = LLZ_ERR_NOMEM;
-    if (hf && tw && cs) {
+    if (!cs) rc = LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {
+        float *hf = host[0], *tw = host[1], *w2 = host[2], *w4 = host[3];
         for (int i = 0; i < N; i++) {
             /* exact quadrant values keep the table symmetric */
             const double ang = 2.0 * M_PI * (double)i / (double)N;
@@ -190,167 +230,22 @@ static int firm_build_ols_tables(firm_t *f, const float *taps)
                 re += (double)taps[t] * cs[2 * m];
                 im -= (double)taps[t] * cs[2 * m + 1];
             }
-            hf[2 * k] = (float)(re / N);
-            hf[2 * k + 1] = (float)(im / N);
-        }
-        for (int a = 0; a < 32; a++)
-            for (int b = 0; b < 32; b++) {
-                const int m = (a * b) % N;
-                tw[2 * (a * 32 + b)] = (float)cs[2 * m];
-                tw[2 * (a * 32 + b) + 1] = (float)(-cs[2 * m + 1]);       /* W = exp(-2 pi j m / N) */
-            }
-        f->d_hfreq = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)N);
-        f->d_twid = (float *)llzs_malloc(sizeof(float) * 2 * 1024);
-        rc = (f->d_hfreq && f->d_twid) ? LLZ_OK : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_hfreq, hf, sizeof(float) * 2 * (size_t)N);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_twid, tw, sizeof(float) * 2 * 1024);
-    }
-    free(hf); free(tw); free(cs);
-    return rc;
-}
-
-/* 258 .. 1025 taps (k_fir_ols2k_chain_f32): DFT_2048(taps) / 2048 as [even bins | odd bins], the 32 x 32 twiddles of the
- * 1024-point halves, and W_2048^n for the radix-2 step.  Direct DFT in double, setup time only. */
-static int firm_build_ols2k_tables(firm_t *f, const float *taps)
-{
-    const int N = 2048, H = 1024;
-    float *hf = (float *)malloc(sizeof(float) * 2 * (size_t)N);
-    float *tw = (float *)malloc(sizeof(float) * 2 * 1024);
-    float *w2 = (float *)malloc(sizeof(float) * 2 * (size_t)H);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = LLZ_ERR_NOMEM;
-    if (hf && tw && w2 && cs) {
-        for (int i = 0; i < N; i++) {
-            const double ang = 2.0 * M_PI * (double)i / (double)N;
-            cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-            cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-        }
-        for (int k = 0; k < N; k++) {
-            double re = 0.0, im = 0.0;
-            for (int t = 0; t < f->flt_len; t++) {
-                const int m = (int)(((long)k * t) % N);
-                re += (double)taps[t] * cs[2 * m];
-                im -= (double)taps[t] * cs[2 * m + 1];
-            }
-            const int dst = (k & 1) * H + (k >> 1);                    /* even bins first, then odd bins */
+            const int dst = (k % P) * 1024 + k / P;                    /* bin k -> plane k mod P, row k / P */
             hf[2 * dst] = (float)(re / N);
             hf[2 * dst + 1] = (float)(im / N);
         }
         for (int a = 0; a < 32; a++)
-            for (int b = 0; b < 32; b++) {
-                const int m = (2 * a * b) % N;                         /* W_1024^(ab) = W_2048^(2ab) */
-                tw[2 * (a * 32 + b)] = (float)cs[2 * m];
-                tw[2 * (a * 32 + b) + 1] = (float)(-cs[2 * m + 1]);
-            }
-        for (int i = 0; i < H; i++) {
-            w2[2 * i] = (float)cs[2 * i];
-            w2[2 * i + 1] = (float)(-cs[2 * i + 1]);                   /* W = exp(-2 pi j i / 2048) */
-        }
-        f->d_hfreq = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)N);
-        f->d_twid = (float *)llzs_malloc(sizeof(float) * 2 * 1024);
-        f->d_tw2k = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)H);
-        rc = (f->d_hfreq && f->d_twid && f->d_tw2k) ? LLZ_OK : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_hfreq, hf, sizeof(float) * 2 * (size_t)N);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_twid, tw, sizeof(float) * 2 * 1024);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_tw2k, w2, sizeof(float) * 2 * (size_t)H);
+            for (int b = 0; b < 32; b++) firm_w(&tw[2 * (a * 32 + b)], cs, (P * a * b) % N);
+        for (int i = 0; i < count[2]; i++) firm_w(&w2[2 * i], cs, i * (N / 2048));
+        for (int i = 0; i < count[3]; i++) firm_w(&w4[2 * i], cs, i * (N / 4096));
+        /* allocate, then upload in the order hfreq, twid, tw2k, tw4k: a sharded init records the tables in upload order */
+        for (int i = 0; i < 4; i++)
+            if (count[i] && !(*dev[i] = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)count[i]))) rc = LLZ_ERR_NOMEM;
+        for (int i = 0; i < 4 && rc == LLZ_OK; i++)
+            if (count[i]) rc = llzs_h2d_table(*dev[i], host[i], sizeof(float) * 2 * (size_t)count[i]);
     }
-    free(hf); free(tw); free(w2); free(cs);
-    return rc;
-}
-
-/* 514 .. 3073 taps (k_fir_ols4k_f32): DFT_4096(taps) / 4096 as four planes (plane j = bins 4m + j), the 32 x 32 twiddles
- * of the 1024-point transforms, W_2048^n and W_4096^n for the two radix-2 steps.  Direct DFT in double, setup time only. */
-static int firm_build_ols4k_tables(firm_t *f, const float *taps)
-{
-    const int N = 4096, Q = 1024;
-    float *hf = (float *)malloc(sizeof(float) * 2 * (size_t)N);
-    float *tw = (float *)malloc(sizeof(float) * 2 * 1024);
-    float *w2 = (float *)malloc(sizeof(float) * 2 * 1024);
-    float *w4 = (float *)malloc(sizeof(float) * 2 * 2048);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = LLZ_ERR_NOMEM;
-    if (hf && tw && w2 && w4 && cs) {
-        for (int i = 0; i < N; i++) {
-            const double ang = 2.0 * M_PI * (double)i / (double)N;
-            cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-            cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-        }
-        for (int k = 0; k < N; k++) {
-            double re = 0.0, im = 0.0;
-            for (int t = 0; t < f->flt_len; t++) {
-                const int m = (int)(((long)k * t) % N);
-                re += (double)taps[t] * cs[2 * m];
-                im -= (double)taps[t] * cs[2 * m + 1];
-            }
-            const int dst = (k & 3) * Q + (k >> 2);
-            hf[2 * dst] = (float)(re / N);
-            hf[2 * dst + 1] = (float)(im / N);
-        }
-        for (int a = 0; a < 32; a++)
-            for (int b = 0; b < 32; b++) {
-                const int m = (4 * a * b) % N;                         /* W_1024^(ab) = W_4096^(4ab) */
-                tw[2 * (a * 32 + b)] = (float)cs[2 * m];
-                tw[2 * (a * 32 + b) + 1] = (float)(-cs[2 * m + 1]);
-            }
-        for (int i = 0; i < 1024; i++) { w2[2 * i] = (float)cs[2 * (2 * i)]; w2[2 * i + 1] = (float)(-cs[2 * (2 * i) + 1]); }
-        for (int i = 0; i < 2048; i++) { w4[2 * i] = (float)cs[2 * i]; w4[2 * i + 1] = (float)(-cs[2 * i + 1]); }
-        f->d_hfreq = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)N);
-        f->d_twid = (float *)llzs_malloc(sizeof(float) * 2 * 1024);
-        f->d_tw2k = (float *)llzs_malloc(sizeof(float) * 2 * 1024);
-        f->d_tw4k = (float *)llzs_malloc(sizeof(float) * 2 * 2048);
-        rc = (f->d_hfreq && f->d_twid && f->d_tw2k && f->d_tw4k) ? LLZ_OK : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_hfreq, hf, sizeof(float) * 2 * (size_t)N);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_twid, tw, sizeof(float) * 2 * 1024);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_tw2k, w2, sizeof(float) * 2 * 1024);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_tw4k, w4, sizeof(float) * 2 * 2048);
-    }
-    free(hf); free(tw); free(w2); free(w4); free(cs);
-    return rc;
-}
-
-/* 2 .. 6145 taps on pairs of waves (k_fir_ols8k_f32): DFT_8192(taps) / 8192 as eight planes (plane j = bins 8m + j), the
- * 32 x 32 twiddles of the 1024-point transforms and W_4096^n (the kernel forms W_8192^n itself).  Direct DFT in double. */
-static int firm_build_ols8k_tables(firm_t *f, const float *taps)
-{
-    const int N = 8192, Q = 1024;
-    float *hf = (float *)malloc(sizeof(float) * 2 * (size_t)N);
-    float *tw = (float *)malloc(sizeof(float) * 2 * 1024);
-    float *w4 = (float *)malloc(sizeof(float) * 2 * 2048);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = LLZ_ERR_NOMEM;
-    if (hf && tw && w4 && cs) {
-        for (int i = 0; i < N; i++) {
-            const double ang = 2.0 * M_PI * (double)i / (double)N;
-            cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-            cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-        }
-        for (int k = 0; k < N; k++) {
-            double re = 0.0, im = 0.0;
-            for (int t = 0; t < f->flt_len; t++) {
-                const int m = (int)(((long)k * t) % N);
-                re += (double)taps[t] * cs[2 * m];
-                im -= (double)taps[t] * cs[2 * m + 1];
-            }
-            const int dst = (k & 7) * Q + (k >> 3);
-            hf[2 * dst] = (float)(re / N);
-            hf[2 * dst + 1] = (float)(im / N);
-        }
-        for (int a = 0; a < 32; a++)
-            for (int b = 0; b < 32; b++) {
-                const int m = (8 * a * b) % N;                         /* W_1024^(ab) = W_8192^(8ab) */
-                tw[2 * (a * 32 + b)] = (float)cs[2 * m];
-                tw[2 * (a * 32 + b) + 1] = (float)(-cs[2 * m + 1]);
-            }
-        for (int i = 0; i < 2048; i++) { w4[2 * i] = (float)cs[2 * (2 * i)]; w4[2 * i + 1] = (float)(-cs[2 * (2 * i) + 1]); }
-        f->d_hfreq = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)N);
-        f->d_twid = (float *)llzs_malloc(sizeof(float) * 2 * 1024);
-        f->d_tw4k = (float *)llzs_malloc(sizeof(float) * 2 * 2048);
-        rc = (f->d_hfreq && f->d_twid && f->d_tw4k) ? LLZ_OK : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_hfreq, hf, sizeof(float) * 2 * (size_t)N);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_twid, tw, sizeof(float) * 2 * 1024);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_tw4k, w4, sizeof(float) * 2 * 2048);
-    }
-    free(hf); free(tw); free(w4); free(cs);
+    for (int i = 0; i < 4; i++) free(host[i]);
+    free(cs);
     return rc;
 }
 
@@ -366,43 +261,23 @@ unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *t
         return LLZ_BAD_HANDLE;
     }
     if (algo == LLZ_FIR_ALGO_AUTO) {
-        /* measured on 4096 ch x 2^20 (tools/fir_crossover.py): time domain 6.0 / 6.4 / 7.9 / 9.5 ms at 9 / 17 / 33 / 63
-         * taps, overlap-save 6.7 ms at any length up to 257 -> overlap-save from 33 taps on; beyond 257 taps the
-         * matrix-core form of the time domain (23.7 ms at 257 taps against 31.9 ms on the VALU) */
+        int i = 0;
+        while (i < FIRM_OLS_RUNGS && flt_len > FIRM_OLS[i].auto_max) i++;
         if (flt_len <= 32) algo = LLZ_FIR_ALGO_TIME;
-        else if (flt_len <= LLZS_OLS_MAX_TAPS) algo = LLZ_FIR_ALGO_OVERLAP_SAVE;
-        /* whole-wave overlap-save (4096 ch x 2^20): 2048 points with 512 of overlap 7.8 ms up to 513 taps (10.6 ms with 1024
-         * of overlap); 4096 points 8.0 / 7.9 / 8.3 / 9.6 / 11.3 / 14.7 / 19.5 ms with 512 / 768 / 1024 / 1536 / 2048 / 2560 /
-         * 3072 of overlap */
-        else if (flt_len <= 513) algo = LLZ_FIR_ALGO_OVERLAP_SAVE_2048;
-        /* 8192 points on pairs of waves, same batch: 9.1 / 10.9 / 10.9 / 11.3 / 13.8 ms with 1536 / 2304 / 2560 / 3072 / 4096 of
-         * overlap -> from 1026 taps on (4096 points: 9.4 / 11.2 / 14.4 / 19.2 ms with 1536 / 2048 / 2560 / 3072), up to 6145 taps */
-        else if (flt_len <= 1025) algo = LLZ_FIR_ALGO_OVERLAP_SAVE_4096;
-        else if (flt_len <= LLZS_OLS8K_MAX_TAPS) algo = LLZ_FIR_ALGO_OVERLAP_SAVE_8192;
+        else if (i < FIRM_OLS_RUNGS) algo = FIRM_OLS[i].algo;
         else algo = llzs_fir_mfma_f32_fits(flt_len, 1) ? LLZ_FIR_ALGO_TIME_MFMA : LLZ_FIR_ALGO_TIME;
     }
-    if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE_2048 && (flt_len < 2 || flt_len > LLZS_OLS2K_MAX_TAPS)) {
-        llzs_set_error("llz_fir_filter_mc_init: the 2048-point overlap-save takes 2..%d taps", LLZS_OLS2K_MAX_TAPS);
-        return LLZ_BAD_HANDLE;
-    }
-    if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE_4096 && (flt_len < 2 || flt_len > LLZS_OLS4K_MAX_TAPS)) {
-        llzs_set_error("llz_fir_filter_mc_init: the 4096-point overlap-save takes 2..%d taps", LLZS_OLS4K_MAX_TAPS);
-        return LLZ_BAD_HANDLE;
-    }
-    if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE_8192 && (flt_len < 2 || flt_len > LLZS_OLS8K_MAX_TAPS)) {
-        llzs_set_error("llz_fir_filter_mc_init: the 8192-point overlap-save takes 2..%d taps", LLZS_OLS8K_MAX_TAPS);
-        return LLZ_BAD_HANDLE;
-    }
-    if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE && flt_len > LLZS_OLS_MAX_TAPS) {
-        llzs_set_error("llz_fir_filter_mc_init: overlap-save supports at most %d taps", LLZS_OLS_MAX_TAPS);
+    const struct firm_ols_rung *ols = firm_ols_rung(algo);
+    if (ols && (flt_len < ols->min_taps || flt_len > ols->max_taps)) {
+        llzs_set_error("llz_fir_filter_mc_init: the %d-point overlap-save takes %d..%d taps", ols->nfft, ols->min_taps,
+                       ols->max_taps);
         return LLZ_BAD_HANDLE;
     }
     if (algo == LLZ_FIR_ALGO_TIME_MFMA && !llzs_fir_mfma_f32_fits(flt_len, 1)) {
         llzs_set_error("llz_fir_filter_mc_init: %d taps do not fit the matrix-core kernel's LDS tile", flt_len);
         return LLZ_BAD_HANDLE;
     }
-    if (algo != LLZ_FIR_ALGO_TIME && algo != LLZ_FIR_ALGO_OVERLAP_SAVE && algo != LLZ_FIR_ALGO_TIME_MFMA &&
-        algo != LLZ_FIR_ALGO_OVERLAP_SAVE_2048 && algo != LLZ_FIR_ALGO_OVERLAP_SAVE_4096 && algo != LLZ_FIR_ALGO_OVERLAP_SAVE_8192) {
+    if (!ols && algo != LLZ_FIR_ALGO_TIME && algo != LLZ_FIR_ALGO_TIME_MFMA) {
         llzs_set_error("llz_fir_filter_mc_init: unknown algo %d", algo);
         return LLZ_BAD_HANDLE;
     }
@@ -428,11 +303,7 @@ unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *t
     if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[0], 0, hist_bytes, NULL);
     if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[1], 0, hist_bytes, NULL);
     if (rc == LLZ_OK) rc = llzs_memset(f->d_zero, 0, hist_bytes, NULL);
-    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_OVERLAP_SAVE) rc = firm_build_ols_tables(f, taps);
-    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_OVERLAP_SAVE_2048) rc = firm_build_ols2k_tables(f, taps);
-    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_OVERLAP_SAVE_4096)
-        rc = firm_build_ols4k_tables(f, taps);
-    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_OVERLAP_SAVE_8192) rc = firm_build_ols8k_tables(f, taps);
+    if (rc == LLZ_OK && ols) rc = firm_build_ols_tables(f, taps, ols->nfft);
     if (rc == LLZ_OK) rc = llzs_sync(NULL);
     free(padded);
     if (rc != LLZ_OK) {
@@ -524,19 +395,11 @@ int llz_fir_filter_mc_set_stream(unsigned long handle, void *stream)
 static int firm_launch(firm_t *f, const float *d_in, float *d_out, int n, long pitch_in, long pitch_out, int algo)
 {
     const float *hist = f->flt_len > 1 ? f->d_hist[f->cur] : NULL;
+    const struct firm_ols_rung *ols = firm_ols_rung(algo);
     int rc;
-    if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE)
-        rc = llzs_fir_ols_f32(d_in, d_out, hist, f->d_hfreq, f->d_twid, f->channels, n, pitch_in, pitch_out,
-                              f->flt_len, f->stream);
-    else if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE_2048)
-        rc = llzs_fir_ols2k_f32(d_in, d_out, hist, f->d_hfreq, f->d_twid, f->d_tw2k, f->channels, n, pitch_in, pitch_out,
-                                f->flt_len, f->stream);
-    else if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE_4096)
-        rc = llzs_fir_ols4k_f32(d_in, d_out, hist, f->d_hfreq, f->d_twid, f->d_tw2k, f->d_tw4k, f->channels, n, pitch_in,
-                                pitch_out, f->flt_len, f->stream);
-    else if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE_8192)
-        rc = llzs_fir_ols8k_f32(d_in, d_out, hist, f->d_hfreq, f->d_twid, f->d_tw4k, f->channels, n, pitch_in, pitch_out,
-                                f->flt_len, f->stream);
+    if (ols)
+        rc = llzs_fir_ols_f32(ols->nfft, &f->ols, d_in, d_out, hist, f->channels, n, pitch_in, pitch_out, f->flt_len,
+                              f->stream);
     else if (algo == LLZ_FIR_ALGO_TIME_MFMA)
         rc = llzs_fir_mfma_f32(d_in, d_out, hist, f->d_taps, f->channels, n, n, pitch_in, pitch_out, f->flt_len, 1,
                                1.0f, f->stream);

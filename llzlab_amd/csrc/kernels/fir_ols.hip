@@ -964,232 +964,128 @@ k_fir_ols8k_f32(const float *__restrict__ in, float *__restrict__ out, const flo
     O8K_DUMP();
 }
 
-} // namespace
+// ---- launch: every transform size is one row of OLS_RUNGS ----
 
-extern "C" int llzs_fir_ols_f32(const float *in, float *out, const float *hist, const float *hfreq,
-                                const float *twid, int channels, int n, long in_pitch, long out_pitch,
-                                int flt_len, void *stream)
-{
-    if (!in || !out || !hfreq || !twid || channels <= 0 || n <= 0 || in_pitch < n || out_pitch < n) {
-        llzs_set_error("fir_ols_f32: bad arguments");
-        return LLZ_ERR_ARG;
-    }
-    if (flt_len < 1 || flt_len > LLZS_OLS_MAX_TAPS) {
-        llzs_set_error("fir_ols_f32: flt_len %d outside 1..%d", flt_len, LLZS_OLS_MAX_TAPS);
-        return LLZ_ERR_RANGE;
-    }
-    ols_geom G;
-    G.n = n;
-    G.keep = flt_len - 1;
-    G.in_pitch = in_pitch;
-    G.out_pitch = out_pitch;
-    G.jobs_per_channel = (n + OLS_JOB - 1) / OLS_JOB;
-    const size_t lds_bytes = 2 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float);
-    // one resident set of workgroups (two per CU: 49 KB of LDS and ~240 registers per lane), grid stride over the segments
-    const int tuned_per_cu = llzs_tune(LLZS_TUNE_OLS_WG_PER_CU);
-    const long max_blocks = 256L * (tuned_per_cu > 0 ? tuned_per_cu : 2);
-    const long slots = max_blocks * OLS_WAVES * 2;
-    // jobs per segment: a half-wave walks seg_len consecutive jobs of one channel (the overlap stays in registers), at most
-    // OLS_SEG.  Small batches (BASELINE config 2: 64 channels) would leave half-wave slots idle or quantise badly into
-    // rounds with the full length, so they take the length that minimises rounds x (length + one job of start-up).  Large
-    // batches keep the full length: on 4096 channels a shorter segment measured 2.6 % slower.
-    const bool large = (long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels >= 4 * slots;
-    int seg_len = OLS_SEG;
-    if (!large) {
-        double best = 1e300;
-        for (int sl = OLS_SEG; sl >= 1; sl--) {
-            const long segs = (long)((G.jobs_per_channel + sl - 1) / sl) * channels;
-            const double cost = (double)((segs + slots - 1) / slots) * (sl + 1.0);
-            if (cost < best * 0.999) { best = cost; seg_len = sl; }
-        }
-    }
-    if (const int v = llzs_tune(LLZS_TUNE_OLS_SEG_LEN); v >= 1 && v <= 1024) seg_len = v;
-    G.seg_len = seg_len;
-    G.segs_per_channel = (G.jobs_per_channel + seg_len - 1) / seg_len;
-    G.total_segs = (long)G.segs_per_channel * channels;
-    long blocks = (G.total_segs + 2 * OLS_WAVES - 1) / (2 * OLS_WAVES);
-    if (blocks > max_blocks) blocks = max_blocks;
-    const float2 *hf = reinterpret_cast<const float2 *>(hfreq), *tw = reinterpret_cast<const float2 *>(twid);
-    const dim3 grid((unsigned)blocks), block(OLS_THREADS);
-    hipLaunchKernelGGL(k_fir_ols_chain_f32, grid, block, lds_bytes, as_stream(stream), in, out, hist, hf, tw, G);
-    LLZ_LAUNCH_CHECK("k_fir_ols_f32");
-    return LLZ_OK;
-}
+// one overlap-save size: how its segments map onto workgroups, and the kernel instance built for each overlap
+struct ols_rung {
+    int nfft, min_taps;
+    const char *name;
+    int threads;                // per workgroup
+    int segs_per_wg;            // segments a workgroup walks at once: half-waves (1024), waves (2048, 4096), wave pairs (8192)
+    int wg_per_cu;              // resident workgroups per CU the grid is sized for (256 CUs)
+    bool tuned;                 // the ols_wg_per_cu and ols_seg_len tune knobs apply
+    double startup;             // segment-length cost: rounds x (length + startup)
+    size_t lds_bytes;
+    bool w2k, w4k;              // the kernel takes W_2048^n / W_4096^n
+    int count;                  // overlaps instantiated, ascending: the launch takes the smallest that holds flt_len - 1
+    int overlap[8];
+    const void *kernel[8];
+};
 
-// 258 .. 1025 taps on 2048-point transforms split over the two half-waves (k_fir_ols2k_chain_f32): hfreq2 = [2][1024] complex,
-// even then odd bins of DFT_2048(taps) / 2048 in natural order; twid as above; tw2k = [1024] complex W_2048^n
-extern "C" int llzs_fir_ols2k_f32(const float *in, float *out, const float *hist, const float *hfreq2, const float *twid,
-                                  const float *tw2k, int channels, int n, long in_pitch, long out_pitch, int flt_len,
-                                  void *stream)
-{
-    if (!in || !out || !hfreq2 || !twid || !tw2k || channels <= 0 || n <= 0 || in_pitch < n || out_pitch < n ||
-        flt_len < 2 || flt_len > 1025) {
-        llzs_set_error("fir_ols2k_f32: bad arguments (flt_len=%d, 2..1025)", flt_len);
-        return LLZ_ERR_ARG;
-    }
-    const int overlap = flt_len <= 513 ? 512 : 1024;
-    const int O2K_JOB = 2 * (2048 - overlap);
-    ols_geom G;
-    G.n = n;
-    G.keep = flt_len - 1;
-    G.in_pitch = in_pitch;
-    G.out_pitch = out_pitch;
-    G.jobs_per_channel = (n + O2K_JOB - 1) / O2K_JOB;
-    const size_t lds_bytes = 4 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float);
-    const long max_blocks = 256L * 2;
-    const long slots = max_blocks * OLS_WAVES;                  // a wave per segment
-    int seg_len = OLS_SEG;
-    if ((long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels < 4 * slots) {
-        double best = 1e300;
-        for (int sl = OLS_SEG; sl >= 1; sl--) {
-            const long segs = (long)((G.jobs_per_channel + sl - 1) / sl) * channels;
-            const double cost = (double)((segs + slots - 1) / slots) * (sl + 1.0);
-            if (cost < best * 0.999) { best = cost; seg_len = sl; }
-        }
-    }
-    G.seg_len = seg_len;
-    G.segs_per_channel = (G.jobs_per_channel + seg_len - 1) / seg_len;
-    G.total_segs = (long)G.segs_per_channel * channels;
-    long blocks = (G.total_segs + OLS_WAVES - 1) / OLS_WAVES;
-    if (blocks > max_blocks) blocks = max_blocks;
-    const float2 *hf = reinterpret_cast<const float2 *>(hfreq2), *tw = reinterpret_cast<const float2 *>(twid),
-                 *w2 = reinterpret_cast<const float2 *>(tw2k);
-    if (overlap == 512) {
-        LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_ols2k_chain_f32<512>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        hipLaunchKernelGGL(k_fir_ols2k_chain_f32<512>, dim3((unsigned)blocks), dim3(OLS_THREADS), lds_bytes, as_stream(stream),
-                           in, out, hist, hf, tw, w2, G);
-    } else {
-        LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_ols2k_chain_f32<1024>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        hipLaunchKernelGGL(k_fir_ols2k_chain_f32<1024>, dim3((unsigned)blocks), dim3(OLS_THREADS), lds_bytes, as_stream(stream),
-                           in, out, hist, hf, tw, w2, G);
-    }
-    LLZ_LAUNCH_CHECK("k_fir_ols2k_chain_f32");
-    return LLZ_OK;
-}
+template <typename K> static const void *kfn(K k) { return reinterpret_cast<const void *>(k); }
 
-// 514 .. 3073 taps on 4096-point transforms (k_fir_ols4k_f32; overlap 1024 / 2048 / 3072 by tap count): hfreq4 = [4][1024]
-// complex, plane j = bins 4m + j of DFT_4096(taps) / 4096; twid [32][32] W_1024^(ab); tw2k [1024] W_2048^n; tw4k [2048] W_4096^n
-template <int O>
-static int ols4k_launch(const float *in, float *out, const float *hist, const float *hfreq4, const float *twid,
-                        const float *tw2k, const float *tw4k, int channels, int n, long in_pitch, long out_pitch, int flt_len,
-                        void *stream)
-{
-    constexpr int JOB = 2 * (4096 - O);
-    ols_geom G;
-    G.n = n;
-    G.keep = flt_len - 1;
-    G.in_pitch = in_pitch;
-    G.out_pitch = out_pitch;
-    G.jobs_per_channel = (n + JOB - 1) / JOB;
-    const size_t lds_bytes = 8 * 1024 * sizeof(float2) + (size_t)O4K_WAVES * 2 * OLS_XBUF * sizeof(float);
-    const long max_blocks = 256L;                               // one 8-wave workgroup per CU
-    const long slots = max_blocks * O4K_WAVES;
-    int seg_len = OLS_SEG;
-    if ((long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels < 4 * slots) {
-        double best = 1e300;
-        for (int sl = OLS_SEG; sl >= 1; sl--) {
-            const long segs = (long)((G.jobs_per_channel + sl - 1) / sl) * channels;
-            const double cost = (double)((segs + slots - 1) / slots) * sl;
-            if (cost < best * 0.999) { best = cost; seg_len = sl; }
-        }
-    }
-    G.seg_len = seg_len;
-    G.segs_per_channel = (G.jobs_per_channel + seg_len - 1) / seg_len;
-    G.total_segs = (long)G.segs_per_channel * channels;
-    long blocks = (G.total_segs + O4K_WAVES - 1) / O4K_WAVES;
-    if (blocks > max_blocks) blocks = max_blocks;
-    LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_ols4k_f32<O>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(k_fir_ols4k_f32<O>, dim3((unsigned)blocks), dim3(O4K_THREADS), lds_bytes, as_stream(stream), in, out, hist,
-                       reinterpret_cast<const float2 *>(hfreq4), reinterpret_cast<const float2 *>(twid),
-                       reinterpret_cast<const float2 *>(tw2k), reinterpret_cast<const float2 *>(tw4k), G);
-    LLZ_LAUNCH_CHECK("k_fir_ols4k_f32");
-    return LLZ_OK;
-}
-
-extern "C" int llzs_fir_ols4k_f32(const float *in, float *out, const float *hist, const float *hfreq4, const float *twid,
-                                  const float *tw2k, const float *tw4k, int channels, int n, long in_pitch, long out_pitch,
-                                  int flt_len, void *stream)
-{
-    if (!in || !out || !hfreq4 || !twid || !tw2k || !tw4k || channels <= 0 || n <= 0 || in_pitch < n || out_pitch < n ||
-        flt_len < 2 || flt_len > LLZS_OLS4K_MAX_TAPS) {
-        llzs_set_error("fir_ols4k_f32: bad arguments (flt_len=%d, 2..%d)", flt_len, LLZS_OLS4K_MAX_TAPS);
-        return LLZ_ERR_ARG;
-    }
-    // the smallest overlap of the ladder that holds flt_len - 1 samples: a block yields 4096 - O outputs
-#define LLZ_OLS4K_GO(O) return ols4k_launch<O>(in, out, hist, hfreq4, twid, tw2k, tw4k, channels, n, in_pitch, out_pitch, flt_len, stream)
-    if (flt_len <= 513) LLZ_OLS4K_GO(512);
-    if (flt_len <= 769) LLZ_OLS4K_GO(768);
-    if (flt_len <= 1025) LLZ_OLS4K_GO(1024);
-    if (flt_len <= 1537) LLZ_OLS4K_GO(1536);
-    if (flt_len <= 2049) LLZ_OLS4K_GO(2048);
-    if (flt_len <= 2561) LLZ_OLS4K_GO(2560);
-    LLZ_OLS4K_GO(3072);
-#undef LLZ_OLS4K_GO
-}
-
-// 2 .. 6145 taps on 8192-point transforms (k_fir_ols8k_f32: a pair of waves per job; overlap 1536 / 2304 / ... / 6144 by tap
-// count): hfreq8 = [8][1024] complex, plane j = bins 8m + j of DFT_8192(taps) / 8192; twid [32][32] W_1024^(ab); tw4k [2048] W_4096^n
-template <int O>
-static int ols8k_launch(const float *in, float *out, const float *hist, const float *hfreq8, const float *twid,
-                        const float *tw4k, int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream)
-{
-    constexpr int JOB = 2 * (8192 - O);
-    ols_geom G;
-    G.n = n;
-    G.keep = flt_len - 1;
-    G.in_pitch = in_pitch;
-    G.out_pitch = out_pitch;
-    G.jobs_per_channel = (n + JOB - 1) / JOB;
-    const size_t lds_bytes = (1024 + 2048 + 8192) * sizeof(float2) + (size_t)O8K_WAVES * 2 * OLS_XBUF * sizeof(float) +
-                             2 * O8K_WAVES * sizeof(int) + 64 * sizeof(float2);
-    const long max_blocks = 256L;                               // one 8-wave workgroup per CU
-    const long slots = max_blocks * O8K_PAIRS;
-    int seg_len = OLS_SEG;
-    if ((long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels < 4 * slots) {
-        double best = 1e300;
-        for (int sl = OLS_SEG; sl >= 1; sl--) {
-            const long segs = (long)((G.jobs_per_channel + sl - 1) / sl) * channels;
-            const double cost = (double)((segs + slots - 1) / slots) * sl;
-            if (cost < best * 0.999) { best = cost; seg_len = sl; }
-        }
-    }
-    G.seg_len = seg_len;
-    G.segs_per_channel = (G.jobs_per_channel + seg_len - 1) / seg_len;
-    G.total_segs = (long)G.segs_per_channel * channels;
-    long blocks = (G.total_segs + O8K_PAIRS - 1) / O8K_PAIRS;
-    if (blocks > max_blocks) blocks = max_blocks;
-    LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_ols8k_f32<O>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(k_fir_ols8k_f32<O>, dim3((unsigned)blocks), dim3(O8K_THREADS), lds_bytes, as_stream(stream), in, out, hist,
-                       reinterpret_cast<const float2 *>(hfreq8), reinterpret_cast<const float2 *>(twid),
-                       reinterpret_cast<const float2 *>(tw4k), G);
-    LLZ_LAUNCH_CHECK("k_fir_ols8k_f32");
-    return LLZ_OK;
-}
-
-extern "C" int llzs_fir_ols8k_f32(const float *in, float *out, const float *hist, const float *hfreq8, const float *twid,
-                                  const float *tw4k, int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream)
-{
-    if (!in || !out || !hfreq8 || !twid || !tw4k || channels <= 0 || n <= 0 || in_pitch < n || out_pitch < n ||
-        flt_len < 2 || flt_len > LLZS_OLS8K_MAX_TAPS) {
-        llzs_set_error("fir_ols8k_f32: bad arguments (flt_len=%d, 2..%d)", flt_len, LLZS_OLS8K_MAX_TAPS);
-        return LLZ_ERR_ARG;
-    }
-#define LLZ_OLS8K_GO(O) return ols8k_launch<O>(in, out, hist, hfreq8, twid, tw4k, channels, n, in_pitch, out_pitch, flt_len, stream)
-    if (flt_len <= 1537) LLZ_OLS8K_GO(1536);
+const ols_rung OLS_RUNGS[] = {
+    // two workgroups per CU: 49 KB of LDS and ~240 registers per lane
+    {1024, 1, "k_fir_ols_f32", OLS_THREADS, 2 * OLS_WAVES, 2, true, 1.0,
+     2 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float), false, false,
+     1, {OLS_OVERLAP}, {kfn(k_fir_ols_chain_f32)}},
+    {2048, 2, "k_fir_ols2k_chain_f32", OLS_THREADS, OLS_WAVES, 2, false, 1.0,
+     4 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float), true, false,
+     2, {512, 1024}, {kfn(k_fir_ols2k_chain_f32<512>), kfn(k_fir_ols2k_chain_f32<1024>)}},
+    // one 8-wave workgroup per CU
+    {4096, 2, "k_fir_ols4k_f32", O4K_THREADS, O4K_WAVES, 1, false, 0.0,
+     8 * 1024 * sizeof(float2) + (size_t)O4K_WAVES * 2 * OLS_XBUF * sizeof(float), true, true,
+     7, {512, 768, 1024, 1536, 2048, 2560, 3072},
+     {kfn(k_fir_ols4k_f32<512>), kfn(k_fir_ols4k_f32<768>), kfn(k_fir_ols4k_f32<1024>), kfn(k_fir_ols4k_f32<1536>),
+      kfn(k_fir_ols4k_f32<2048>), kfn(k_fir_ols4k_f32<2560>), kfn(k_fir_ols4k_f32<3072>)}},
     // (a job costs 27 .. 31 us whatever the overlap between 2048 and 2560 -- 10.96 / 10.92 / 10.90 ms for 2048 / 2304 / 2560 on
     // the headline batch -- so the ladder is coarse there)
-    if (flt_len <= 2305) LLZ_OLS8K_GO(2304);
-    if (flt_len <= 2561) LLZ_OLS8K_GO(2560);
-    if (flt_len <= 3073) LLZ_OLS8K_GO(3072);
-    if (flt_len <= 3585) LLZ_OLS8K_GO(3584);
-    if (flt_len <= 4097) LLZ_OLS8K_GO(4096);
-    if (flt_len <= 5121) LLZ_OLS8K_GO(5120);
-    LLZ_OLS8K_GO(6144);
-#undef LLZ_OLS8K_GO
+    {8192, 2, "k_fir_ols8k_f32", O8K_THREADS, O8K_PAIRS, 1, false, 0.0,
+     (1024 + 2048 + 8192) * sizeof(float2) + (size_t)O8K_WAVES * 2 * OLS_XBUF * sizeof(float) + 2 * O8K_WAVES * sizeof(int) +
+         64 * sizeof(float2), false, true,
+     8, {1536, 2304, 2560, 3072, 3584, 4096, 5120, 6144},
+     {kfn(k_fir_ols8k_f32<1536>), kfn(k_fir_ols8k_f32<2304>), kfn(k_fir_ols8k_f32<2560>), kfn(k_fir_ols8k_f32<3072>),
+      kfn(k_fir_ols8k_f32<3584>), kfn(k_fir_ols8k_f32<4096>), kfn(k_fir_ols8k_f32<5120>), kfn(k_fir_ols8k_f32<6144>)}},
+};
+
+struct ols_plan {
+    int instance;               // index into the rung's overlaps
+    long blocks;
+    ols_geom G;
+};
+
+// the geometry of one call, on the host alone; flt_len is within the rung's range
+static ols_plan ols_plan_of(const ols_rung &r, int channels, int n, long in_pitch, long out_pitch, int flt_len)
+{
+    ols_plan p;
+    p.instance = 0;
+    while (r.overlap[p.instance] < flt_len - 1) p.instance++;
+    const int job = 2 * (r.nfft - r.overlap[p.instance]);     // new samples per transform: two blocks of nfft - overlap
+    ols_geom &G = p.G;
+    G.n = n;
+    G.keep = flt_len - 1;
+    G.in_pitch = in_pitch;
+    G.out_pitch = out_pitch;
+    G.jobs_per_channel = (n + job - 1) / job;
+    // one resident set of workgroups, grid stride over the segments
+    const int tuned_per_cu = r.tuned ? llzs_tune(LLZS_TUNE_OLS_WG_PER_CU) : -1;
+    const long max_blocks = 256L * (tuned_per_cu > 0 ? tuned_per_cu : r.wg_per_cu);
+    const long slots = max_blocks * r.segs_per_wg;
+    // jobs per segment: a segment walks seg_len consecutive jobs of one channel (the overlap stays in registers), at most
+    // OLS_SEG.  Small batches (BASELINE config 2: 64 channels) would leave segment slots idle or quantise badly into rounds
+    // with the full length, so they take the length that minimises the cost in rounds.  Large batches keep the full length:
+    // on 4096 channels a shorter segment measured 2.6 % slower (1024 points).
+    int seg_len = OLS_SEG;
+    if ((long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels < 4 * slots) {
+        double best = 1e300;
+        for (int sl = OLS_SEG; sl >= 1; sl--) {
+            const long segs = (long)((G.jobs_per_channel + sl - 1) / sl) * channels;
+            const double cost = (double)((segs + slots - 1) / slots) * (sl + r.startup);
+            if (cost < best * 0.999) { best = cost; seg_len = sl; }
+        }
+    }
+    if (r.tuned)
+        if (const int v = llzs_tune(LLZS_TUNE_OLS_SEG_LEN); v >= 1 && v <= 1024) seg_len = v;
+    G.seg_len = seg_len;
+    G.segs_per_channel = (G.jobs_per_channel + seg_len - 1) / seg_len;
+    G.total_segs = (long)G.segs_per_channel * channels;
+    p.blocks = (G.total_segs + r.segs_per_wg - 1) / r.segs_per_wg;
+    if (p.blocks > max_blocks) p.blocks = max_blocks;
+    return p;
+}
+
+} // namespace
+
+extern "C" int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float *in, float *out, const float *hist, int channels,
+                                int n, long in_pitch, long out_pitch, int flt_len, void *stream)
+{
+    const ols_rung *r = nullptr;
+    for (const ols_rung &c : OLS_RUNGS)
+        if (c.nfft == nfft) r = &c;
+    if (!r || !t || !t->hfreq || !t->twid || (r->w2k && !t->tw2k) || (r->w4k && !t->tw4k) || !in || !out || channels <= 0 ||
+        n <= 0 || in_pitch < n || out_pitch < n) {
+        llzs_set_error("fir_ols_f32: bad arguments (%d points)", nfft);
+        return LLZ_ERR_ARG;
+    }
+    if (flt_len < r->min_taps || flt_len - 1 > r->overlap[r->count - 1]) {
+        llzs_set_error("fir_ols_f32: flt_len %d outside %d..%d (%d points)", flt_len, r->min_taps, r->overlap[r->count - 1] + 1,
+                       nfft);
+        return LLZ_ERR_RANGE;
+    }
+    ols_plan p = ols_plan_of(*r, channels, n, in_pitch, out_pitch, flt_len);
+    const float2 *hf = reinterpret_cast<const float2 *>(t->hfreq), *tw = reinterpret_cast<const float2 *>(t->twid),
+                 *w2 = reinterpret_cast<const float2 *>(t->tw2k), *w4 = reinterpret_cast<const float2 *>(t->tw4k);
+    void *args[8] = {&in, &out, &hist, &hf, &tw};              // the kernels' parameters: w2 and w4 where the rung takes them
+    int k = 5;
+    if (r->w2k) args[k++] = &w2;
+    if (r->w4k) args[k++] = &w4;
+    args[k] = &p.G;
+    const void *kernel = r->kernel[p.instance];
+    if (r->lds_bytes > 64 * 1024)
+        LLZ_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+    (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(r->threads), args, r->lds_bytes, as_stream(stream));
+    LLZ_LAUNCH_CHECK(r->name);
+    return LLZ_OK;
 }
 
 #ifdef O8K_TRACE

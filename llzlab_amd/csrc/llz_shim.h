@@ -91,34 +91,21 @@ int  llzs_tables_broadcast_ranks(void);     /* ranks of the RCCL communicator th
 
 /* ---- FIR ---- */
 #define LLZS_FIR_TAP_PAD 8      /* time-domain kernels read taps in groups of 8: pad the table with zeros */
-#define LLZS_OLS_NFFT   1024
-#define LLZS_OLS_MAX_TAPS 257   /* overlap = 256, 768 new samples per 1024-point block */
 
 /* y[c][i] = sum_k taps[k] * x[c][i-k]; x[c][i<0] = hist[c][flt_len-1+i] (hist NULL = zeros).
  * in/out planar with row pitch in_pitch/out_pitch elements. taps: flt_len floats padded to a multiple of 8. */
 int llzs_fir_td_f32(const float *in, float *out, const float *hist, const float *taps_padded,
                     int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream);
 int llzs_fir_td_f32_fits(int flt_len);      /* 1 when the taps fit the time-domain kernel's LDS tile */
-/* overlap-save: hfreq = 1024 complex floats, FFT(taps)/1024 in natural bin order; twid = 32x32 complex
- * W_1024^(a*b).  Requires flt_len <= 257. */
-int llzs_fir_ols_f32(const float *in, float *out, const float *hist, const float *hfreq, const float *twid,
-                     int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream);
-/* overlap-save with 2048-point transforms split over the two half-waves of a wave (fir_ols.hip), 2..1025 taps: hfreq2 [2][1024] complex =
- * even then odd bins of DFT_2048(taps) / 2048, twid [32][32] W_1024^(ab), tw2k [1024] W_2048^n */
-int llzs_fir_ols2k_f32(const float *in, float *out, const float *hist, const float *hfreq2, const float *twid,
-                       const float *tw2k, int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream);
-#define LLZS_OLS2K_MAX_TAPS 1025
-/* 4096-point transforms on a whole wave (fir_ols.hip: radix-2 step + two 2048-point problems), 2..3073 taps (overlap 512 / 1024 / 2048 / 3072 by tap count): hfreq4 [4][1024]
- * complex = bins 4m + j of DFT_4096(taps) / 4096; twid [32][32] W_1024^(ab); tw2k [1024] W_2048^n; tw4k [2048] W_4096^n */
-int llzs_fir_ols4k_f32(const float *in, float *out, const float *hist, const float *hfreq4, const float *twid,
-                       const float *tw2k, const float *tw4k, int channels, int n, long in_pitch, long out_pitch, int flt_len,
-                       void *stream);
-#define LLZS_OLS4K_MAX_TAPS 3073
-/* 8192-point transforms on a pair of waves (fir_ols.hip: radix-2 step across the pair + the 4096-point problem per wave), 2..6145
- * taps (overlap 1536 ... 6144 by tap count): hfreq8 [8][1024] complex = bins 8m + j of DFT_8192(taps) / 8192; twid, tw4k as above */
-int llzs_fir_ols8k_f32(const float *in, float *out, const float *hist, const float *hfreq8, const float *twid,
-                       const float *tw4k, int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream);
-#define LLZS_OLS8K_MAX_TAPS 6145
+/* overlap-save with nfft = 1024, 2048, 4096 or 8192 points (fir_ols.hip): 1..257, 2..1025, 2..3073 or 2..6145 taps.  The
+ * tables, all complex floats: hfreq = DFT_nfft(taps) / nfft as P = nfft / 1024 planes of 1024 (bin k in plane k mod P, row
+ * k / P; P = 1 is natural order), twid = [32][32] W_1024^(ab), tw2k = [1024] W_2048^n (2048 and 4096 points, else NULL),
+ * tw4k = [2048] W_4096^n (4096 and 8192 points, else NULL). */
+typedef struct {
+    float *hfreq, *twid, *tw2k, *tw4k;
+} llzs_ols_tables;
+int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float *in, float *out, const float *hist, int channels,
+                     int n, long in_pitch, long out_pitch, int flt_len, void *stream);
 /* time domain on the fp32 matrix cores (v_mfma_f32_16x16x4_f32), with optional decimation:
  * y[c][i] = gain * sum_{k<T} taps[k] * x[c][i*M - k], x[c][<0] = hist[c][T-1+idx] (hist NULL = zeros); n_out outputs
  * per channel from n_in inputs, (n_out-1)*M < n_in.  taps: T floats (no padding needed). */

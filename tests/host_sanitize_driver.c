@@ -52,9 +52,9 @@ int main(void)
     llz_iir_filter_uninit(h);
     /* batch FIR: every algorithm, host buffers (staging), flush, wrong sizes */
     const int algos[] = {LLZ_FIR_ALGO_AUTO, LLZ_FIR_ALGO_TIME, LLZ_FIR_ALGO_OVERLAP_SAVE, LLZ_FIR_ALGO_TIME_MFMA,
-                         LLZ_FIR_ALGO_OVERLAP_SAVE_2048, LLZ_FIR_ALGO_OVERLAP_SAVE_4096};
-    const int taps_n[] = {257, 63, 200, 300, 700, 2049};
-    for (int i = 0; i < 6; i++) {
+                         LLZ_FIR_ALGO_OVERLAP_SAVE_2048, LLZ_FIR_ALGO_OVERLAP_SAVE_4096, LLZ_FIR_ALGO_OVERLAP_SAVE_8192};
+    const int taps_n[] = {257, 63, 200, 300, 700, 2049, 4000};
+    for (int i = 0; i < 7; i++) {
         float *t = calloc((size_t)taps_n[i], sizeof(float));
         h = llz_fir_filter_mc_init(4, 1000, t, taps_n[i], algos[i]);
         CHECK(h != BAD);
