@@ -251,30 +251,50 @@ int llz_resample(unsigned long handle, unsigned char *sample_in, int sample_in_s
  * Part 2: multi-channel rational resampler
  * ===================================================================================================== */
 
+/* The shim entries that run a batch handle.  rsm_choose picks a primary and a fallback at init and again in set_matrix; the
+ * first row that applies wins:
+ *   format    primary              when                                                     fallback
+ *   F32       fir_mfma_f32         L = 1, it fits, rs_dec_valu != 1                         -
+ *   F32       resample_dec_f32     L = 1, it fits (M, tp)                                   -
+ *   F32       resample_mfma_f32    it fits, rs_generic < 1                                  resample_f32
+ *   F32       resample_f32         otherwise                                                -
+ *   I16       fir_mfma_i16x        L = 1, the screen takes the taps, rs_i16_path != 1       resample_i16
+ *   I16       resample_i16x        L >= 2, the screen takes the taps, rs_i16_path != 1      resample_i16
+ *   I16       resample_i16         otherwise                                                -
+ *   I16_FAST  fir_mfma_i16x        the screen takes the taps, rs_i16_path != 1              fir_mfma_i16
+ *   I16_FAST  fir_mfma_i16         otherwise                                                -
+ * A primary declines a call when rsm_path_ok refuses it or the entry returns LLZ_ERR_RANGE (a frame too short for a screened
+ * kernel); the fallback then runs, and the primary's message stays in llz_hip_last_error().  RSM_TABLES lists the tables
+ * each entry reads: a handle uploads those of its primary and its fallback, in the order of the TAB_ values. */
+typedef enum {
+    RSM_NONE, RSM_FIR_MFMA_F32, RSM_DEC_F32, RSM_MFMA_F32, RSM_F32, RSM_FIR_MFMA_I16X, RSM_I16X, RSM_I16, RSM_FIR_MFMA_I16
+} rsm_path;
+enum { TAB_M32 = 1, TAB_M64 = 2, TAB_BAND = 4, TAB_PHASE = 8, TAB_SCREEN = 16 };
+static const int RSM_TABLES[] = {
+    [RSM_NONE] = 0, [RSM_FIR_MFMA_F32] = TAB_M32, [RSM_DEC_F32] = TAB_PHASE, [RSM_MFMA_F32] = TAB_BAND, [RSM_F32] = TAB_M32,
+    [RSM_FIR_MFMA_I16X] = TAB_M64 | TAB_SCREEN, [RSM_I16X] = TAB_M64 | TAB_SCREEN, [RSM_I16] = TAB_M64, [RSM_FIR_MFMA_I16] = TAB_M32,
+};
+
 typedef struct {
     int tag;
     int channels, L, M, fmt, Q;
     double gain;
     tapmat_t taps;
-    void *d_mat;                /* float (F32) or double (I16) L x Q */
-    float *d_phase;             /* F32, L == 1: M x tp phase taps for the polyphase fast path (NULL otherwise) */
+    rsm_path primary, fallback;
+    void *d_m32;                /* TAB_M32: the L x Q taps as floats */
+    void *d_m64;                /* TAB_M64: the L x Q taps as doubles (the all-double kernel, the screen's second looks) */
+    void *d_band, *d_band_c0;   /* TAB_BAND: the banded tap matrix in matrix-core operand order (resample_mfma.hip) */
+    void *d_phase;              /* TAB_PHASE, L == 1: M x tp phase taps (resample_dec_f32) */
     int tp;
-    int use_mfma;               /* F32, L == 1: decimating FIR on the matrix cores (fir_mfma.hip) */
-    /* I16, L == 1: the bit-exact path screened on the matrix cores (fir_mfma_i8.hip) */
-    int use_screen, screen_shift;
+    /* TAB_SCREEN: the bit-exact int16 screen's fixed-point taps (fir_mfma_i8.hip for L = 1, resample_i8.hip for L >= 2); L = 1
+     * takes a bias, L >= 2 a flag: some phase is a single tap 1.0 at gain 1.0 (its outputs are integers) */
+    int screen_shift, screen_any_exact;
     long long screen_bias;
     double screen_eps;
-    int screen_any_exact;               /* general L/M: some phase is a single tap 1.0 at gain 1.0 (its outputs are integers) */
-    signed char *d_digits;      /* [LLZS_MX_PLANES][Q] */
-    /* I16, L >= 2: the same screen per phase, on the phase-tile mapping (resample_i8.hip) */
-    int use_screen_lm;
-    signed char *d_scr_atab;    /* [ceil(L/16)][steps][5][64][16] tap digits in matrix-core operand order */
-    int *d_scr_aoff;            /* [ceil(L/16)] band starts */
-    int *d_scr_bq;              /* [16 ceil(L/16)][4] per phase: bias (lo, hi), e32, exact flag */
-    /* F32, L >= 5: the banded tap matrix in matrix-core operand order (resample_mfma.hip) */
-    float *d_band;
-    int *d_band_c0;
-    double *d_gd;                       /* LLZ_PCM_I16_FAST on the screened kernel: the double taps of its second looks */
+    void *d_digits;             /* L = 1: [LLZS_MX_PLANES][Q] */
+    void *d_scr_atab;           /* L >= 2: [ceil(L/16)][steps][LLZS_MX_PLANES][64][16] tap digits in matrix-core operand order */
+    void *d_scr_aoff;           /* [ceil(L/16)] band starts */
+    void *d_scr_bq;             /* [16 ceil(L/16)][4] per phase: bias (lo, hi), e32, exact flag */
     void *d_hist[2];            /* [channels][Q-1] samples of the handle's format, ping-pong */
     int cur;
     long long in_count, out_count;   /* samples consumed / produced per channel so far */
@@ -283,104 +303,42 @@ typedef struct {
     llz_stage_t st_in, st_out;
 } rsm_t;
 
+/* a path's call-time precondition: the period-tile kernels need the call to start on a period boundary */
+static int rsm_path_ok(const rsm_t *r, rsm_path p)
+{
+    return (p != RSM_MFMA_F32 && p != RSM_I16X) || (r->in_count % r->M == 0 && r->out_count % r->L == 0);
+}
+
 static size_t rsm_sample_bytes(const rsm_t *r) { return r->fmt == LLZ_PCM_F32 ? sizeof(float) : sizeof(short); }
 
 static void rsm_destroy(rsm_t *r)
 {
     if (!r) return;
     tapmat_free(&r->taps);
-    llzs_free(r->d_mat); llzs_free(r->d_phase); llzs_free(r->d_digits); llzs_free(r->d_scr_atab); llzs_free(r->d_scr_aoff);
-    llzs_free(r->d_scr_bq); llzs_free(r->d_band); llzs_free(r->d_band_c0); llzs_free(r->d_gd); llzs_free(r->d_hist[0]); llzs_free(r->d_hist[1]);
+    llzs_free(r->d_m32); llzs_free(r->d_m64); llzs_free(r->d_band); llzs_free(r->d_band_c0); llzs_free(r->d_phase); llzs_free(r->d_digits);
+    llzs_free(r->d_scr_atab); llzs_free(r->d_scr_aoff); llzs_free(r->d_scr_bq); llzs_free(r->d_hist[0]); llzs_free(r->d_hist[1]);
     llz_stage_release(&r->st_in); llz_stage_release(&r->st_out);
     r->tag = 0;
     free(r);
 }
 
-/* Screen tables of the bit-exact int16 decimator (fir_mfma_i8.hip): fixed-point taps G[k] = round(gain g[k] 2^shift) as
- * five balanced base-256 digits, the constant 128 sum G[k] of the samples' +128 offset, and eps, a bound on the distance
- * between the screen's value v = S 2^-shift and the reference's double result y = fl(fl(sum x g) gain)
- * (llz_resample.c:590-594), for |x| <= 32768 and u = 2^-53:
- *   tap quantisation     |sum x (gain g - G 2^-shift)|    <= 32768 sum_k |fl(gain g[k]) - G[k] 2^-shift|   (evaluated below)
- *                        + the rounding of fl(gain g[k])   <= 32768 u |gain| sum_k |g[k]|
- *   reference's sum      |fl(sum x g) - sum x g|          <= Q u / (1 - Q u) sum |x g| <= Q 2^-52 32768 sum_k |g[k]|
- *   reference's * gain   one more rounding of a value <= 32768 |gain| sum|g|
- * eps = 2 (the sum of those) + 2^-30 + (the integer terms the kernel does not form, see below): the factor 2 and the constant
- * are margin (they also cover this function's own floating-point sums).  Returns 0 when the taps do not suit the screen (the all-double kernel then runs). */
-static int rsm_build_screen(rsm_t *r)
+/* uploads one table, allocating its device buffer on first use (set_matrix uploads into the same buffer again) */
+static int rsm_put(void **dev, const void *src, size_t bytes)
 {
-    const int Q = r->Q;
-    const double *g = r->taps.mat;
-    const double gain = r->gain;
-    double maxabs = 0.0, sumabs = 0.0;
-    for (int k = 0; k < Q; k++) {
-        const double a = fabs(g[k] * gain);
-        if (!(a < 1e30)) return 0;
-        if (a > maxabs) maxabs = a;
-        sumabs += a;
-    }
-    if (maxabs == 0.0 || !llzs_fir_mfma_i16x_fits(Q, r->M)) return 0;
-    int e_max, e_sum;
-    (void)frexp(maxabs, &e_max);                        /* maxabs < 2^e_max */
-    (void)frexp(sumabs, &e_sum);
-    int shift = 38 - e_max;                             /* |G| < 2^38: five balanced digits hold it */
-    if (shift > 46 - e_sum) shift = 46 - e_sum;         /* 2^15 sum|G| < 2^62: the int64 total cannot wrap */
-    if (shift > 46) shift = 46;
-    if (shift < 32) return 0;                           /* (gains above ~64: the integer decision needs shift >= 32) */
-    signed char *digits = (signed char *)malloc((size_t)LLZS_MX_PLANES * Q);
-    if (!digits) return 0;
-    long long sumG = 0, sum_d0 = 0;
-    double qerr = 0.0;
-    int ok = 1;
-    for (int k = 0; k < Q; k++) {
-        const double gk = g[k] * gain;
-        long long G = llround(ldexp(gk, shift));
-        qerr += fabs(gk - ldexp((double)G, -shift));
-        sumG += G;
-        for (int p = 0; p < LLZS_MX_PLANES; p++) {
-            const int d = (int)(((G + 128) & 255) - 128);            /* balanced digit in [-128, 127] */
-            digits[(size_t)p * Q + k] = (signed char)d;
-            if (p == 0) sum_d0 += d < 0 ? -d : d;
-            G = (G - d) / 256;
-        }
-        if (G != 0) ok = 0;
-    }
-    /* the kernel leaves out two integer terms of S = sum x G: the product of the samples' low digit (|.| <= 128) with the
-     * taps' lowest digit, |.| <= 128 sum|d_0|, and the low 8 bits of the bias 128 sum G, < 256 -- both exact bounds, in
-     * units of 2^-shift */
-    const double eps = 2.0 * 32768.0 * (qerr + (double)(Q + 2) * ldexp(1.0, -52) * sumabs) + ldexp(1.0, -30) +
-                       ldexp(128.0 * (double)sum_d0 + 256.0, -shift);
-    if (ok && eps < 0.0625) {
-        if (!r->d_digits) r->d_digits = (signed char *)llzs_malloc((size_t)LLZS_MX_PLANES * Q);
-        ok = r->d_digits && llzs_h2d_table(r->d_digits, digits, (size_t)LLZS_MX_PLANES * Q) == LLZ_OK;
-    } else {
-        ok = 0;
-    }
-    free(digits);
-    if (ok) {
-        r->screen_shift = shift;
-        r->screen_bias = 128 * sumG;
-        r->screen_eps = eps;
-    }
-    return ok;
+    if (!*dev) *dev = llzs_malloc(bytes);
+    return *dev ? llzs_h2d_table(*dev, src, bytes) : LLZ_ERR_NOMEM;
 }
 
-/* The same screen for L >= 2 (resample_i8.hip): one tap row per phase f, g_f[k] = taps.mat[f][k]; ONE shift for all rows (from
- * the largest |gain g|), per-row digits, bias and error bound (the formulas of rsm_build_screen with the row's own sums), eps =
- * the largest row bound.  The digits go straight into matrix-core operand order: phase tile t = phases 16 t .. 16 t + 15; its
- * band starts at window position a_t = c_{16t} + Hp - (Q-1) (Hp = Q-1 rounded up to 8, the position of a period's own
- * first sample; c_f = (f M) / L); lane (r = lane % 16, kq = lane / 16) of step s and digit plane p holds, in byte j, digit p of
- * the tap of phase f = 16 t + r that multiplies window position pos = a_t + 64 s + 16 chunk(kq) + j, i.e. tap k = c_f + Hp - pos
- * (chunk(kq) = ((kq & 1) << 1) | (kq >> 1): kernels/screen_i8.hpp). */
-static int rsm_build_screen_lm(rsm_t *r)
+/* The screen of the bit-exact int16 kernels works on fixed-point taps G[k] = round(gain g[k] 2^shift), one shift for all
+ * rows.  scr_shift picks it from the largest |gain g| and the largest row sum of |gain g|; 0 when the taps do not suit the
+ * screen. */
+static int scr_shift(const double *g, int rows, int Q, double gain)
 {
-    const int L = r->L, M = r->M, Q = r->Q, nt = (L + 15) / 16;
-    const double gain = r->gain;
-    if (!llzs_resample_i16x_fits(L, M, Q)) return 0;
     double maxabs = 0.0, max_sumabs = 0.0;
-    for (int f = 0; f < L; f++) {
+    for (int f = 0; f < rows; f++) {
         double sumabs = 0.0;
         for (int k = 0; k < Q; k++) {
-            const double a = fabs(r->taps.mat[(size_t)f * Q + k] * gain);
+            const double a = fabs(g[(size_t)f * Q + k] * gain);
             if (!(a < 1e30)) return 0;
             if (a > maxabs) maxabs = a;
             sumabs += a;
@@ -389,63 +347,109 @@ static int rsm_build_screen_lm(rsm_t *r)
     }
     if (maxabs == 0.0) return 0;
     int e_max, e_sum;
-    (void)frexp(maxabs, &e_max);
+    (void)frexp(maxabs, &e_max);                        /* maxabs < 2^e_max */
     (void)frexp(max_sumabs, &e_sum);
     int shift = 38 - e_max;                             /* |G| < 2^38: five balanced digits hold it */
-    if (shift > 46 - e_sum) shift = 46 - e_sum;         /* 2^15 sum|G| < 2^62 */
+    if (shift > 46 - e_sum) shift = 46 - e_sum;         /* 2^15 sum|G| < 2^62: the int64 total cannot wrap */
     if (shift > 46) shift = 46;
-    if (shift < 32) return 0;
+    return shift < 32 ? 0 : shift;                      /* (gains above ~64: the integer decision needs shift >= 32) */
+}
+
+/* Quantises one row of Q taps at `shift` into dig[LLZS_MX_PLANES][Q], balanced base-256 digits lowest first, sets *bias to
+ * 128 sum G[k] (the constant of the samples' +128 offset) and returns the row's eps, a bound on the distance between the
+ * screen's value v = S 2^-shift and the reference's double result y = fl(fl(sum x g) gain) (llz_resample.c:590-594), for
+ * |x| <= 32768 and u = 2^-53:
+ *   tap quantisation     |sum x (gain g - G 2^-shift)|    <= 32768 sum_k |fl(gain g[k]) - G[k] 2^-shift|   (evaluated below)
+ *                        + the rounding of fl(gain g[k])   <= 32768 u |gain| sum_k |g[k]|
+ *   reference's sum      |fl(sum x g) - sum x g|          <= Q u / (1 - Q u) sum |x g| <= Q 2^-52 32768 sum_k |g[k]|
+ *   reference's * gain   one more rounding of a value <= 32768 |gain| sum|g|
+ * eps = 2 (the sum of those) + 2^-30 + (the integer terms the kernel does not form, see below): the factor 2 and the constant
+ * are margin (they also cover this function's own floating-point sums).  HUGE_VAL when a tap needs more than five digits. */
+static double scr_row(const double *g, int Q, double gain, int shift, signed char *dig, long long *bias)
+{
+    long long sumG = 0, sum_d0 = 0;
+    double qerr = 0.0, sumabs = 0.0;
+    for (int k = 0; k < Q; k++) {
+        const double gk = g[k] * gain;
+        long long G = llround(ldexp(gk, shift));
+        qerr += fabs(gk - ldexp((double)G, -shift));
+        sumabs += fabs(gk);
+        sumG += G;
+        for (int p = 0; p < LLZS_MX_PLANES; p++) {
+            const int d = (int)(((G + 128) & 255) - 128);            /* balanced digit in [-128, 127] */
+            dig[(size_t)p * Q + k] = (signed char)d;
+            if (p == 0) sum_d0 += d < 0 ? -d : d;
+            G = (G - d) / 256;
+        }
+        if (G != 0) return HUGE_VAL;
+    }
+    *bias = 128 * sumG;
+    /* the kernel leaves out two integer terms of S = sum x G: the product of the samples' low digit (|.| <= 128) with the
+     * taps' lowest digit, |.| <= 128 sum|d_0|, and the low 8 bits of the bias 128 sum G, < 256 -- both exact bounds, in
+     * units of 2^-shift */
+    return 2.0 * 32768.0 * (qerr + (double)(Q + 2) * ldexp(1.0, -52) * sumabs) + ldexp(1.0, -30) +
+           ldexp(128.0 * (double)sum_d0 + 256.0, -shift);
+}
+
+/* L = 1: the one row's digits as they are.  Returns 0 when the screen declines the taps. */
+static int rsm_put_screen(rsm_t *r)
+{
+    const int Q = r->Q, shift = scr_shift(r->taps.mat, 1, Q, r->gain);
+    const size_t bytes = (size_t)LLZS_MX_PLANES * Q;
+    signed char *digits = shift ? (signed char *)malloc(bytes) : NULL;
+    if (!digits) return 0;
+    long long bias = 0;
+    const double eps = scr_row(r->taps.mat, Q, r->gain, shift, digits, &bias);
+    const int rc = eps < 0.0625 ? rsm_put(&r->d_digits, digits, bytes) : LLZ_ERR_RANGE;
+    free(digits);
+    r->screen_shift = shift; r->screen_bias = bias; r->screen_eps = eps;      /* (read only when the screen takes the taps) */
+    return rc == LLZ_OK;
+}
+
+/* L >= 2: one tap row per phase f, g_f[k] = taps.mat[f][k], per-row digits, bias and bound; eps = the largest row bound.  The
+ * digits go straight into matrix-core operand order: phase tile t = phases 16 t .. 16 t + 15; its band starts at window
+ * position a_t = c_{16t} + Hp - (Q-1) (Hp = Q-1 rounded up to 8, the position of a period's own first sample; c_f =
+ * (f M) / L); lane (r = lane % 16, kq = lane / 16) of step s and digit plane p holds, in byte j, digit p of the tap of phase
+ * f = 16 t + r that multiplies window position pos = a_t + 64 s + 16 chunk(kq) + j, i.e. tap k = c_f + Hp - pos
+ * (chunk(kq) = ((kq & 1) << 1) | (kq >> 1): kernels/screen_i8.hpp).  Returns 0 when the screen declines the taps. */
+static int rsm_put_screen_lm(rsm_t *r)
+{
+    const int L = r->L, M = r->M, Q = r->Q, nt = (L + 15) / 16, P = LLZS_MX_PLANES, shift = scr_shift(r->taps.mat, L, Q, r->gain);
+    if (!shift) return 0;
     const int steps = llzs_resample_i16x_ksteps(L, M, Q), Hp = (Q - 1 + 7) & ~7;
-    const size_t abytes = (size_t)nt * steps * 5 * 1024;
-    signed char *atab = (signed char *)calloc(abytes, 1);
-    signed char *dig = (signed char *)malloc((size_t)5 * Q);
+    const size_t abytes = (size_t)nt * steps * P * 1024;
+    signed char *atab = (signed char *)calloc(abytes, 1), *dig = (signed char *)malloc((size_t)P * Q);
     int *aoff = (int *)calloc((size_t)nt, sizeof(int)), *bq = (int *)calloc((size_t)nt * 64, sizeof(int));
-    int ok = atab && dig && aoff && bq;
-    double eps = 0.0;
+    double eps = atab && dig && aoff && bq ? 0.0 : HUGE_VAL;
     int any_exact = 0;
-    for (int f = 0; ok && f < L; f++) {
+    for (int f = 0; eps < 0.0625 && f < L; f++) {
         const double *g = r->taps.mat + (size_t)f * Q;
         const int t = f / 16, row = f % 16, cf = (int)(((long)f * M) / L);
         const int a_t = (int)(((long)16 * t * M) / L) + Hp - (Q - 1);
         aoff[t] = a_t;
-        long long sumG = 0, sum_d0 = 0;
-        double qerr = 0.0, sumabs = 0.0;
-        int nonzero = 0, unit = 0, kfirst = Q - 1, klast = 0;
-        for (int k = 0; k < Q; k++) {
-            const double gk = g[k] * gain;
-            long long G = llround(ldexp(gk, shift));
-            qerr += fabs(gk - ldexp((double)G, -shift));
-            sumabs += fabs(gk);
-            sumG += G;
-            nonzero += g[k] != 0.0;
-            unit += g[k] == 1.0;
-            if (g[k] != 0.0) {
-                if (k < kfirst) kfirst = k;
-                if (k > klast) klast = k;
-            }
-            for (int p = 0; p < 5; p++) {
-                const int d = (int)(((G + 128) & 255) - 128);
-                dig[(size_t)p * Q + k] = (signed char)d;
-                if (p == 0) sum_d0 += d < 0 ? -d : d;
-                G = (G - d) / 256;
-            }
-            if (G != 0) ok = 0;
-        }
-        const double e = 2.0 * 32768.0 * (qerr + (double)(Q + 2) * ldexp(1.0, -52) * sumabs) + ldexp(1.0, -30) +
-                         ldexp(128.0 * (double)sum_d0 + 256.0, -shift);
+        long long bias;
+        const double e = scr_row(g, Q, r->gain, shift, dig, &bias);
         if (e > eps) eps = e;
-        const long long bias = 128 * sumG, bqv = bias >= 0 ? bias / 256 : -((-bias + 255) / 256);      /* floor(bias / 256) */
+        if (!(eps < 0.0625)) break;
+        const long long bqv = bias >= 0 ? bias / 256 : -((-bias + 255) / 256);      /* floor(bias / 256) */
         bq[4 * f] = (int)(unsigned)((unsigned long long)bqv & 0xffffffffull);
         bq[4 * f + 1] = (int)(bqv >> 32);
         bq[4 * f + 2] = (int)((unsigned)ceil(ldexp(e, 32)) + 2u);
+        int nonzero = 0, unit = 0, kfirst = Q - 1, klast = 0;
+        for (int k = 0; k < Q; k++)
+            if (g[k] != 0.0) {
+                if (!nonzero++) kfirst = k;
+                unit += g[k] == 1.0;
+                klast = k;
+            }
         /* a phase whose only non-zero tap is exactly 1.0, at gain 1.0 (phase 0 whenever fc = 1/L: the windowed sinc is zero at
          * the other multiples of L): the reference's y is the sample itself, an integer, and so is the screen's value -- bit
          * for bit (G = 2^shift, every digit product exact, lowest digit and bias remainder zero).  Every such output would
-         * otherwise take the recompute path: one lane row in 16 of that phase tile, 47 double steps each. */
+         * otherwise take the recompute path: one lane row in 16 of that phase tile, 47 double steps each.  A phase without any
+         * tap: every output is the integer 0, whatever the gain.  (The recompute path runs taps kfirst .. klast only: zero taps
+         * in front and behind add +-0 to the reference's sum.) */
         if (nonzero == 0) kfirst = klast = 0;
-        /* (the recompute path runs taps kfirst .. klast only: zero taps in front and behind add +-0 to the reference's sum) */
-        /* (a phase without any tap: every output is the integer 0, whatever the gain) */
-        const int exact = nonzero == 0 || (nonzero == 1 && unit == 1 && gain == 1.0);
+        const int exact = nonzero == 0 || (nonzero == 1 && unit == 1 && r->gain == 1.0);
         any_exact |= exact;
         bq[4 * f + 3] = kfirst | (klast << 8) | (exact ? 1 << 16 : 0);
         for (int s = 0; s < steps; s++)
@@ -454,93 +458,97 @@ static int rsm_build_screen_lm(rsm_t *r)
                     const int pos = a_t + 64 * s + 16 * (((kq & 1) << 1) | (kq >> 1)) + j;
                     const int k = cf + Hp - pos;
                     if (k < 0 || k >= Q) continue;
-                    for (int p = 0; p < 5; p++)
-                        atab[((((size_t)t * steps + s) * 5 + p) * 64 + (size_t)(16 * kq + row)) * 16 + j] = dig[(size_t)p * Q + k];
+                    for (int p = 0; p < P; p++)
+                        atab[((((size_t)t * steps + s) * P + p) * 64 + (size_t)(16 * kq + row)) * 16 + j] = dig[(size_t)p * Q + k];
                 }
     }
-    if (ok && eps < 0.0625) {
-        if (!r->d_scr_atab) r->d_scr_atab = (signed char *)llzs_malloc(abytes);
-        if (!r->d_scr_aoff) r->d_scr_aoff = (int *)llzs_malloc(sizeof(int) * (size_t)nt);
-        if (!r->d_scr_bq) r->d_scr_bq = (int *)llzs_malloc(sizeof(int) * (size_t)nt * 64);
-        ok = r->d_scr_atab && r->d_scr_aoff && r->d_scr_bq && llzs_h2d_table(r->d_scr_atab, atab, abytes) == LLZ_OK &&
-             llzs_h2d_table(r->d_scr_aoff, aoff, sizeof(int) * (size_t)nt) == LLZ_OK &&
-             llzs_h2d_table(r->d_scr_bq, bq, sizeof(int) * (size_t)nt * 64) == LLZ_OK;
-    } else {
-        ok = 0;
-    }
+    int rc = eps < 0.0625 ? rsm_put(&r->d_scr_atab, atab, abytes) : LLZ_ERR_RANGE;
+    if (rc == LLZ_OK) rc = rsm_put(&r->d_scr_aoff, aoff, sizeof(int) * (size_t)nt);
+    if (rc == LLZ_OK) rc = rsm_put(&r->d_scr_bq, bq, sizeof(int) * (size_t)nt * 64);
     free(atab); free(dig); free(aoff); free(bq);
-    if (ok) {
-        r->screen_shift = shift;
-        r->screen_eps = eps;
-        r->screen_any_exact = any_exact;
+    r->screen_shift = shift; r->screen_eps = eps; r->screen_any_exact = any_exact;
+    return rc == LLZ_OK;
+}
+
+/* phase tile t = phases 16t .. 16t+15; its band starts at input offset c0 - (Q-1), c0 = floor(16 t M / L), and is walked 4
+ * samples per matrix-core step: lane (r = lane % 16, kq = lane / 16) of step s holds the tap of phase f = 16t + r that
+ * multiplies the band's sample 4s + kq, i.e. g_f[c_f - c0 + (Q-1) - (4s + kq)], gain folded in */
+static int rsm_put_band(rsm_t *r)
+{
+    const int L = r->L, M = r->M, Q = r->Q, steps = llzs_resample_mfma_f32_table_steps(L, M, Q), nt = (L + 15) / 16;
+    float *band = (float *)calloc((size_t)nt * steps * 64, sizeof(float));
+    int *c0 = (int *)malloc(sizeof(int) * (size_t)nt);
+    int rc = band && c0 ? LLZ_OK : LLZ_ERR_NOMEM;
+    for (int t = 0; rc == LLZ_OK && t < nt; t++) {
+        c0[t] = (int)(((long)16 * t * M) / L);
+        for (int s = 0; s < steps; s++)
+            for (int lane = 0; lane < 64; lane++) {
+                const int f = 16 * t + (lane & 15), u = 4 * s + (lane >> 4);
+                if (f >= L) continue;
+                const int k = (int)(((long)f * M) / L) - c0[t] + (Q - 1) - u;
+                if (k >= 0 && k < Q)
+                    band[((size_t)t * steps + s) * 64 + lane] = (float)r->taps.mat[(size_t)f * Q + k] * (float)r->gain;
+            }
     }
-    return ok;
+    if (rc == LLZ_OK) rc = rsm_put(&r->d_band, band, sizeof(float) * (size_t)nt * steps * 64);
+    if (rc == LLZ_OK) rc = rsm_put(&r->d_band_c0, c0, sizeof(int) * (size_t)nt);
+    free(band); free(c0);
+    return rc;
+}
+
+/* the taps as floats (TAB_M32), or as the phase taps of the L = 1 decimator (TAB_PHASE): gp[m][j] = g[0][j*M + m], rows
+ * zero padded to tp */
+static int rsm_put_f32(rsm_t *r, int phase)
+{
+    const size_t count = phase ? (size_t)r->M * r->tp : (size_t)r->L * r->Q;
+    float *h = (float *)calloc(count, sizeof(float));
+    if (!h) return LLZ_ERR_NOMEM;
+    for (int k = 0; k < r->L * r->Q; k++) h[phase ? (size_t)(k % r->M) * r->tp + k / r->M : (size_t)k] = (float)r->taps.mat[k];
+    const int rc = rsm_put(phase ? &r->d_phase : &r->d_m32, h, sizeof(float) * count);
+    free(h);
+    return rc;
+}
+
+/* the table at the top of Part 2, the screen's verdict aside (rsm_upload_matrix applies it) */
+static int rsm_choose(rsm_t *r)
+{
+    const int L = r->L, M = r->M, Q = r->Q, screen = llzs_tune(LLZS_TUNE_RS_I16_PATH) != 1;
+    rsm_path p, fb = RSM_NONE;
+    if (r->fmt == LLZ_PCM_F32) {
+        if (L == 1 && llzs_fir_mfma_f32_fits(Q, M) && llzs_tune(LLZS_TUNE_RS_DEC_VALU) != 1) p = RSM_FIR_MFMA_F32;
+        else if (L == 1 && llzs_resample_dec_f32_fits(M, r->tp)) p = RSM_DEC_F32;
+        else if (llzs_resample_mfma_f32_fits(L, M, Q) && llzs_tune(LLZS_TUNE_RS_GENERIC) < 1) p = RSM_MFMA_F32, fb = RSM_F32;
+        else p = RSM_F32;
+    } else if (r->fmt == LLZ_PCM_I16) {
+        if (screen && L == 1 && llzs_fir_mfma_i16x_fits(Q, M)) p = RSM_FIR_MFMA_I16X, fb = RSM_I16;
+        else if (screen && L >= 2 && llzs_resample_i16x_fits(L, M, Q)) p = RSM_I16X, fb = RSM_I16;
+        else p = RSM_I16;
+    } else {
+        /* the bit-exact screened kernel is the faster one (BASELINE config 5: 23 against 31 ms); the float32-sum kernel, within
+         * the format's 1 LSB, takes what the screen declines, so it must fit */
+        if (!llzs_fir_mfma_i16_fits(Q, M)) {
+            llzs_set_error("llz_resample_mc_init: %d taps at 1:%d do not fit the matrix-core kernel", Q, M);
+            return LLZ_ERR_RANGE;
+        }
+        if (screen && llzs_fir_mfma_i16x_fits(Q, M)) p = RSM_FIR_MFMA_I16X, fb = RSM_FIR_MFMA_I16;
+        else p = RSM_FIR_MFMA_I16;
+    }
+    r->primary = p; r->fallback = fb;
+    return LLZ_OK;
 }
 
 static int rsm_upload_matrix(rsm_t *r)
 {
-    const size_t count = (size_t)r->L * r->Q;
-    if (r->fmt == LLZ_PCM_I16) {
-        const int rc = llzs_h2d_table(r->d_mat, r->taps.mat, sizeof(double) * count);
-        const int want = rc == LLZ_OK && llzs_tune(LLZS_TUNE_RS_I16_PATH) != 1;
-        r->use_screen = want && r->L == 1 && rsm_build_screen(r);
-        r->use_screen_lm = want && r->L >= 2 && rsm_build_screen_lm(r);
-        return rc;
+    int rc = rsm_choose(r);
+    const int need = RSM_TABLES[r->primary] | RSM_TABLES[r->fallback];
+    if (rc == LLZ_OK && (need & TAB_M32)) rc = rsm_put_f32(r, 0);
+    if (rc == LLZ_OK && (need & TAB_M64)) rc = rsm_put(&r->d_m64, r->taps.mat, sizeof(double) * (size_t)r->L * r->Q);
+    if (rc == LLZ_OK && (need & TAB_BAND)) rc = rsm_put_band(r);
+    if (rc == LLZ_OK && (need & TAB_PHASE)) rc = rsm_put_f32(r, 1);
+    if (rc == LLZ_OK && (need & TAB_SCREEN) && !(r->L == 1 ? rsm_put_screen(r) : rsm_put_screen_lm(r))) {
+        r->primary = r->fallback;               /* the screen declines these taps */
+        r->fallback = RSM_NONE;
     }
-    float *m32 = (float *)malloc(sizeof(float) * count);
-    if (!m32) return LLZ_ERR_NOMEM;
-    for (size_t i = 0; i < count; i++) m32[i] = (float)r->taps.mat[i];
-    int rc = llzs_h2d_table(r->d_mat, m32, sizeof(float) * count);
-    /* LLZ_PCM_I16_FAST promises the reference's result within 1 LSB.  The bit-exact screened kernel is the faster of the two since
-     * round 3 (BASELINE config 5: 23 ms against 31 ms for the float32-sum kernel): a FAST handle takes it whenever the screen
-     * accepts the taps, and keeps the float32-sum kernel for the rest (gains above ~64, frames shorter than a tile). */
-    r->use_screen = 0;
-    if (rc == LLZ_OK && r->fmt == LLZ_PCM_I16_FAST && r->L == 1 && llzs_tune(LLZS_TUNE_RS_I16_PATH) != 1) {
-        if (!r->d_gd) r->d_gd = (double *)llzs_malloc(sizeof(double) * count);
-        r->use_screen = r->d_gd && llzs_h2d_table(r->d_gd, r->taps.mat, sizeof(double) * count) == LLZ_OK && rsm_build_screen(r);
-    }
-    if (rc == LLZ_OK && r->fmt == LLZ_PCM_F32 && llzs_resample_mfma_f32_fits(r->L, r->M, r->Q) &&
-        llzs_tune(LLZS_TUNE_RS_GENERIC) < 1) {
-        /* phase tile t = phases 16t .. 16t+15; its band starts at input offset c0 - (Q-1), c0 = floor(16 t M / L), and is
-         * walked 4 samples per matrix-core step: lane (r = lane % 16, kq = lane / 16) of step s holds the tap of phase
-         * f = 16t + r that multiplies the band's sample 4s + kq, i.e. g_f[c_f - c0 + (Q-1) - (4s + kq)] */
-        const int steps = llzs_resample_mfma_f32_table_steps(r->L, r->M, r->Q), nt = (r->L + 15) / 16;
-        float *band = (float *)calloc((size_t)nt * steps * 64, sizeof(float));
-        int *c0 = (int *)malloc(sizeof(int) * (size_t)nt);
-        if (!band || !c0) { free(band); free(c0); free(m32); return LLZ_ERR_NOMEM; }
-        for (int t = 0; t < nt; t++) {
-            c0[t] = (int)(((long)16 * t * r->M) / r->L);
-            for (int s = 0; s < steps; s++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int f = 16 * t + (lane & 15), u = 4 * s + (lane >> 4);
-                    if (f >= r->L) continue;
-                    const int k = (int)(((long)f * r->M) / r->L) - c0[t] + (r->Q - 1) - u;
-                    if (k >= 0 && k < r->Q)
-                        band[((size_t)t * steps + s) * 64 + lane] = (float)(m32[(size_t)f * r->Q + k] * (float)r->gain);
-                }
-        }
-        if (!r->d_band) r->d_band = (float *)llzs_malloc(sizeof(float) * (size_t)nt * steps * 64);
-        if (!r->d_band_c0) r->d_band_c0 = (int *)llzs_malloc(sizeof(int) * (size_t)nt);
-        rc = (r->d_band && r->d_band_c0) ? LLZ_OK : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_h2d_table(r->d_band, band, sizeof(float) * (size_t)nt * steps * 64);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(r->d_band_c0, c0, sizeof(int) * (size_t)nt);
-        free(band); free(c0);
-    }
-    if (rc == LLZ_OK && r->L == 1) {
-        r->use_mfma = llzs_fir_mfma_f32_fits(r->Q, r->M) && llzs_tune(LLZS_TUNE_RS_DEC_VALU) != 1;
-        /* phase taps for the decimator fast path: gp[m][j] = g[0][j*M + m], rows zero padded to tp */
-        const int per_phase = (r->Q + r->M - 1) / r->M;
-        r->tp = (per_phase + 15) & ~15;
-        if (llzs_resample_dec_f32_fits(r->M, r->tp)) {
-            float *gp = (float *)calloc((size_t)r->M * r->tp, sizeof(float));
-            if (!gp) { free(m32); return LLZ_ERR_NOMEM; }
-            for (int k = 0; k < r->Q; k++) gp[(size_t)(k % r->M) * r->tp + k / r->M] = m32[k];
-            if (!r->d_phase) r->d_phase = (float *)llzs_malloc(sizeof(float) * (size_t)r->M * r->tp);
-            rc = r->d_phase ? llzs_h2d_table(r->d_phase, gp, sizeof(float) * (size_t)r->M * r->tp) : LLZ_ERR_NOMEM;
-            free(gp);
-        }
-    }
-    free(m32);
     return rc;
 }
 
@@ -569,16 +577,12 @@ unsigned long llz_resample_mc_init(int channels, int L, int M, double gain, win_
     int rc = tapmat_build(&r->taps, L, M, fc, L, win_type);
     if (rc == LLZ_OK) {
         r->Q = r->taps.cols;
+        r->tp = ((r->Q + M - 1) / M + 15) & ~15;
         const size_t hist_bytes = rsm_sample_bytes(r) * (size_t)channels * (size_t)(r->Q > 1 ? r->Q - 1 : 1);
-        r->d_mat = llzs_malloc((r->fmt == LLZ_PCM_I16 ? sizeof(double) : sizeof(float)) * (size_t)L * r->Q);
         r->d_hist[0] = llzs_malloc(hist_bytes);
         r->d_hist[1] = llzs_malloc(hist_bytes);
-        if (!r->d_mat || !r->d_hist[0] || !r->d_hist[1]) rc = LLZ_ERR_NOMEM;
+        if (!r->d_hist[0] || !r->d_hist[1]) rc = LLZ_ERR_NOMEM;
         if (rc == LLZ_OK) rc = rsm_upload_matrix(r);
-        if (rc == LLZ_OK && r->fmt == LLZ_PCM_I16_FAST && !llzs_fir_mfma_i16_fits(r->Q, r->M)) {
-            llzs_set_error("llz_resample_mc_init: %d taps at 1:%d do not fit the matrix-core kernel", r->Q, r->M);
-            rc = LLZ_ERR_RANGE;
-        }
         if (rc == LLZ_OK) rc = llzs_memset(r->d_hist[0], 0, hist_bytes, NULL);
         if (rc == LLZ_OK) rc = llzs_memset(r->d_hist[1], 0, hist_bytes, NULL);
         if (rc == LLZ_OK) rc = llzs_sync(NULL);
@@ -652,19 +656,34 @@ int llz_resample_mc_set_matrix(unsigned long handle, const double *src, int coun
     return rc;
 }
 
-static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_in, void *out);
-
-long llz_resample_mc(unsigned long handle, const void *in, long n_in, void *out)
+/* one call of one path, with the handle's tables */
+static int rsm_run(const rsm_t *r, rsm_path p, const void *in, void *out, const void *hist, long n_in, long n_out)
 {
-    if (!LLZ_HANDLE_OK(handle, rsm_t, LLZ_TAG_RSM) || !in || !out) {
-        llzs_set_error("llz_resample_mc: bad handle or NULL buffer");
-        return LLZ_ERR_ARG;
+    const int C = r->channels, L = r->L, M = r->M, Q = r->Q;
+    switch (p) {
+    case RSM_FIR_MFMA_F32:
+        return llzs_fir_mfma_f32(in, out, hist, r->d_m32, C, n_in, n_out, n_in, n_out, Q, M, (float)r->gain, r->stream);
+    case RSM_DEC_F32:
+        return llzs_resample_dec_f32(in, out, hist, r->d_phase, C, n_in, n_out, n_in, n_out, M, Q, r->tp, (float)r->gain,
+                                     r->stream);
+    case RSM_MFMA_F32:
+        return llzs_resample_mfma_f32(in, out, hist, r->d_band, r->d_band_c0, C, n_in, n_out, n_in, n_out, L, M, Q, r->stream);
+    case RSM_F32:
+        return llzs_resample_f32(in, out, hist, r->d_m32, C, n_in, n_out, n_in, n_out, L, M, Q, (float)r->gain, r->out_count,
+                                 r->in_count, r->stream);
+    case RSM_FIR_MFMA_I16X:
+        return llzs_fir_mfma_i16x(in, out, hist, r->d_digits, r->d_m64, C, n_in, n_out, n_in, n_out, Q, M, r->screen_shift,
+                                  r->screen_bias, r->gain, r->screen_eps, r->stream);
+    case RSM_I16X:
+        return llzs_resample_i16x(in, out, hist, r->d_scr_atab, r->d_scr_aoff, r->d_scr_bq, r->d_m64, C, n_in, n_out, n_in,
+                                  n_out, L, M, Q, r->screen_shift, r->gain, r->screen_eps, r->screen_any_exact, r->stream);
+    case RSM_I16:
+        return llzs_resample_i16(in, out, hist, r->d_m64, C, n_in, n_out, n_in, n_out, L, M, Q, r->gain, r->out_count,
+                                 r->in_count, r->stream);
+    case RSM_FIR_MFMA_I16:
+        return llzs_fir_mfma_i16(in, out, hist, r->d_m32, C, n_in, n_out, n_in, n_out, Q, M, (float)r->gain, r->stream);
+    default: return LLZ_ERR_ARG;
     }
-    rsm_t *r = (rsm_t *)handle;
-    const int prev = llzs_device_enter(r->device);
-    const long rc = rsm_process(r, handle, in, n_in, out);
-    llzs_device_leave(prev);
-    return rc;
 }
 
 static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_in, void *out)
@@ -695,45 +714,8 @@ static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_i
     }
     const void *hist = r->Q > 1 ? r->d_hist[r->cur] : NULL;
     if (rc == LLZ_OK) {
-        if (r->fmt == LLZ_PCM_I16_FAST && r->use_screen &&
-            (rc = llzs_fir_mfma_i16x((const short *)d_in, (short *)d_out, (const short *)hist, r->d_digits, r->d_gd, r->channels,
-                                     n_in, n_out, n_in, n_out, r->Q, r->M, r->screen_shift, r->screen_bias, r->gain,
-                                     r->screen_eps, r->stream)) != LLZ_ERR_RANGE)
-            ;                                   /* (the exact result is within the format's 1 LSB) */
-        else if (r->fmt == LLZ_PCM_I16_FAST)
-            rc = llzs_fir_mfma_i16((const short *)d_in, (short *)d_out, (const short *)hist, (const float *)r->d_mat,
-                                   r->channels, n_in, n_out, n_in, n_out, r->Q, r->M, (float)r->gain, r->stream);
-        else if (r->fmt == LLZ_PCM_I16 && r->use_screen &&
-                 (rc = llzs_fir_mfma_i16x((const short *)d_in, (short *)d_out, (const short *)hist, r->d_digits,
-                                          (const double *)r->d_mat, r->channels, n_in, n_out, n_in, n_out, r->Q, r->M,
-                                          r->screen_shift, r->screen_bias, r->gain, r->screen_eps, r->stream)) !=
-                     LLZ_ERR_RANGE)
-            ;                                   /* (LLZ_ERR_RANGE: a frame too short or misaligned for the screened kernel) */
-        else if (r->fmt == LLZ_PCM_I16 && r->use_screen_lm && r->in_count % r->M == 0 && r->out_count % r->L == 0 &&
-                 r->channels <= 65535 &&
-                 (rc = llzs_resample_i16x((const short *)d_in, (short *)d_out, (const short *)hist, r->d_scr_atab, r->d_scr_aoff,
-                                          r->d_scr_bq, (const double *)r->d_mat, r->channels, n_in, n_out, n_in, n_out, r->L,
-                                          r->M, r->Q, r->screen_shift, r->gain, r->screen_eps, r->screen_any_exact,
-                                          r->stream)) != LLZ_ERR_RANGE)
-            ;                                   /* (LLZ_ERR_RANGE: a frame shorter than one span's image) */
-        else if (r->fmt == LLZ_PCM_I16)
-            rc = llzs_resample_i16((const short *)d_in, (short *)d_out, (const short *)hist,
-                                   (const double *)r->d_mat, r->channels, n_in, n_out, n_in, n_out, r->L, r->M,
-                                   r->Q, r->gain, r->out_count, r->in_count, r->stream);
-        else if (r->use_mfma)
-            rc = llzs_fir_mfma_f32((const float *)d_in, (float *)d_out, (const float *)hist, (const float *)r->d_mat,
-                                   r->channels, n_in, n_out, n_in, n_out, r->Q, r->M, (float)r->gain, r->stream);
-        else if (r->d_phase)
-            rc = llzs_resample_dec_f32((const float *)d_in, (float *)d_out, (const float *)hist, r->d_phase,
-                                       r->channels, n_in, n_out, n_in, n_out, r->M, r->Q, r->tp, (float)r->gain,
-                                       r->stream);
-        else if (r->d_band && r->in_count % r->M == 0 && r->out_count % r->L == 0 && r->channels <= 65535)
-            rc = llzs_resample_mfma_f32((const float *)d_in, (float *)d_out, (const float *)hist, r->d_band, r->d_band_c0,
-                                        r->channels, n_in, n_out, n_in, n_out, r->L, r->M, r->Q, r->stream);
-        else
-            rc = llzs_resample_f32((const float *)d_in, (float *)d_out, (const float *)hist,
-                                   (const float *)r->d_mat, r->channels, n_in, n_out, n_in, n_out, r->L, r->M,
-                                   r->Q, (float)r->gain, r->out_count, r->in_count, r->stream);
+        rc = rsm_path_ok(r, r->primary) ? rsm_run(r, r->primary, d_in, d_out, hist, n_in, n_out) : LLZ_ERR_RANGE;
+        if (rc == LLZ_ERR_RANGE && r->fallback != RSM_NONE) rc = rsm_run(r, r->fallback, d_in, d_out, hist, n_in, n_out);
     }
     if (rc == LLZ_OK && r->Q > 1) {
         if (r->fmt != LLZ_PCM_F32)
@@ -749,4 +731,17 @@ static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_i
     r->in_count += n_in;
     r->out_count += n_out;
     return n_out;
+}
+
+long llz_resample_mc(unsigned long handle, const void *in, long n_in, void *out)
+{
+    if (!LLZ_HANDLE_OK(handle, rsm_t, LLZ_TAG_RSM) || !in || !out) {
+        llzs_set_error("llz_resample_mc: bad handle or NULL buffer");
+        return LLZ_ERR_ARG;
+    }
+    rsm_t *r = (rsm_t *)handle;
+    const int prev = llzs_device_enter(r->device);
+    const long rc = rsm_process(r, handle, in, n_in, out);
+    llzs_device_leave(prev);
+    return rc;
 }
