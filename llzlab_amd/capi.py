@@ -194,6 +194,13 @@ def lib():
     sig("llz_autocorr_fast_mc_uninit", None, ul)
     sig("llz_autocorr_fast_mc", i, ul, vp, vp, i)
     sig("llz_autocorr_fast_mc_set_stream", i, ul, vp)
+    sig("llz_levinson", None, dp, i, dp, dp, dp)
+    sig("llz_levinson1", None, dp, i, dp, dp, dp)
+    sig("llz_atlvs", i, dp, i, dp, dp, dp, dp)
+    sig("llz_lpc_init", ul, i)
+    sig("llz_lpc_uninit", None, ul)
+    sig("llz_lpc", d, ul, dp, i, dp, dp, dp)
+    sig("llz_lpc_mc", i, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp)
     # llz_asmodel.h
     for n in ("llz_analysis_fft_init", "llz_synthesis_fft_init"):
         sig(n, ul, i, i, i)

@@ -8,6 +8,7 @@
 //                      the pointwise steps of the FFT form around the batched float32 FFT of fft.hip:
 //                      zero-padded real -> complex, |X|^2 of the FIRST n bins (the reference's definition), 2*Re.
 #include "common.hpp"
+#include "acf_reg.hpp"
 
 namespace {
 
@@ -37,32 +38,6 @@ constexpr int AC_MAXLAG = 256;                // p <= 255
 constexpr int AC_LDS = (AC_CHUNK + AC_MAXLAG + 16) + ((AC_CHUNK + AC_MAXLAG + 16) >> 3) * 4;   // padded image
 
 __device__ __forceinline__ int ac_phys(int p) { return p + ((p >> 3) << 2); }
-
-// All K per-lane partial sums of a wave at once by recursive halving: in the step with distance d a lane keeps one accumulator of a
-// pair and hands the other to lane ^ d, which keeps that one -- the number of live sums halves with every step (17 -> 9 -> 5 -> 3
-// -> 2 -> 1 -> 1: 21 exchanges instead of 17 x 6).  Returns the total of sum number (six bits of the lane, reversed) -- for
-// K <= 64 every sum ends in exactly one lane; *which says which.
-template <int K>
-__device__ __forceinline__ float wave_sums(float (&acc)[K], int lane, int *which)
-{
-    static_assert(K <= 64, "one sum per lane at most");
-    int cnt = K;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const bool upper = (lane & d) != 0;
-        const int half = (cnt + 1) / 2;
-#pragma unroll
-        for (int i = 0; i < (K + 1) / 2; i++) {
-            if (i < half) {
-                const float a = acc[2 * i], b = 2 * i + 1 < cnt ? acc[2 * i + 1] : 0.f;
-                acc[i] = (upper ? b : a) + __shfl_xor(upper ? a : b, d, 64);
-            }
-        }
-        cnt = half;
-    }
-    *which = (int)(__brev((unsigned)lane) >> 26);
-    return acc[0];
-}
 
 template <int NG>                               // lag groups of 8 kept in registers: lags 0 .. 8*NG-1
 __global__ void __launch_bounds__(64 * AC_WAVES)
@@ -118,62 +93,20 @@ k_autocorr_mc_f32(const float *__restrict__ x, float *__restrict__ r, int frames
     }
 }
 
-// Direct autocorrelation for SHORT lag ranges (p <= 8 NL <= 32: the LPC orders) without LDS: lane l keeps x[8 l .. 8 l + 7] of a
-// chunk in registers and gets the samples it slides over from lanes l + 1 .. l + NL through the wave shuffle, so a chunk is
-// 8 (64 - NL) samples (the last NL lanes only look ahead: their own products are formed by the next chunk, where they are the
-// first lanes); the next chunk's samples are requested before the current one is worked on.  One 16-byte-pair load and
-// 8 (p + 1) FMAs per lane and chunk; the per-lane partial sums are reduced across the wave once per frame.  (The LDS form
+// Direct autocorrelation for SHORT lag ranges (p <= 8 NL <= 32: the LPC orders) without LDS: the register form of one frame
+// (acf_reg_frame in acf_reg.hpp: 8 samples per lane, the look-ahead through the wave shuffle, 8 (p + 1) FMAs per lane and
+// chunk); the per-lane partial sums are reduced across the wave once per frame.  (The LDS form
 // above -- staging, two waits and the window reads per 512 samples, nothing in flight meanwhile -- measured 0.93 ms for 2^18
 // frames of 1024 at p = 16; this one is bound by the reduction and the FMAs.)
-typedef float ac_f32x4 __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(4))) ac_x4 { ac_f32x4 v; };     // a 16-byte load at any 4-byte address
-
 template <int NL>
 __global__ void __launch_bounds__(64 * AC_WAVES)
 k_autocorr_reg_f32(const float *__restrict__ x, float *__restrict__ r, int frames, int n, int p)
 {
-    constexpr int NLAG = 8 * NL + 1, STEP = 8 * (64 - NL);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long waves_total = (long)gridDim.x * AC_WAVES;
-    const bool active = lane < 64 - NL;
     for (long f = (long)blockIdx.x * AC_WAVES + wave; f < frames; f += waves_total) {
-        const float *row = x + (size_t)f * n;
-        auto fetch = [&](int c0, float (&v)[8]) {
-            const int i0 = c0 + 8 * lane;
-            if (i0 + 8 <= n) {
-                const ac_f32x4 a = reinterpret_cast<const ac_x4 *>(row + i0)->v, b = reinterpret_cast<const ac_x4 *>(row + i0 + 4)->v;
-                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-                v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; j++) v[j] = i0 + j < n ? row[i0 + j] : 0.f;   // zeros behind the frame: those products vanish
-            }
-        };
-        float acc[NLAG];
-#pragma unroll
-        for (int k = 0; k < NLAG; k++) acc[k] = 0.f;
-        float cur[8], nxt[8];
-        fetch(0, cur);
-        for (int c0 = 0; c0 < n; c0 += STEP) {
-            if (c0 + STEP < n) fetch(c0 + STEP, nxt);
-            // s = the lane's own samples followed by those of lanes l + 1 .. l + NL
-            float s[8 * (NL + 1)];
-#pragma unroll
-            for (int j = 0; j < 8; j++) s[j] = cur[j];
-#pragma unroll
-            for (int h = 1; h <= NL; h++)
-#pragma unroll
-                for (int j = 0; j < 8; j++) s[8 * h + j] = __shfl_down(s[8 * (h - 1) + j], 1, 64);
-            float xa[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) xa[j] = active ? cur[j] : 0.f;
-#pragma unroll
-            for (int k = 0; k < NLAG; k++)
-#pragma unroll
-                for (int j = 0; j < 8; j++) acc[k] = __builtin_fmaf(xa[j], s[j + k], acc[k]);
-#pragma unroll
-            for (int j = 0; j < 8; j++) cur[j] = nxt[j];
-        }
+        float acc[8 * NL + 1];
+        acf_reg_frame<NL, false>(x + (size_t)f * n, nullptr, n, lane, acc);
         int k;
         const float v = wave_sums(acc, lane, &k);
         if (k <= p) r[(size_t)f * (p + 1) + k] = v;

@@ -55,6 +55,7 @@ enum {
     LLZS_TUNE_RS_I16_WALK,          /* ... consecutive spans per workgroup */
     LLZS_TUNE_ACF_LDS,              /* 1: direct autocorrelation always on the LDS-window kernel (no register form for p <= 32) */
     LLZS_TUNE_STFT_FULL,            /* 1: STFT synthesis frames of 512 / 2048 points on the full-size complex inverse transform */
+    LLZS_TUNE_LPC_SPLIT,            /* 1: batch LPC with p <= 32 as two launches (correlation, then recursion) like p > 32 */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -246,6 +247,18 @@ int llzs_acf_power(float *z, int frames, int n, int F, void *stream);
 int llzs_acf_extract(const float *z, float *r, int frames, int p, int F, void *stream);
 /* the same five steps fused in LDS (fft.hip): one read of the frames, p+1 floats written per frame */
 int llzs_acf_fused_f32(const float *x, float *r, int frames, int n, int p, int size, const float *cs, void *stream);
+
+/* ---- linear prediction (lpc.hip) ---- */
+/* LPC of frames x n float32 (0 <= p <= 32): the correlation of llzs_autocorr_mc_f32 (the same bits; on x*win when win is not
+ * NULL) and the Levinson-Durbin recursion in double in one launch.  acof [frames][p+1]; kcof [frames][p], err, gain
+ * [frames] and r [frames][p+1] may be NULL */
+int llzs_lpc_fused_f32(const float *x, const float *win, float *acof, float *kcof, float *err, float *gain, float *r,
+                       int frames, int n, int p, void *stream);
+/* the recursion alone from r [frames][p+1] (0 <= p <= 64), outputs as above; n divides the error */
+int llzs_levinson_f32(const float *r, float *acof, float *kcof, float *err, float *gain, int frames, int n, int p,
+                      void *stream);
+/* y[f][i] = x[f][i] * win[i] (float32, one rounding) */
+int llzs_window_f32(const float *x, const float *win, float *y, int frames, int n, void *stream);
 
 /* windowed-FFT frames (llz_asmodel.c:180-310), float32 batch: x planar [C][frames*F] (row pitch x_pitch), spectra
  * [C][frames][size/2+1]; hist / ola: [C][size-F] state carried between calls (ola_old != ola_new); w: size floats;

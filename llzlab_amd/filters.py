@@ -498,6 +498,88 @@ class AutocorrFastMC:
     __del__ = close
 
 
+# ------------------------------------------------------------------------------------------ linear prediction
+LEVINSON_ORDER_MAX = 64
+
+
+def _order_ok(p, what, lo=0):
+    if not lo <= p <= LEVINSON_ORDER_MAX:
+        raise LlzError(f"{what}: order {p} outside {lo}..{LEVINSON_ORDER_MAX}")
+
+
+def _levinson(fn, r, p):
+    _order_ok(p, fn)
+    r = _f64(r)
+    if len(r) < p + 1:
+        raise LlzError(f"{fn}: r needs p + 1 = {p + 1} entries")
+    acof, kcof, err = np.zeros(p + 1), np.zeros(p + 1), np.zeros(1)
+    getattr(capi.lib(), fn)(r.ctypes.data_as(_dp), p, acof.ctypes.data_as(_dp), kcof.ctypes.data_as(_dp),
+                            err.ctypes.data_as(_dp))
+    return acof, kcof, float(err[0])
+
+
+def levinson(r, p):
+    """llz_levinson: host float64, exact -> (acof[p+1], kcof[p+1] (kcof[0..p-1] used), err)."""
+    return _levinson("llz_levinson", r, p)
+
+
+def levinson1(r, p):
+    """llz_levinson1 (negated coefficients): host float64, exact -> (acof[p+1], kcof[p+1], err)."""
+    return _levinson("llz_levinson1", r, p)
+
+
+def atlvs(r, b):
+    """llz_atlvs: solves the Toeplitz system T(r[0..n-1]) x = b -> (x[n], kcof[n], err, rc); rc -1 = singular."""
+    r, b = _f64(r), _f64(b)
+    n = len(b)
+    _order_ok(n, "llz_atlvs", 1)
+    if len(r) < n:
+        raise LlzError("llz_atlvs: r needs len(b) entries")
+    x, kcof, err = np.zeros(n), np.zeros(n), np.zeros(1)
+    rc = capi.lib().llz_atlvs(r.ctypes.data_as(_dp), n, b.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                              kcof.ctypes.data_as(_dp), err.ctypes.data_as(_dp))
+    return x, kcof, float(err[0]), rc
+
+
+class Lpc:
+    """llz_lpc_{init,uninit} handle: run(x) -> (acof[p+1], kcof[p+1], err, gain), state kept between calls as in the
+    reference."""
+
+    def __init__(self, p):
+        self._L = capi.lib()
+        self.p = p
+        self.handle = check_handle(self._L.llz_lpc_init(p), "llz_lpc_init")
+
+    def run(self, x):
+        x = _f64(x)
+        if len(x) < 1:
+            raise LlzError("llz_lpc: empty frame")
+        acof, kcof, err = np.zeros(self.p + 1), np.zeros(self.p + 1), np.zeros(1)
+        gain = self._L.llz_lpc(self.handle, x.ctypes.data_as(_dp), len(x), acof.ctypes.data_as(_dp),
+                               kcof.ctypes.data_as(_dp), err.ctypes.data_as(_dp))
+        return acof, kcof, float(err[0]), gain
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_lpc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
+def lpc_mc(x, acof, kcof=None, err=None, gain=None, r=None, win=None, p=None, stream=None):
+    """llz_lpc_mc: x [frames, n] float32 -> acof [frames, p+1] (kcof [frames, p], err / gain [frames], r [frames, p+1]
+    when given); win None or [n].  p defaults to acof's width - 1.  Device tensors or numpy arrays."""
+    frames, n = x.shape
+    if p is None:
+        p = acof.shape[1] - 1
+    ptr = lambda b, numel, what: None if b is None else _typed(b, "float32", numel, what)  # noqa: E731
+    check(capi.lib().llz_lpc_mc(ptr(x, frames * n, "x"), ptr(win, n, "win"), ptr(acof, frames * (p + 1), "acof"),
+                                ptr(kcof, frames * p, "kcof"), ptr(err, frames, "err"), ptr(gain, frames, "gain"),
+                                ptr(r, frames * (p + 1), "r"), frames, n, p, _stream_ptr(stream)), "llz_lpc_mc")
+    return acof
+
+
 # ------------------------------------------------------------------------------------------ windowed-FFT frames
 class _FftFrames:
     """llz_analysis_fft_* / llz_synthesis_fft_* (llz_asmodel.h:36-42): one frame per call, host float64, exact."""
