@@ -44,8 +44,8 @@ double *llz_host_fft_table_f64(int size)
 
 unsigned long llz_fft_init(int size)
 {
-    if (!is_pow2_in_range(size, 2, 4096)) {
-        llzs_set_error("llz_fft_init: size %d must be a power of two in 2..4096", size);
+    if (!is_pow2_in_range(size, 2, LLZS_FFT_MAX)) {
+        llzs_set_error("llz_fft_init: size %d must be a power of two in 2..%d", size, LLZS_FFT_MAX);
         return LLZ_BAD_HANDLE;
     }
     fft1_t *f = (fft1_t *)calloc(1, sizeof(*f));
@@ -82,7 +82,9 @@ static void fft1_run(unsigned long handle, double *data, int inverse)
     const size_t bytes = sizeof(double) * 2 * (size_t)f->size;
     const int prev = llzs_device_enter(f->device);
     int rc = llzs_h2d(f->d_data, data, bytes, NULL);
-    if (rc == LLZ_OK) rc = llzs_fft_f64(f->d_data, f->size, f->d_cs, inverse, NULL);
+    if (rc == LLZ_OK)   /* above 4096 points: outer passes over device memory around 4096-point blocks (fft_large.hip) */
+        rc = f->size <= 4096 ? llzs_fft_f64(f->d_data, f->size, f->d_cs, inverse, NULL)
+                             : llzs_fft_large_f64(f->d_data, f->size, f->d_cs, inverse, NULL);
     if (rc == LLZ_OK) (void)llzs_d2h(data, f->d_data, bytes, NULL);
     llzs_device_leave(prev);
 }
@@ -95,14 +97,22 @@ void llz_ifft(unsigned long handle, double *data) { fft1_run(handle, data, 1); }
 typedef struct {
     int tag, size, device;
     float *d_cs;
+    float *d_twb;       /* above 4096 points: the large path's LDS-block table in memory */
     void *stream;
     llz_stage_t st;
 } fftb_t;
 
+/* the float32 batch on device memory: the register / LDS kernels of fft.hip up to 4096 points, fft_large.hip above */
+static int fftb_launch(const fftb_t *f, float *d, int count, int inverse)
+{
+    return f->size <= 4096 ? llzs_fft_f32(d, count, f->size, f->d_cs, inverse, f->stream)
+                           : llzs_fft_large_f32(d, count, f->size, f->d_cs, f->d_twb, inverse, f->stream);
+}
+
 unsigned long llz_fft_batch_init(int size)
 {
-    if (!is_pow2_in_range(size, 8, 4096)) {
-        llzs_set_error("llz_fft_batch_init: size %d must be a power of two in 8..4096", size);
+    if (!is_pow2_in_range(size, 8, LLZS_FFT_MAX)) {
+        llzs_set_error("llz_fft_batch_init: size %d must be a power of two in 8..%d", size, LLZS_FFT_MAX);
         return LLZ_BAD_HANDLE;
     }
     fftb_t *f = (fftb_t *)calloc(1, sizeof(*f));
@@ -115,9 +125,14 @@ unsigned long llz_fft_batch_init(int size)
         cs[size + i] = (float)sin(ang);
     }
     f->d_cs = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)size);
-    const int ok = f->d_cs && llzs_h2d(f->d_cs, cs, sizeof(float) * 2 * (size_t)size, NULL) == LLZ_OK;
+    int ok = f->d_cs && llzs_h2d(f->d_cs, cs, sizeof(float) * 2 * (size_t)size, NULL) == LLZ_OK;
     free(cs);
-    if (!ok) { llzs_free(f->d_cs); free(f); return LLZ_BAD_HANDLE; }
+    const size_t twb = size > 4096 ? (size_t)llzs_fft_large_twb_bytes(size) : 0;
+    if (ok && twb) {
+        f->d_twb = (float *)llzs_malloc(twb);
+        ok = f->d_twb && llzs_fft_large_twb(f->d_twb, size, f->d_cs, NULL) == LLZ_OK && llzs_sync(NULL) == LLZ_OK;
+    }
+    if (!ok) { llzs_free(f->d_cs); llzs_free(f->d_twb); free(f); return LLZ_BAD_HANDLE; }
     return (unsigned long)f;
 }
 
@@ -128,6 +143,7 @@ void llz_fft_batch_uninit(unsigned long handle)
     const int prev = llzs_device_enter(f->device);
     llzs_sync(f->stream);
     llzs_free(f->d_cs);
+    llzs_free(f->d_twb);
     llz_stage_release(&f->st);
     llzs_device_leave(prev);
     f->tag = 0;
@@ -153,11 +169,11 @@ static int fftb_run(unsigned long handle, float *data, int count, int inverse)
     const int on_dev = llzs_is_device_ptr(data);
     int rc = on_dev < 0 ? LLZ_ERR_ARG : LLZ_OK;
     if (rc == LLZ_OK && on_dev) {
-        rc = llzs_fft_f32(data, count, f->size, f->d_cs, inverse, f->stream);
+        rc = fftb_launch(f, data, count, inverse);
     } else if (rc == LLZ_OK) {
         float *d = (float *)llz_stage_reserve(&f->st, bytes);
         rc = d ? llzs_h2d(d, data, bytes, f->stream) : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_fft_f32(d, count, f->size, f->d_cs, inverse, f->stream);
+        if (rc == LLZ_OK) rc = fftb_launch(f, d, count, inverse);
         if (rc == LLZ_OK) rc = llzs_d2h(data, d, bytes, f->stream);
     }
     llzs_device_leave(prev);

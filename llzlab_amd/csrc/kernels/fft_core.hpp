@@ -230,7 +230,7 @@ __device__ __forceinline__ void small_fft(cpx<float> (&v)[E], std::integer_seque
     (small_stage<E, Gs, INVERSE>(v, std::make_integer_sequence<int, E>{}), ...);
 }
 
-template <int G, bool INVERSE>
+template <int G, bool INVERSE, int NT = FFT_THREADS>         // NT: threads of the workgroup
 __device__ __forceinline__ void fft_pass_f32(cpx<float> *s, int tpw, int size, int log2n, int log2step, int tstride,
                                              const cpx<float> *tw, int tid)
 {
@@ -240,7 +240,7 @@ __device__ __forceinline__ void fft_pass_f32(cpx<float> *s, int tpw, int size, i
     const int items = tpw << log2items;
     const int tshift = log2n - G - log2step;               // W_(E*step)^m = W_size^(m << tshift)
     const int half = size >> 1;
-    for (int it = tid; it < items; it += FFT_THREADS) {
+    for (int it = tid; it < items; it += NT) {
         const int tr = it >> log2items, rem = it & ((1 << log2items) - 1);
         const int r = rem & (step - 1), blk = rem >> log2step;
         cpx<float> *base = s + tr * tstride;

@@ -235,6 +235,15 @@ int llzs_fft_f32(float *data, int count, int size, const float *cs, int inverse,
 int llzs_fft_f64(double *data, int size, const double *cs, int inverse, void *stream);
 /* int32 data, Q15 twiddles (size cos then size sin shorts), bit-exact */
 int llzs_fft_fixed(int *data, int count, int size, const short *cs, int inverse, void *stream);
+/* transforms of 8192 .. LLZS_FFT_MAX points (fft_large.hip), in place, same contract as the two above.  cs: the size-point
+ * table.  twb (float32): a device buffer of llzs_fft_large_twb_bytes(size) bytes, filled once by
+ * llzs_fft_large_twb.  llzs_fft_large_passes: passes over device memory of one transform. */
+#define LLZS_FFT_MAX (1 << 24)
+int llzs_fft_large_f32(float *data, int count, int size, const float *cs, const float *twb, int inverse, void *stream);
+int llzs_fft_large_f64(double *data, int size, const double *cs, int inverse, void *stream);
+int llzs_fft_large_twb_bytes(int size);
+int llzs_fft_large_twb(float *twb, int size, const float *cs, void *stream);
+int llzs_fft_large_passes(int size, int f32);
 
 /* ---- correlation ---- */
 /* r[k] = sum_i x[i]*y[i+k], k = 0..p, one channel, double, the reference's summation order (llz_corr.c:38-58) */
