@@ -24,8 +24,8 @@ enum {
 };
 
 /* ---- Part 1: reference-identical symbols (llz_asmodel.h:36-42) ---- */
-/* fft_len must be a power of two <= 4096 here (the reference's llz_fft assumes one without checking);
- * returns (unsigned long)-1 otherwise */
+/* fft_len must be a power of two in 2..2^24 here (the reference's llz_fft assumes one without checking; 2^24 is the
+ * bound of llz_fft); returns (unsigned long)-1 otherwise */
 unsigned long llz_analysis_fft_init(int overlap_hint, int frame_len, win_t win_type);
 void          llz_analysis_fft_uninit(unsigned long handle);
 /* slides frame_len new samples in, windows the last fft_len samples, transforms; re/im receive bins 0..fft_len/2 */
@@ -50,7 +50,9 @@ void          llz_synthesis_mdct(unsigned long handle, double *X, double *x);
 /* ---- Part 2: batch extension, float32 ---- */
 /* One handle serves both directions and keeps the streaming state of each per channel (analysis: the last
  * fft_len - frame_len input samples; synthesis: the overlap-add tail), so consecutive calls continue the streams.
- * fft_len a power of two in 8..2048.  Pointers may be device or host memory. */
+ * fft_len a power of two in 8..2^24 (the range of llz_fft_batch).  Pointers may be device or host memory.  Above
+ * fft_len 4096 a call also uses a device scratch buffer of at most 2^24 complex points (128 MiB) plus, in the synthesis,
+ * the overlap-add tails of the channels of one chunk; a handle keeps it until llz_stft_mc_uninit. */
 unsigned long llz_stft_mc_init(int channels, int overlap_hint, int frame_len, win_t win_type);
 void          llz_stft_mc_uninit(unsigned long handle);
 int           llz_stft_mc_bins(unsigned long handle);          /* fft_len/2 + 1 */

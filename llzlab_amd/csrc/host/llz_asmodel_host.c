@@ -15,6 +15,7 @@
 static int asm_shape(int overlap_hint, int frame_len, int *fft_len, double *magic)
 {
     /* llz_asmodel.c:114-123 */
+    if (frame_len > LLZS_FFT_MAX) return 0;                        /* (the shift below would overflow) */
     if (overlap_hint == LLZ_OVERLAP_HIGH) { *fft_len = frame_len << 2; *magic = 0.812; }
     else if (overlap_hint == LLZ_OVERLAP_LOW) { *fft_len = frame_len << 1; *magic = 1; }
     else return 0;
@@ -34,7 +35,8 @@ static int asm_window(double *w, int n, win_t win_type)
 /* ---- Part 1: the reference's symbols, one channel, one frame per call ----
  * A handle keeps its running frame buffer, the window and the scratch spectrum in DEVICE memory.  A call copies the new
  * samples (or the two spectrum planes) in, runs framing kernel -> exact-order transform -> framing kernel on the device
- * (kernels/frames_f64.hip, kernels/fft.hip), and copies the result out; nothing is computed on the host. */
+ * (kernels/frames_f64.hip; the transform of llz_fft: kernels/fft.hip up to 4096 points, kernels/fft_large.hip above, up
+ * to LLZS_FFT_MAX), and copies the result out; nothing is computed on the host. */
 
 typedef struct {
     int tag, device, hop, size, bins;       /* hop = frame_len, size = fft_len, bins = size/2 + 1 */
@@ -73,9 +75,9 @@ static unsigned long asm1_init(int overlap_hint, int frame_len, win_t win_type, 
 {
     int fft_len;
     double magic;
-    if (!asm_shape(overlap_hint, frame_len, &fft_len, &magic) || fft_len > 4096) {
-        llzs_set_error("%s: overlap_hint %d frame_len %d (fft_len must be a power of two <= 4096)", who, overlap_hint,
-                       frame_len);
+    if (!asm_shape(overlap_hint, frame_len, &fft_len, &magic) || fft_len > LLZS_FFT_MAX) {
+        llzs_set_error("%s: overlap_hint %d frame_len %d (fft_len must be a power of two in 2..%d)", who, overlap_hint,
+                       frame_len, LLZS_FFT_MAX);
         return LLZ_BAD_HANDLE;
     }
     asm1_t *f = (asm1_t *)calloc(1, sizeof(*f));
@@ -128,6 +130,13 @@ unsigned long llz_synthesis_fft_init(int overlap_hint, int frame_len, win_t win_
 void llz_analysis_fft_uninit(unsigned long handle) { asm1_uninit(handle); }
 void llz_synthesis_fft_uninit(unsigned long handle) { asm1_uninit(handle); }
 
+/* the exact-order transform of llz_fft / llz_ifft on the handle's spectrum, picked by size as fft1_run does */
+static int asm1_fft(asm1_t *f, int inverse)
+{
+    return f->size <= 4096 ? llzs_fft_f64(f->d_spectrum, f->size, f->d_fft_cs, inverse, NULL)
+                           : llzs_fft_large_f64(f->d_spectrum, f->size, f->d_fft_cs, inverse, NULL);
+}
+
 /* reference llz_asmodel.c:177-203: slide the input buffer by one frame, window, forward transform, bins 0..N/2 */
 void llz_analysis_fft(unsigned long handle, double *x, double *re, double *im)
 {
@@ -143,7 +152,7 @@ void llz_analysis_fft(unsigned long handle, double *x, double *re, double *im)
         rc = llzs_frame_slide_window_f64(f->d_io, f->d_run[f->cur], f->d_run[f->cur ^ 1], f->d_window, f->d_spectrum,
                                          f->size, f->hop, 1, NULL);
     if (rc == LLZ_OK) f->cur ^= 1;
-    if (rc == LLZ_OK) rc = llzs_fft_f64(f->d_spectrum, f->size, f->d_fft_cs, 0, NULL);
+    if (rc == LLZ_OK) rc = asm1_fft(f, 0);
     if (rc == LLZ_OK) rc = llzs_spectrum_split_f64(f->d_spectrum, f->d_io, f->bins, NULL);
     if (rc == LLZ_OK) rc = llzs_d2h(re, f->d_io, plane, NULL);
     if (rc == LLZ_OK) rc = llzs_d2h(im, f->d_io + f->bins, plane, NULL);
@@ -163,7 +172,7 @@ void llz_synthesis_fft(unsigned long handle, double *re, double *im, double *x)
     int rc = llzs_h2d(f->d_io, re, plane, NULL);
     if (rc == LLZ_OK) rc = llzs_h2d(f->d_io + f->bins, im, plane, NULL);
     if (rc == LLZ_OK) rc = llzs_spectrum_mirror_f64(f->d_io, f->d_spectrum, f->size, NULL);
-    if (rc == LLZ_OK) rc = llzs_fft_f64(f->d_spectrum, f->size, f->d_fft_cs, 1, NULL);
+    if (rc == LLZ_OK) rc = asm1_fft(f, 1);
     if (rc == LLZ_OK)
         rc = llzs_frame_overlap_add_f64(f->d_spectrum, 2, f->d_window, f->d_run[f->cur], f->d_run[f->cur ^ 1], f->d_io,
                                         f->size, f->hop, f->out_scale, NULL);
@@ -291,24 +300,31 @@ void llz_synthesis_mdct(unsigned long handle, double *X, double *x)
     llzs_device_leave(prev);
 }
 
-/* ---- Part 2: batch extension ---- */
+/* ---- Part 2: batch extension ----
+ * fft_len up to 4096: one launch per direction (kernels/fft.hip).  Above 4096, and at 4096 under the fft_generic tune: the
+ * composed form -- framing kernel, the float32 batch transform of llz_fft_batch on a scratch buffer, framing kernel
+ * (kernels/stft_large.hip) -- over chunks of at most LLZS_STFT_CHUNK_POINTS points, so the scratch stays bounded whatever
+ * a call's frame count.  (A one-launch form of 8192 on the staged LDS kernels measured slower than the composed form:
+ * DESIGN.md section 3, rank 3.) */
 
 typedef struct {
     int tag, device, channels, frame_len, fft_len, bins;
     float magic;
     float *d_w, *d_cs;
+    float *d_twb;                       /* fft_len above 4096: the large transform's LDS-block table (llz_fft_batch_init's) */
     float *d_hist[2], *d_ola[2];        /* analysis history / synthesis overlap-add tail: [channels][fft_len-frame_len] */
     int cur_hist, cur_ola;
     llz_stage_t st_x, st_re, st_im;
+    llz_stage_t st_z;                   /* the composed form's scratch: one chunk of frames, then the synthesis tails */
     void *stream;
 } asmm_t;
 
 static void asmm_destroy(asmm_t *f)
 {
     if (!f) return;
-    llzs_free(f->d_w); llzs_free(f->d_cs);
+    llzs_free(f->d_w); llzs_free(f->d_cs); llzs_free(f->d_twb);
     llzs_free(f->d_hist[0]); llzs_free(f->d_hist[1]); llzs_free(f->d_ola[0]); llzs_free(f->d_ola[1]);
-    llz_stage_release(&f->st_x); llz_stage_release(&f->st_re); llz_stage_release(&f->st_im);
+    llz_stage_release(&f->st_x); llz_stage_release(&f->st_re); llz_stage_release(&f->st_im); llz_stage_release(&f->st_z);
     f->tag = 0;
     free(f);
 }
@@ -317,9 +333,9 @@ unsigned long llz_stft_mc_init(int channels, int overlap_hint, int frame_len, wi
 {
     int N;
     double magic;
-    if (channels < 1 || !asm_shape(overlap_hint, frame_len, &N, &magic) || N < 8 || N > 2048) {
-        llzs_set_error("llz_stft_mc_init: channels %d overlap_hint %d frame_len %d (fft_len a power of two in 8..2048)",
-                       channels, overlap_hint, frame_len);
+    if (channels < 1 || !asm_shape(overlap_hint, frame_len, &N, &magic) || N < 8 || N > LLZS_FFT_MAX) {
+        llzs_set_error("llz_stft_mc_init: channels %d overlap_hint %d frame_len %d (fft_len a power of two in 8..%d)",
+                       channels, overlap_hint, frame_len, LLZS_FFT_MAX);
         return LLZ_BAD_HANDLE;
     }
     asmm_t *f = (asmm_t *)calloc(1, sizeof(*f));
@@ -349,6 +365,13 @@ unsigned long llz_stft_mc_init(int channels, int overlap_hint, int frame_len, wi
         if (!f->d_w || !f->d_cs || !f->d_hist[0] || !f->d_hist[1] || !f->d_ola[0] || !f->d_ola[1]) rc = LLZ_ERR_NOMEM;
         if (rc == LLZ_OK) rc = llzs_h2d(f->d_w, tab, sizeof(float) * (size_t)N, NULL);
         if (rc == LLZ_OK) rc = llzs_h2d(f->d_cs, tab + N, sizeof(float) * 2 * (size_t)N, NULL);
+        if (rc == LLZ_OK && N > 4096) {                              /* as llz_fft_batch_init builds it */
+            f->d_twb = (float *)llzs_malloc((size_t)llzs_fft_large_twb_bytes(N));
+            rc = f->d_twb ? llzs_fft_large_twb(f->d_twb, N, f->d_cs, NULL) : LLZ_ERR_NOMEM;
+        }
+        if (rc == LLZ_ERR_NOMEM)
+            llzs_set_error("llz_stft_mc_init: device allocation failed (channels %d fft_len %d: 4 x %zu bytes of state)",
+                           channels, N, keep);
         for (int k = 0; k < 2 && rc == LLZ_OK; k++) {
             rc = llzs_memset(f->d_hist[k], 0, keep, NULL);
             if (rc == LLZ_OK) rc = llzs_memset(f->d_ola[k], 0, keep, NULL);
@@ -413,6 +436,71 @@ static int asmm_stage(asmm_t *f, const float *x, const float *re, const float *i
     return rc;
 }
 
+/* the composed form: fft_len above 4096, or 4096 under the fft_generic tune (the A/B of the one-launch kernels) */
+static int asmm_composed(const asmm_t *f)
+{
+    return f->fft_len > 4096 || (f->fft_len == 4096 && llzs_tune(LLZS_TUNE_FFT_GENERIC) == 1);
+}
+
+/* transforms per chunk, and the scratch of a chunk: count * N complex points, then (synthesis) the tails of the chunk's
+ * channels (at most count + 1 of them) */
+static int asmm_chunk(const asmm_t *f)
+{
+    const int count = LLZS_STFT_CHUNK_POINTS / f->fft_len;
+    return count > 0 ? count : 1;
+}
+
+static float *asmm_scratch(asmm_t *f, int count, int with_tails)
+{
+    const long tails = with_tails ? (count + 1 < f->channels ? count + 1 : f->channels) : 0;
+    const size_t bytes = sizeof(float) * ((size_t)2 * count * f->fft_len + (size_t)tails * (f->fft_len - f->frame_len));
+    float *z = (float *)llz_stage_reserve(&f->st_z, bytes);
+    if (!z) llzs_set_error("llz_stft_mc: no device memory for the %zu-byte transform scratch", bytes);
+    return z;
+}
+
+/* the float32 batch transform of llz_fft_batch (fftb_launch in llz_fft_host.c) */
+static int asmm_fft(const asmm_t *f, float *z, int count, int inverse)
+{
+    return f->fft_len <= 4096 ? llzs_fft_f32(z, count, f->fft_len, f->d_cs, inverse, f->stream)
+                              : llzs_fft_large_f32(z, count, f->fft_len, f->d_cs, f->d_twb, inverse, f->stream);
+}
+
+static int asmm_analysis_composed(asmm_t *f, const float *dx, float *dre, float *dim, int frames, long x_pitch)
+{
+    const long total = (long)f->channels * frames;
+    const int chunk = asmm_chunk(f);
+    float *z = asmm_scratch(f, (int)(total < chunk ? total : chunk), 0);
+    int rc = z ? LLZ_OK : LLZ_ERR_NOMEM;
+    for (long g0 = 0; g0 < total && rc == LLZ_OK; g0 += chunk) {
+        const int count = (int)(total - g0 < chunk ? total - g0 : chunk);
+        rc = llzs_stft_frames_large_f32(dx, f->d_hist[f->cur_hist], z, f->d_w, frames, f->frame_len, f->fft_len, x_pitch,
+                                        g0, count, f->stream);
+        if (rc == LLZ_OK) rc = asmm_fft(f, z, count, 0);
+        if (rc == LLZ_OK) rc = llzs_stft_bins_large_f32(z, dre, dim, f->fft_len, g0, count, f->stream);
+    }
+    return rc;
+}
+
+static int asmm_synthesis_composed(asmm_t *f, const float *dre, const float *dim, float *dx, int frames, long x_pitch)
+{
+    const long total = (long)f->channels * frames;
+    const int chunk = asmm_chunk(f);
+    const int most = (int)(total < chunk ? total : chunk);
+    float *z = asmm_scratch(f, most, 1);
+    int rc = z ? LLZ_OK : LLZ_ERR_NOMEM;
+    float *tails = z + (size_t)2 * most * f->fft_len;
+    for (long g0 = 0; g0 < total && rc == LLZ_OK; g0 += chunk) {
+        const int count = (int)(total - g0 < chunk ? total - g0 : chunk);
+        rc = llzs_stft_mirror_large_f32(dre, dim, z, f->fft_len, g0, count, f->stream);
+        if (rc == LLZ_OK) rc = asmm_fft(f, z, count, 1);
+        if (rc == LLZ_OK)
+            rc = llzs_stft_ola_large_f32(z, dx, f->d_ola[f->cur_ola], f->d_ola[f->cur_ola ^ 1], tails, f->d_w, frames,
+                                         f->frame_len, f->fft_len, x_pitch, g0, count, f->magic, f->stream);
+    }
+    return rc;
+}
+
 int llz_stft_mc_analysis(unsigned long handle, const float *x, float *re, float *im, int frames)
 {
     if (!LLZ_HANDLE_OK(handle, asmm_t, LLZ_TAG_ASMM) || !x || !re || !im || frames < 1) {
@@ -424,12 +512,14 @@ int llz_stft_mc_analysis(unsigned long handle, const float *x, float *re, float 
     float *dx, *dre, *dim;
     const int prev = llzs_device_enter(f->device);
     int rc = asmm_stage(f, x, re, im, frames, 1, &dx, &dre, &dim);
-    if (rc == LLZ_OK)
+    if (rc == LLZ_OK && asmm_composed(f))
+        rc = asmm_analysis_composed(f, dx, dre, dim, frames, n);
+    else if (rc == LLZ_OK)
         rc = llzs_stft_analysis_f32(dx, f->d_hist[f->cur_hist], dre, dim, f->d_w, f->d_cs, f->channels, frames,
                                     f->frame_len, f->fft_len, n, f->stream);
     /* history for the next call: the last fft_len - frame_len samples of concat(history, x) */
     if (rc == LLZ_OK)
-        rc = llzs_fir_tail_f32(dx, f->d_hist[f->cur_hist], f->d_hist[f->cur_hist ^ 1], f->channels, (int)n, n,
+        rc = llzs_fir_tail_f32(dx, f->d_hist[f->cur_hist], f->d_hist[f->cur_hist ^ 1], f->channels, n, n,
                                f->fft_len - f->frame_len + 1, f->stream);
     if (rc == LLZ_OK) f->cur_hist ^= 1;
     const size_t sb = sizeof(float) * (size_t)f->channels * frames * f->bins;
@@ -450,7 +540,9 @@ int llz_stft_mc_synthesis(unsigned long handle, const float *re, const float *im
     float *dx, *dre, *dim;
     const int prev = llzs_device_enter(f->device);
     int rc = asmm_stage(f, x, re, im, frames, 0, &dx, &dre, &dim);
-    if (rc == LLZ_OK)
+    if (rc == LLZ_OK && asmm_composed(f))
+        rc = asmm_synthesis_composed(f, dre, dim, dx, frames, n);
+    else if (rc == LLZ_OK)
         rc = llzs_stft_synthesis_f32(dre, dim, dx, f->d_ola[f->cur_ola], f->d_ola[f->cur_ola ^ 1], f->d_w, f->d_cs,
                                      f->channels, frames, f->frame_len, f->fft_len, n, f->magic, f->stream);
     if (rc == LLZ_OK) f->cur_ola ^= 1;

@@ -262,7 +262,9 @@ k_stft_analysis1024_f32(const float *__restrict__ x, const float *__restrict__ h
 // windowed inverse transforms of frames t-R+1 .. t (llz_asmodel.c:279-304), so the workgroup walks frames
 // max(0, b0-R+1) .. b1-1 in groups of tpw, keeps the running overlap-add tail (size - F samples) in LDS and drops the
 // blocks in front of b0 (their sums are incomplete; the first run of a channel starts from the handle's tail instead).
-// Accumulation order per sample is the reference's: oldest frame first.
+// Accumulation order per sample is the reference's: oldest frame first.  ACC = FFT_THREADS-sample slices of a group's
+// span: 8 up to fft_len 2048 (tpw frames in 2048 points), 16 for the one-frame groups of fft_len 4096.
+template <int ACC>
 __global__ void __launch_bounds__(FFT_THREADS)
 k_stft_synthesis_f32(const float *__restrict__ re, const float *__restrict__ im, float *__restrict__ x,
                      const float *__restrict__ ola_old, float *__restrict__ ola_new, const float *__restrict__ w,
@@ -314,10 +316,10 @@ k_stft_synthesis_f32(const float *__restrict__ re, const float *__restrict__ im,
             done += G;
         }
         // overlap-add over the group's span: position p counts from the group's first block
-        const int span = (ng - 1) * F + size;                              // <= 2048
-        float acc[8];
+        const int span = (ng - 1) * F + size;                              // <= ACC * FFT_THREADS
+        float acc[ACC];
 #pragma unroll
-        for (int m = 0; m < 8; m++) {
+        for (int m = 0; m < ACC; m++) {
             const int p = tid + m * FFT_THREADS;
             float a = 0.f;
             if (p < span) {
@@ -333,7 +335,7 @@ k_stft_synthesis_f32(const float *__restrict__ re, const float *__restrict__ im,
         }
         __syncthreads();                                                   // every read of carry and s is done
 #pragma unroll
-        for (int m = 0; m < 8; m++) {
+        for (int m = 0; m < ACC; m++) {
             const int p = tid + m * FFT_THREADS;
             if (p < span) {
                 if (p < ng * F) {
@@ -1955,9 +1957,9 @@ static int stft_check(int channels, int frames, int F, int size, int *log2n, con
 {
     *log2n = 0;
     while ((1 << *log2n) < size) (*log2n)++;
-    if (channels < 1 || frames < 1 || F < 1 || size < 8 || size > 2048 || (1 << *log2n) != size ||
+    if (channels < 1 || frames < 1 || F < 1 || size < 8 || size > 4096 || (1 << *log2n) != size ||
         (size != 2 * F && size != 4 * F)) {
-        llzs_set_error("%s: bad shape (channels=%d frames=%d frame_len=%d fft_len=%d; fft_len a power of two in 8..2048)",
+        llzs_set_error("%s: bad shape (channels=%d frames=%d frame_len=%d fft_len=%d; fft_len a power of two in 8..4096)",
                        who, channels, frames, F, size);
         return LLZ_ERR_ARG;
     }
@@ -2030,7 +2032,7 @@ extern "C" int llzs_stft_analysis_f32(const float *x, const float *hist, float *
         LLZ_LAUNCH_CHECK("k_stft_analysis1024_f32");
         return LLZ_OK;
     }
-    int tpw = 2048 / size;
+    int tpw = size <= 2048 ? 2048 / size : 1;                           // 4096: one frame per workgroup, 50 KB of LDS
     if (tpw > total_tr) tpw = (int)total_tr;
     const int tstride = size + (size >> 5) + 1;
     const size_t lds = (size_t)tpw * tstride * 2 * sizeof(float) + (size_t)tw_entries(size) * 2 * sizeof(float);
@@ -2053,10 +2055,11 @@ extern "C" int llzs_stft_synthesis_f32(const float *re, const float *im, float *
     const int rc = stft_check(channels, frames, F, size, &log2n, "stft_synthesis_f32");
     if (rc != LLZ_OK) return rc;
     const int R = size / F;
-    int tpw = 2048 / size;
+    int tpw = size <= 2048 ? 2048 / size : 1;
     if (tpw > frames) tpw = frames;
     // blocks per workgroup: enough workgroups to fill the chip, long enough that the R-1 warm-up frames stay cheap
     long want = ((long)frames * channels + 2047) / 2048;
+    if (want > frames) want = frames;                                   // (clamped before the int: no overflow)
     int run_len = (int)(want < 8 * R ? 8 * R : want);
     if (run_len < tpw) run_len = tpw;
     if (run_len > frames) run_len = frames;
@@ -2103,9 +2106,13 @@ extern "C" int llzs_stft_synthesis_f32(const float *re, const float *im, float *
     const int tstride = size + (size >> 5) + 1;
     const size_t lds = (size_t)tpw * tstride * 2 * sizeof(float) + (size_t)tw_entries(size) * 2 * sizeof(float) +
                        (size_t)(size - F) * sizeof(float);
-    hipLaunchKernelGGL(k_stft_synthesis_f32, dim3((unsigned)((long)channels * runs)), dim3(FFT_THREADS), lds,
-                       as_stream(stream), re, im, x, ola_old, ola_new, w, frames, F, size, log2n, cs, tpw,
-                       stft_groups(log2n), x_pitch, run_len, runs, magic);
+    const dim3 grid((unsigned)((long)channels * runs));
+    if (size <= 2048)
+        hipLaunchKernelGGL(k_stft_synthesis_f32<8>, grid, dim3(FFT_THREADS), lds, as_stream(stream), re, im, x, ola_old,
+                           ola_new, w, frames, F, size, log2n, cs, tpw, stft_groups(log2n), x_pitch, run_len, runs, magic);
+    else                                                                // 4096: <= 62 KB of LDS
+        hipLaunchKernelGGL(k_stft_synthesis_f32<16>, grid, dim3(FFT_THREADS), lds, as_stream(stream), re, im, x, ola_old,
+                           ola_new, w, frames, F, size, log2n, cs, tpw, stft_groups(log2n), x_pitch, run_len, runs, magic);
     LLZ_LAUNCH_CHECK("k_stft_synthesis_f32");
     return LLZ_OK;
 }

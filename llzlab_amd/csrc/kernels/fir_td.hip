@@ -115,12 +115,12 @@ k_fir_td_f32(const float *__restrict__ in, float *__restrict__ out, const float 
 // hist_new[c][j] = sample (n - (T-1) + j) of concat(hist_old, in): one thread per element
 __global__ void __launch_bounds__(256)
 k_fir_tail_f32(const float *__restrict__ in, const float *__restrict__ hist_old, float *__restrict__ hist_new,
-               int n, long in_pitch, int keep)
+               long n, long in_pitch, int keep)
 {
     const int c = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= keep) return;
-    const long idx = (long)n - keep + j;            // index into this call's input; negative -> old history
+    const long idx = n - keep + j;                  // index into this call's input; negative -> old history
     float v;
     if (idx >= 0) v = in[(size_t)c * in_pitch + idx];
     else v = hist_old[(size_t)c * keep + (keep + idx)];
@@ -182,7 +182,7 @@ extern "C" int llzs_fir_td_f32(const float *in, float *out, const float *hist, c
     return LLZ_OK;
 }
 
-extern "C" int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new, int channels, int n,
+extern "C" int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new, int channels, long n,
                                  long in_pitch, int flt_len, void *stream)
 {
     const int keep = flt_len - 1;

@@ -128,7 +128,7 @@ int llzs_fir_mfma_i16x_fits(int T, int M);
 #define LLZS_MX_PLANES 5
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
-                      int channels, int n, long in_pitch, int flt_len, void *stream);
+                      int channels, long n, long in_pitch, int flt_len, void *stream);
 /* single channel, double, the reference's exact accumulation order (ascending k, multiply then add) */
 int llzs_fir_td_f64(const double *in, double *out, const double *hist, const double *taps,
                     int n, int flt_len, void *stream);
@@ -269,14 +269,27 @@ int llzs_levinson_f32(const float *r, float *acof, float *kcof, float *err, floa
 /* y[f][i] = x[f][i] * win[i] (float32, one rounding) */
 int llzs_window_f32(const float *x, const float *win, float *y, int frames, int n, void *stream);
 
-/* windowed-FFT frames (llz_asmodel.c:180-310), float32 batch: x planar [C][frames*F] (row pitch x_pitch), spectra
- * [C][frames][size/2+1]; hist / ola: [C][size-F] state carried between calls (ola_old != ola_new); w: size floats;
- * cs: cos then sin of 2*pi*i/size */
+/* windowed-FFT frames (llz_asmodel.c:180-310), float32 batch, fft_len 8..4096 in one launch per direction: x planar
+ * [C][frames*F] (row pitch x_pitch), spectra [C][frames][size/2+1]; hist / ola: [C][size-F] state carried between calls
+ * (ola_old != ola_new); w: size floats; cs: cos then sin of 2*pi*i/size */
 int llzs_stft_analysis_f32(const float *x, const float *hist, float *re, float *im, const float *w, const float *cs,
                            int channels, int frames, int F, int size, long x_pitch, void *stream);
 int llzs_stft_synthesis_f32(const float *re, const float *im, float *x, const float *ola_old, float *ola_new,
                             const float *w, const float *cs, int channels, int frames, int F, int size, long x_pitch,
                             float magic, void *stream);
+/* the composed form (stft_large.hip) for fft_len above 4096, and 4096 under the fft_generic tune: per chunk of
+ * `count` consecutive transforms g0 .. g0+count-1 (g = c * frames + f), z: count * N interleaved complex scratch points.
+ * frames: windowed frames into z; bins: bins 0..N/2 of z into re / im; mirror: Hermitian extension of re / im into z;
+ * ola: overlap-add of the inverse-transformed z into x, tail read from ola_old (a channel's first frame) or ola_new and
+ * written to ola_new through `tail` ((channels in the chunk) * (N - F) floats).  A chunk holds at most
+ * LLZS_STFT_CHUNK_POINTS points (at least one transform). */
+#define LLZS_STFT_CHUNK_POINTS (1 << 24)
+int llzs_stft_frames_large_f32(const float *x, const float *hist, float *z, const float *w, int frames, int F, int N,
+                               long x_pitch, long g0, int count, void *stream);
+int llzs_stft_bins_large_f32(const float *z, float *re, float *im, int N, long g0, int count, void *stream);
+int llzs_stft_mirror_large_f32(const float *re, const float *im, float *z, int N, long g0, int count, void *stream);
+int llzs_stft_ola_large_f32(const float *z, float *x, const float *ola_old, float *ola_new, float *tail, const float *w,
+                            int frames, int F, int N, long x_pitch, long g0, int count, float magic, void *stream);
 
 /* MDCT (llz_mdct.c): y[r] = sum_c x[c]*A[r][c] in ascending c, separately rounded multiply and add (device doubles) */
 int llzs_matvec_exact_f64(const double *A, const double *x, double *y, int rows, int cols, void *stream);
