@@ -167,7 +167,8 @@ static void firm_destroy(firm_t *f)
 
 /* The overlap-save sizes: algo, transform points, the taps the rung accepts, and auto_max: AUTO takes the first rung whose
  * auto_max holds the filter (from 33 taps on; up to 32 the time domain).  auto_max is a crossover measured on 4096 ch x 2^20
- * (tools/fir_crossover.py), not the rung's limit.  Beyond the last rung AUTO takes the matrix-core form of the time domain. */
+ * (tools/fir_crossover.py), not the rung's limit.  Beyond the last rung AUTO takes the time domain: the matrix-core form where
+ * the filter fits its LDS image (it never does there: that form ends at 1521 taps), else k_fir_td_f32, up to 25248 taps. */
 static const struct firm_ols_rung {
     int algo, nfft, min_taps, max_taps, auto_max;
 } FIRM_OLS[] = {
