@@ -37,7 +37,15 @@ int           llz_iir_cascade_mc_precision(unsigned long handle);
  * double arithmetic in the reference's operation order; delay lines stay on the device between calls. ---- */
 unsigned long llz_iir_mc_init(int channels, int M, const double *a, int N, const double *b);
 void          llz_iir_mc_uninit(unsigned long handle);
-/* planar [channels][frame_len] float32, device or host pointers, out of place; any frame_len >= 1. Returns frame_len. */
+/* planar [channels][frame_len] float32, device or host pointers, out of place; any frame_len >= 1. Returns frame_len.
+ * Time segments: to fill the chip, the batch forms (this one and the cascade of part 2) may split a channel's frame into
+ * segments that run in parallel.  The first continues from the handle's state; a later one starts early, from ZERO state,
+ * and drops its warm-up outputs.  The host probes the filter at init (its response to a unit state, zero input) and takes
+ * as warm-up the length after which that response stays below 1e-13 of its peak, so the state error of a segment is below
+ * 1e-13 of peak before its first kept sample; segments are at least 8 warm-ups long, and a filter that has not decayed within
+ * the probe is never split.  The output then equals the one-segment (reference-order) double sequence to about 1e-13
+ * relative before the rounding to float32, not bit for bit, and may depend on frame_len.  llz_hip_tune("iir_segs", 1)
+ * opts out: one segment per channel, bit for bit the reference's sequence rounded once. */
 int           llz_iir_mc(unsigned long handle, const float *x, float *y, int frame_len);
 int           llz_iir_mc_flush(unsigned long handle, float *y);         /* N more samples of x = 0 per channel: [channels][N]; returns N */
 int           llz_iir_mc_set_stream(unsigned long handle, void *stream);

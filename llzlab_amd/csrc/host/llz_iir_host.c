@@ -102,17 +102,17 @@ int llz_iir_filter_flush(unsigned long handle, double *y)
 
 /* ---- Part 2: multi-channel biquad cascade (k_iir_cascade_f32) ---- */
 
+#define IIRM_PIPE (-1)   /* the stage pipeline, next to the wave forms LLZS_IIR_WAVE*: what iirm_path chooses between */
+
 typedef struct {
     int tag;
     int channels, stages;
-    double *d_coef;      /* stages x {b0,b1,b2,a1,a2} */
-    double *d_pd, *d_pl; /* state-transition powers for the pipelined kernel: [S][6][4] and [S][64][12] */
-    float *d_coef32, *d_pd32, *d_pl32;   /* float copies for the wave-autonomous float32 kernel: [S][5], [S][16], [S][64][12] */
-    float *d_pd32w, *d_pl32w, *d_ph32w;   /* 32-sample-per-lane packed kernel: powers of A^32, ph [S][40] (b0 folded) */
-    float in_gain32;     /* the product of the b0's (that kernel scales the input once) */
-    double *d_cw64, *d_pd64w, *d_pl64w;   /* the same form in double (k_iir_cascade_wave_pf64w): cw [S][8], pd [S][16], plc [S][448] */
-    double in_gain64;
-    float *d_ph32;       /* [S][24]: (h1[k], h2[k]) k < 8 = zero-input outputs of the unit start states, b0 b1 b2 a1 a2, pad */
+    void *d_tab[10];     /* every coefficient table, in upload order; the views below point into them */
+    int ntab;
+    const double *d_coef;    /* stages x {b0,b1,b2,a1,a2} */
+    /* per wave form: the tables its kernel reads (llz_shim.h), pl == NULL where the form was not built.  WAVE16_F64 reads the
+     * stage pipeline's own: coef, pd [S][6][4], pl [S][64][12] */
+    llzs_iir_wave_tables wave[LLZS_IIR_WAVE_FORMS];
     double *d_state;     /* [channels][stages][x1,x2,y1,y2]: the current state */
     double *d_state_alt; /* where a time-segmented launch writes the frame's end state (then the two swap) */
     int warm_chunks;     /* 1024-sample chunks after which any state error has decayed below 1e-13 (0: unknown / too long) */
@@ -125,13 +125,31 @@ typedef struct {
 static void iirm_destroy(iirm_t *f)
 {
     if (!f) return;
-    llzs_free(f->d_coef); llzs_free(f->d_state); llzs_free(f->d_state_alt); llzs_free(f->d_pd); llzs_free(f->d_pl);
-    llzs_free(f->d_coef32); llzs_free(f->d_pd32); llzs_free(f->d_pl32); llzs_free(f->d_ph32);
-    llzs_free(f->d_pd32w); llzs_free(f->d_pl32w); llzs_free(f->d_ph32w);
-    llzs_free(f->d_cw64); llzs_free(f->d_pd64w); llzs_free(f->d_pl64w);
+    for (int i = 0; i < f->ntab; i++) llzs_free(f->d_tab[i]);
+    llzs_free(f->d_state); llzs_free(f->d_state_alt);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     f->tag = 0;
     free(f);
+}
+
+/* allocate the device tables of one group, then upload them in order (llzs_h2d_table: a sharded init pairs them by index),
+ * or fail; the handle owns whatever was allocated */
+typedef struct {
+    const void **dev;
+    const void *host;
+    size_t bytes;
+} iirm_up_t;
+
+static int iirm_upload(iirm_t *f, const iirm_up_t *u, int n)
+{
+    int rc = LLZ_OK;
+    for (int i = 0; i < n; i++) {
+        void *d = llzs_malloc(u[i].bytes);
+        if (d) f->d_tab[f->ntab++] = d; else rc = LLZ_ERR_NOMEM;
+        *u[i].dev = d;
+    }
+    for (int i = 0; i < n && rc == LLZ_OK; i++) rc = llzs_h2d_table((void *)*u[i].dev, u[i].host, u[i].bytes);
+    return rc;
 }
 
 static void mat2_mul(const double *a, const double *b, double *o)
@@ -141,187 +159,151 @@ static void mat2_mul(const double *a, const double *b, double *o)
     o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3;
 }
 
-/* transition matrices of the feedback recurrence (y[n-1], y[n-2]) -> 16 samples later, its powers of two for the
- * lane scan and its lane-th powers: see k_iir_cascade_pipe_f32 */
-static int iirm_build_powers(iirm_t *f, const double *c5, int lane_run)
+/* Powers of a section's transition matrix P = A^run, A = [[-a1,-a2],[1,0]]: the feedback recurrence (y[n-1], y[n-2]) ->
+ * `run` samples later (one lane's samples).  p2 = P^(2^d) for the lane scan, pw = P^0 .. P^64, pl = per lane P^lane,
+ * P^(lane%16+1), P^(lane%32+1): see k_iir_cascade_pipe_f32.  All 2 x 2 row major. */
+typedef struct {
+    double p2[6][4], pw[65][4], pl[64][12];
+} iirm_pow_t;
+
+static void iirm_powers(double a1, double a2, int run, iirm_pow_t *o)
 {
-    const int S = f->stages;
-    double *pd = (double *)malloc(sizeof(double) * (size_t)S * 6 * 4);
-    double *pl = (double *)malloc(sizeof(double) * (size_t)S * 64 * 12);
-    int rc = (pd && pl) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) {
-        for (int s = 0; s < S; s++) {
-            const double A[4] = {-c5[5 * s + 3], -c5[5 * s + 4], 1.0, 0.0};
-            double P[4] = {1.0, 0.0, 0.0, 1.0};
-            for (int i = 0; i < lane_run; i++) mat2_mul(A, P, P);      /* P = A^lane_run (16 or 32 samples per lane) */
-            double *d = pd + (size_t)s * 24;
-            memcpy(d, P, sizeof(P));
-            for (int k = 1; k < 6; k++) mat2_mul(d + 4 * (k - 1), d + 4 * (k - 1), d + 4 * k);
-            double pw[65][4];                                          /* P^0 .. P^64 */
-            pw[0][0] = 1.0; pw[0][1] = 0.0; pw[0][2] = 0.0; pw[0][3] = 1.0;
-            for (int k = 1; k <= 64; k++) mat2_mul(P, pw[k - 1], pw[k]);
-            for (int lane = 0; lane < 64; lane++) {                    /* per lane: P^lane, P^(lane%16+1), P^(lane%32+1) */
-                double *l = pl + ((size_t)s * 64 + lane) * 12;
-                memcpy(l, pw[lane], sizeof(pw[0]));
-                memcpy(l + 4, pw[lane % 16 + 1], sizeof(pw[0]));
-                memcpy(l + 8, pw[lane % 32 + 1], sizeof(pw[0]));
-            }
-        }
-        f->d_pd = (double *)llzs_malloc(sizeof(double) * (size_t)S * 24);
-        f->d_pl = (double *)llzs_malloc(sizeof(double) * (size_t)S * 768);
-        rc = (f->d_pd && f->d_pl) ? LLZ_OK : LLZ_ERR_NOMEM;
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pd, pd, sizeof(double) * (size_t)S * 24);
-        if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pl, pl, sizeof(double) * (size_t)S * 768);
-        if (rc == LLZ_OK && f->float32_ok) {                           /* float copies for k_iir_cascade_wave_f32 */
-            float *t = (float *)malloc(sizeof(float) * (size_t)S * (5 + 16 + 768 + 24));
-            if (!t) rc = LLZ_ERR_NOMEM;
-            if (rc == LLZ_OK) {
-                float *c32 = t, *pd32 = t + 5 * S, *pl32 = pd32 + 16 * S;
-                for (int i = 0; i < 5 * S; i++) c32[i] = (float)c5[i];
-                for (int s = 0; s < S; s++)
-                    for (int i = 0; i < 16; i++) pd32[16 * s + i] = (float)pd[24 * s + i];
-                for (int i = 0; i < 768 * S; i++) pl32[i] = (float)pl[i];
-                float *ph32 = pl32 + 768 * S;
-                for (int s = 0; s < S; s++) {                          /* y[k] from (y[-1], y[-2]) = (1,0) and (0,1) */
-                    const double a1 = c5[5 * s + 3], a2 = c5[5 * s + 4];
-                    double p1 = 1.0, p2 = 0.0, q1 = 0.0, q2 = 1.0;
-                    for (int k = 0; k < 8; k++) {
-                        const double h1 = -a1 * p1 - a2 * p2, h2 = -a1 * q1 - a2 * q2;
-                        ph32[24 * s + 2 * k] = (float)h1; ph32[24 * s + 2 * k + 1] = (float)h2;
-                        p2 = p1; p1 = h1; q2 = q1; q1 = h2;
-                    }
-                    for (int k = 0; k < 8; k++) ph32[24 * s + 16 + k] = k < 5 ? (float)c5[5 * s + k] : 0.f;
-                }
-                f->d_coef32 = (float *)llzs_malloc(sizeof(float) * 5 * (size_t)S);
-                f->d_pd32 = (float *)llzs_malloc(sizeof(float) * 16 * (size_t)S);
-                f->d_pl32 = (float *)llzs_malloc(sizeof(float) * 768 * (size_t)S);
-                f->d_ph32 = (float *)llzs_malloc(sizeof(float) * 24 * (size_t)S);
-                if (!f->d_coef32 || !f->d_pd32 || !f->d_pl32 || !f->d_ph32) rc = LLZ_ERR_NOMEM;
-                if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_coef32, c32, sizeof(float) * 5 * (size_t)S);
-                if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pd32, pd32, sizeof(float) * 16 * (size_t)S);
-                if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pl32, pl32, sizeof(float) * 768 * (size_t)S);
-                if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_ph32, ph32, sizeof(float) * 24 * (size_t)S);
-            }
-            free(t);
-        }
+    const double A[4] = {-a1, -a2, 1.0, 0.0};
+    double P[4] = {1.0, 0.0, 0.0, 1.0};
+    for (int i = 0; i < run; i++) mat2_mul(A, P, P);
+    memcpy(o->p2[0], P, sizeof(P));
+    for (int d = 1; d < 6; d++) mat2_mul(o->p2[d - 1], o->p2[d - 1], o->p2[d]);
+    o->pw[0][0] = 1.0; o->pw[0][1] = 0.0; o->pw[0][2] = 0.0; o->pw[0][3] = 1.0;
+    for (int k = 1; k <= 64; k++) mat2_mul(P, o->pw[k - 1], o->pw[k]);
+    for (int lane = 0; lane < 64; lane++) {
+        memcpy(o->pl[lane], o->pw[lane], sizeof(P));
+        memcpy(o->pl[lane] + 4, o->pw[lane % 16 + 1], sizeof(P));
+        memcpy(o->pl[lane] + 8, o->pw[lane % 32 + 1], sizeof(P));
     }
-    free(pd); free(pl);
+}
+
+/* the homogeneous responses h[2k], h[2k+1] = y[k] from (y[-1], y[-2]) = (1,0) and (0,1) with zero input, k < K */
+static void iirm_h_responses(double a1, double a2, int K, float *h)
+{
+    double p1 = 1.0, p2 = 0.0, q1 = 0.0, q2 = 1.0;
+    for (int k = 0; k < K; k++) {
+        const double h1 = -a1 * p1 - a2 * p2, h2 = -a1 * q1 - a2 * q2;
+        h[2 * k] = (float)h1; h[2 * k + 1] = (float)h2;
+        p2 = p1; p1 = h1; q2 = q1; q1 = h2;
+    }
+}
+
+/* May the b0 gains be folded out of the sections (b' = b / b0, states scaled by xfac_s = prod_{t >= s} b0_t)?  Every b0 must
+ * be usable as a divisor and the partial products must stay inside the arithmetic's range; fills xfac[0..S] when so. */
+typedef struct {
+    double b0_min, xfac_min, xfac_max, ratio_max;
+} iirm_fold_t;
+/* (float32: the scaled states and the scaled input must stay clear of the denormals: signals down to 1e-10 of full scale
+ *  times a partial product of 1e-20 are still 1e-30) */
+static const iirm_fold_t IIRM_FOLD32 = {1e-12, 1e-20, 1e20, 1e4}, IIRM_FOLD64 = {1e-30, 1e-150, 1e150, 1e6};
+
+static int iirm_fold(const double *c5, int S, const iirm_fold_t *lim, double *xfac)
+{
+    xfac[S] = 1.0;
+    for (int s = S - 1; s >= 0; s--) {
+        const double b0 = c5[5 * s];
+        xfac[s] = xfac[s + 1] * b0;
+        if (!(fabs(b0) > lim->b0_min) || !(fabs(xfac[s]) > lim->xfac_min && fabs(xfac[s]) < lim->xfac_max) ||
+            !(fabs(c5[5 * s + 1] / b0) < lim->ratio_max) || !(fabs(c5[5 * s + 2] / b0) < lim->ratio_max)) return 0;
+    }
+    return 1;
+}
+
+/* 16 samples per lane: the stage pipeline's double tables (any section count; WAVE16_F64 reads them too) and, where float32
+ * arithmetic is good enough, float copies with the h responses and the coefficients for WAVE16_F32 */
+static int iirm_build_run16(iirm_t *f, const double *c5)
+{
+    const size_t S = (size_t)f->stages;
+    double *pd = (double *)malloc(sizeof(double) * S * (24 + 768));
+    float *pd32 = (float *)malloc(sizeof(float) * S * (16 + 768 + 24));
+    int rc = (pd && pd32) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {
+        double *pl = pd + 24 * S;
+        float *pl32 = pd32 + 16 * S, *ph32 = pl32 + 768 * S;
+        for (size_t s = 0; s < S; s++) {
+            iirm_pow_t w;
+            iirm_powers(c5[5 * s + 3], c5[5 * s + 4], 16, &w);
+            memcpy(pd + 24 * s, w.p2, sizeof(w.p2));
+            memcpy(pl + 768 * s, w.pl, sizeof(w.pl));
+            for (int i = 0; i < 16; i++) pd32[16 * s + i] = (float)pd[24 * s + i];
+            for (int i = 0; i < 768; i++) pl32[768 * s + i] = (float)pl[768 * s + i];
+            iirm_h_responses(c5[5 * s + 3], c5[5 * s + 4], 8, ph32 + 24 * s);
+            for (int k = 0; k < 8; k++) ph32[24 * s + 16 + k] = k < 5 ? (float)c5[5 * s + k] : 0.f;
+        }
+        llzs_iir_wave_tables *d = &f->wave[LLZS_IIR_WAVE16_F64], *d32 = &f->wave[LLZS_IIR_WAVE16_F32];
+        const iirm_up_t up[2] = {{&d->pd, pd, sizeof(double) * 24 * S}, {&d->pl, pl, sizeof(double) * 768 * S}};
+        const iirm_up_t up32[3] = {{&d32->pd, pd32, sizeof(float) * 16 * S}, {&d32->pl, pl32, sizeof(float) * 768 * S},
+                                   {&d32->cf, ph32, sizeof(float) * 24 * S}};
+        d->cf = f->d_coef;
+        rc = iirm_upload(f, up, 2);
+        if (rc == LLZ_OK && f->float32_ok) rc = iirm_upload(f, up32, 3);
+    }
+    free(pd); free(pd32);
     return rc;
 }
 
-/* Tables of the packed float32 kernel with 32 samples per lane and the b0 gains folded out (k_iir_cascade_wave_pk32):
- * powers of P = A^32 for the lane scan, the homogeneous responses h1[k], h2[k] for k < 16, the section's b1/b0, b2/b0,
- * a1, a2, and the state scales xfac_s = prod_{t >= s} b0_t, yfac_s = prod_{t > s} b0_t.  Built only when every b0 is
- * usable as a divisor (no zero gain, partial products between 1e-20 and 1e20); otherwise the 16-sample kernel runs. */
+/* 32 samples per lane, b0 folded out, float32 (WAVE32_F32; layouts: llz_shim.h).  Not built when the gains cannot be folded:
+ * the 16-sample form runs. */
 static int iirm_build_run32(iirm_t *f, const double *c5)
 {
-    const int S = f->stages;
-    if (S > 8 || !f->float32_ok) return LLZ_OK;
+    const size_t S = (size_t)f->stages;
     double xfac[9];
-    xfac[S] = 1.0;
-    for (int s = S - 1; s >= 0; s--) {
-        const double b0 = c5[5 * s];
-        xfac[s] = xfac[s + 1] * b0;
-        /* (the scaled states and the scaled input must stay clear of the float32 denormals: signals down to 1e-10 of full
-         *  scale times a partial product of 1e-20 are still 1e-30) */
-        if (!(fabs(b0) > 1e-12) || !(fabs(xfac[s]) > 1e-20 && fabs(xfac[s]) < 1e20) ||
-            !(fabs(c5[5 * s + 1] / b0) < 1e4) || !(fabs(c5[5 * s + 2] / b0) < 1e4)) return LLZ_OK;
+    if (S > 8 || !f->float32_ok || !iirm_fold(c5, (int)S, &IIRM_FOLD32, xfac)) return LLZ_OK;
+    float *pd = (float *)calloc(S * (16 + 768 + 40), sizeof(float));
+    if (!pd) return LLZ_ERR_NOMEM;
+    float *pl = pd + 16 * S, *ph = pl + 768 * S;
+    for (size_t s = 0; s < S; s++) {
+        const double b0 = c5[5 * s], a1 = c5[5 * s + 3], a2 = c5[5 * s + 4];
+        iirm_pow_t w;
+        iirm_powers(a1, a2, 32, &w);
+        const double *p2 = &w.p2[0][0], *wl = &w.pl[0][0];
+        for (int i = 0; i < 16; i++) pd[16 * s + i] = (float)p2[i];
+        for (int i = 0; i < 768; i++) pl[768 * s + i] = (float)wl[i];
+        iirm_h_responses(a1, a2, 16, ph + 40 * s);
+        const float c[7] = {1.f, (float)(c5[5 * s + 1] / b0), (float)(c5[5 * s + 2] / b0), (float)a1, (float)a2,
+                            (float)xfac[s], (float)xfac[s + 1]};
+        memcpy(ph + 40 * s + 32, c, sizeof(c));
     }
-    float *t = (float *)calloc((size_t)S * (16 + 768 + 40), sizeof(float));
-    if (!t) return LLZ_ERR_NOMEM;
-    float *pd = t, *pl = t + 16 * S, *ph = pl + 768 * S;
-    for (int s = 0; s < S; s++) {
-        const double a1 = c5[5 * s + 3], a2 = c5[5 * s + 4];
-        const double A[4] = {-a1, -a2, 1.0, 0.0};
-        double P[4] = {1.0, 0.0, 0.0, 1.0};
-        for (int i = 0; i < 32; i++) mat2_mul(A, P, P);
-        double pw2[4][4];                                          /* P^(2^d), d < 4 */
-        memcpy(pw2[0], P, sizeof(P));
-        for (int d = 1; d < 4; d++) mat2_mul(pw2[d - 1], pw2[d - 1], pw2[d]);
-        for (int d = 0; d < 4; d++)
-            for (int i = 0; i < 4; i++) pd[16 * s + 4 * d + i] = (float)pw2[d][i];
-        double pw[65][4];
-        pw[0][0] = 1.0; pw[0][1] = 0.0; pw[0][2] = 0.0; pw[0][3] = 1.0;
-        for (int k = 1; k <= 64; k++) mat2_mul(P, pw[k - 1], pw[k]);
-        for (int lane = 0; lane < 64; lane++) {                    /* per lane: P^lane, P^(lane%16+1), P^(lane%32+1) */
-            float *l = pl + ((size_t)s * 64 + lane) * 12;
-            for (int i = 0; i < 4; i++) {
-                l[i] = (float)pw[lane][i]; l[4 + i] = (float)pw[lane % 16 + 1][i]; l[8 + i] = (float)pw[lane % 32 + 1][i];
-            }
-        }
-        double p1 = 1.0, p2 = 0.0, q1 = 0.0, q2 = 1.0;             /* y[k] from (y[-1], y[-2]) = (1,0) and (0,1) */
-        for (int k = 0; k < 16; k++) {
-            const double h1 = -a1 * p1 - a2 * p2, h2 = -a1 * q1 - a2 * q2;
-            ph[40 * s + 2 * k] = (float)h1; ph[40 * s + 2 * k + 1] = (float)h2;
-            p2 = p1; p1 = h1; q2 = q1; q1 = h2;
-        }
-        const double b0 = c5[5 * s];
-        ph[40 * s + 32] = 1.f;
-        ph[40 * s + 33] = (float)(c5[5 * s + 1] / b0);
-        ph[40 * s + 34] = (float)(c5[5 * s + 2] / b0);
-        ph[40 * s + 35] = (float)a1;
-        ph[40 * s + 36] = (float)a2;
-        ph[40 * s + 37] = (float)xfac[s];
-        ph[40 * s + 38] = (float)xfac[s + 1];
-    }
-    f->in_gain32 = (float)xfac[0];
-    f->d_pd32w = (float *)llzs_malloc(sizeof(float) * 16 * (size_t)S);
-    f->d_pl32w = (float *)llzs_malloc(sizeof(float) * 768 * (size_t)S);
-    f->d_ph32w = (float *)llzs_malloc(sizeof(float) * 40 * (size_t)S);
-    int rc = (f->d_pd32w && f->d_pl32w && f->d_ph32w) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pd32w, pd, sizeof(float) * 16 * (size_t)S);
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pl32w, pl, sizeof(float) * 768 * (size_t)S);
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_ph32w, ph, sizeof(float) * 40 * (size_t)S);
-    free(t);
+    llzs_iir_wave_tables *d = &f->wave[LLZS_IIR_WAVE32_F32];
+    const iirm_up_t up[3] = {{&d->pd, pd, sizeof(float) * 16 * S}, {&d->pl, pl, sizeof(float) * 768 * S},
+                             {&d->cf, ph, sizeof(float) * 40 * S}};
+    d->in_gain = xfac[0];
+    const int rc = iirm_upload(f, up, 3);
+    free(pd);
     return rc;
 }
 
-/* Tables of the double kernel with 32 samples per lane and the b0 gains folded out (k_iir_cascade_wave_pf64w), for the
- * cascades float32 arithmetic is not good enough for: cw [S][8] = b1/b0, b2/b0, a1, a2, xfac_s, xfac_(s+1), 0, 0 with
- * xfac_s = prod_{t >= s} b0_t; pd [S][16] = P^(2^d), d < 4, P = A^32; plc [S][448] = P^lane for 64 lanes, P^(i+1) for
- * i < 16, P^(i+1) for i < 32 (2 x 2, row major).  The b0.s must be usable as divisors (partial products 1e-150..1e150). */
+/* the same in double for the cascades float32 arithmetic is not good enough for (WAVE32_F64) */
 static int iirm_build_run32d(iirm_t *f, const double *c5)
 {
-    const int S = f->stages;
-    if (S > 8 || f->float32_ok) return LLZ_OK;
+    const size_t S = (size_t)f->stages;
     double xfac[9];
-    xfac[S] = 1.0;
-    for (int s = S - 1; s >= 0; s--) {
+    if (S > 8 || f->float32_ok || !iirm_fold(c5, (int)S, &IIRM_FOLD64, xfac)) return LLZ_OK;
+    double *cw = (double *)calloc(S * (8 + 16 + 448), sizeof(double));
+    if (!cw) return LLZ_ERR_NOMEM;
+    double *pd = cw + 8 * S, *pl = pd + 16 * S;
+    for (size_t s = 0; s < S; s++) {
         const double b0 = c5[5 * s];
-        xfac[s] = xfac[s + 1] * b0;
-        if (!(fabs(b0) > 1e-30) || !(fabs(xfac[s]) > 1e-150 && fabs(xfac[s]) < 1e150) ||
-            !(fabs(c5[5 * s + 1] / b0) < 1e6) || !(fabs(c5[5 * s + 2] / b0) < 1e6)) return LLZ_OK;
+        iirm_pow_t w;
+        iirm_powers(c5[5 * s + 3], c5[5 * s + 4], 32, &w);
+        const double c[6] = {c5[5 * s + 1] / b0, c5[5 * s + 2] / b0, c5[5 * s + 3], c5[5 * s + 4], xfac[s], xfac[s + 1]};
+        memcpy(cw + 8 * s, c, sizeof(c));
+        memcpy(pd + 16 * s, w.p2, sizeof(double) * 16);
+        memcpy(pl + 448 * s, &w.pw[0][0], sizeof(double) * 4 * 64);           /* P^lane */
+        memcpy(pl + 448 * s + 256, &w.pw[1][0], sizeof(double) * 4 * 16);     /* P^(i+1), i < 16 */
+        memcpy(pl + 448 * s + 320, &w.pw[1][0], sizeof(double) * 4 * 32);     /* P^(i+1), i < 32 */
     }
-    double *t = (double *)calloc((size_t)S * (8 + 16 + 448), sizeof(double));
-    if (!t) return LLZ_ERR_NOMEM;
-    double *cw = t, *pd = t + 8 * S, *pl = pd + 16 * S;
-    for (int s = 0; s < S; s++) {
-        const double b0 = c5[5 * s], a1 = c5[5 * s + 3], a2 = c5[5 * s + 4];
-        const double A[4] = {-a1, -a2, 1.0, 0.0};
-        double P[4] = {1.0, 0.0, 0.0, 1.0};
-        for (int i = 0; i < 32; i++) mat2_mul(A, P, P);
-        memcpy(pd + 16 * s, P, sizeof(P));
-        for (int d = 1; d < 4; d++) mat2_mul(pd + 16 * s + 4 * (d - 1), pd + 16 * s + 4 * (d - 1), pd + 16 * s + 4 * d);
-        double pw[65][4];
-        pw[0][0] = 1.0; pw[0][1] = 0.0; pw[0][2] = 0.0; pw[0][3] = 1.0;
-        for (int k = 1; k <= 64; k++) mat2_mul(P, pw[k - 1], pw[k]);
-        double *l = pl + (size_t)s * 448;
-        for (int lane = 0; lane < 64; lane++) memcpy(l + 4 * lane, pw[lane], sizeof(pw[0]));
-        for (int i = 0; i < 16; i++) memcpy(l + 256 + 4 * i, pw[i + 1], sizeof(pw[0]));
-        for (int i = 0; i < 32; i++) memcpy(l + 320 + 4 * i, pw[i + 1], sizeof(pw[0]));
-        cw[8 * s + 0] = c5[5 * s + 1] / b0; cw[8 * s + 1] = c5[5 * s + 2] / b0;
-        cw[8 * s + 2] = a1; cw[8 * s + 3] = a2;
-        cw[8 * s + 4] = xfac[s]; cw[8 * s + 5] = xfac[s + 1];
-    }
-    f->in_gain64 = xfac[0];
-    f->d_cw64 = (double *)llzs_malloc(sizeof(double) * 8 * (size_t)S);
-    f->d_pd64w = (double *)llzs_malloc(sizeof(double) * 16 * (size_t)S);
-    f->d_pl64w = (double *)llzs_malloc(sizeof(double) * 448 * (size_t)S);
-    int rc = (f->d_cw64 && f->d_pd64w && f->d_pl64w) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_cw64, cw, sizeof(double) * 8 * (size_t)S);
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pd64w, pd, sizeof(double) * 16 * (size_t)S);
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_pl64w, pl, sizeof(double) * 448 * (size_t)S);
-    free(t);
+    llzs_iir_wave_tables *d = &f->wave[LLZS_IIR_WAVE32_F64];
+    const iirm_up_t up[3] = {{&d->cf, cw, sizeof(double) * 8 * S}, {&d->pd, pd, sizeof(double) * 16 * S},
+                             {&d->pl, pl, sizeof(double) * 448 * S}};
+    d->in_gain = xfac[0];
+    const int rc = iirm_upload(f, up, 3);
+    free(cw);
     return rc;
 }
 
@@ -407,15 +389,16 @@ unsigned long llz_iir_cascade_mc_init(int channels, int stages, const double *co
             c5[5 * s + 0] = coef[6 * s + 0]; c5[5 * s + 1] = coef[6 * s + 1]; c5[5 * s + 2] = coef[6 * s + 2];
             c5[5 * s + 3] = coef[6 * s + 4]; c5[5 * s + 4] = coef[6 * s + 5];
         }
-        f->d_coef = (double *)llzs_malloc(sizeof(double) * 5 * (size_t)stages);
+        f->d_tab[f->ntab++] = llzs_malloc(sizeof(double) * 5 * (size_t)stages);
+        f->d_coef = (const double *)f->d_tab[0];
         f->d_state = (double *)llzs_malloc(st_bytes);
         f->d_state_alt = (double *)llzs_malloc(st_bytes);
         if (!f->d_coef || !f->d_state || !f->d_state_alt) rc = LLZ_ERR_NOMEM;
     }
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_coef, c5, sizeof(double) * 5 * (size_t)stages);
+    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_tab[0], c5, sizeof(double) * 5 * (size_t)stages);
     if (rc == LLZ_OK) rc = llzs_memset(f->d_state, 0, st_bytes, NULL);
     if (rc == LLZ_OK) f->float32_ok = iirm_float32_ok(c5, stages) && llzs_tune(LLZS_TUNE_IIR_F64) != 1;
-    if (rc == LLZ_OK) rc = iirm_build_powers(f, c5, 16);
+    if (rc == LLZ_OK) rc = iirm_build_run16(f, c5);
     if (rc == LLZ_OK && llzs_tune(LLZS_TUNE_IIR_UNPACKED) < 1) rc = iirm_build_run32(f, c5);
     if (rc == LLZ_OK && llzs_tune(LLZS_TUNE_IIR_UNPACKED) < 1) rc = iirm_build_run32d(f, c5);
     if (rc == LLZ_OK) f->warm_chunks = iirm_memory_chunks(c5, stages);
@@ -466,6 +449,38 @@ int llz_iir_cascade_mc(unsigned long handle, const float *x, float *y, int frame
     return rc;
 }
 
+/* Which kernel takes the frame's whole chunks (n_fast samples): the stage pipeline, or for short-memory cascades of up to 8
+ * sections a wave per (channel, time segment) with all sections in registers (float32, packed: 3.65 -> 2.3 ms on config 4;
+ * double: 4.76 -> 3.75 ms on the 0.99-radius set).  That needs enough (channel, segment) items to fill most of the chip with
+ * segments at least 8 x the warm-up long; measured crossover, tools/iir_xover.sh: 1024 items pipeline, 2048 items wave form.
+ * Of the wave forms the one in the cascade's precision with 32 samples per lane (b0 folded out) where it was built and the
+ * frame holds a 2048-sample chunk, else the one with 16. */
+static int iirm_path(const iirm_t *f, int n_fast)
+{
+    const long seg_items = f->warm_chunks > 0 ? (long)f->channels * (n_fast / LLZS_IIR_PIPE_CHUNK / (8 * f->warm_chunks)) : 0;
+    const int min_items = llzs_tune(LLZS_TUNE_IIR_WAVE_MIN_ITEMS) >= 0 ? llzs_tune(LLZS_TUNE_IIR_WAVE_MIN_ITEMS) : 2048;
+    const int w16 = f->float32_ok ? LLZS_IIR_WAVE16_F32 : LLZS_IIR_WAVE16_F64;
+    const int w32 = f->float32_ok ? LLZS_IIR_WAVE32_F32 : LLZS_IIR_WAVE32_F64;
+    if (f->stages > 8 || seg_items < min_items || llzs_tune(LLZS_TUNE_IIR_PIPE) == 1 || !f->wave[w16].pl) return IIRM_PIPE;
+    return (f->wave[w32].pl && n_fast >= LLZS_IIR_WAVE_CHUNK(w32)) ? w32 : w16;
+}
+
+/* every launch reads d_state and writes d_state_alt (segments of one launch are not ordered), which then swap */
+static int iirm_launch(iirm_t *f, int path, const float *d_in, float *d_out, int n, int pitch)
+{
+    const llzs_iir_wave_tables *pipe = &f->wave[LLZS_IIR_WAVE16_F64];
+    const int rc = path == IIRM_PIPE
+        ? llzs_iir_cascade_pipe_f32(d_in, d_out, f->d_coef, (const double *)pipe->pd, (const double *)pipe->pl, f->d_state,
+                                    f->d_state_alt, f->channels, n, pitch, pitch, f->stages, f->warm_chunks, f->float32_ok,
+                                    f->stream)
+        : llzs_iir_cascade_wave(path, &f->wave[path], d_in, d_out, f->d_state, f->d_state_alt, f->channels, n, pitch, pitch,
+                                f->stages, f->warm_chunks, f->stream);
+    if (rc == LLZ_OK) {
+        double *t = f->d_state; f->d_state = f->d_state_alt; f->d_state_alt = t;
+    }
+    return rc;
+}
+
 static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len)
 {
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
@@ -483,60 +498,18 @@ static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len)
         d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
         if (!d_out) return LLZ_ERR_NOMEM;
     }
-    /* whole 1024-sample chunks go through the pipelined kernel (needs 16-byte aligned rows), the ragged remainder
-     * through the one-lane-per-channel kernel; both read and write the same per-section state */
+    /* whole 1024-sample chunks go through the path's kernel (needs 16-byte aligned rows): with a 32-sample form the whole
+     * 2048-sample chunks, then its 16-sample counterpart what is left; the ragged remainder through the one-lane-per-channel
+     * kernel.  All read and write the same per-section state. */
     const int aligned = (frame_len % 4 == 0) && (((size_t)d_in | (size_t)d_out) % 16 == 0);
-    const int chunk = LLZS_IIR_PIPE_CHUNK;
-    const int n_fast = aligned ? frame_len - frame_len % chunk : 0;
-    /* short-memory cascades of up to 8 sections: a wave per (channel, time segment), all sections in registers (float32,
-     * packed: 3.65 -> 2.3 ms on config 4; double: 4.76 -> 3.75 ms on the 0.99-radius set) */
-    /* (needs enough (channel, segment) items to fill most of the chip, segments at least 8 x the warm-up long; measured
-     * crossover against the stage pipeline, tools/iir_xover.sh: 1024 items pipeline, 2048 items wave form) */
-    const long seg_items = f->warm_chunks > 0 ? (long)f->channels * (n_fast / LLZS_IIR_PIPE_CHUNK / (8 * f->warm_chunks)) : 0;
-    const int min_items = llzs_tune(LLZS_TUNE_IIR_WAVE_MIN_ITEMS) >= 0 ? llzs_tune(LLZS_TUNE_IIR_WAVE_MIN_ITEMS) : 2048;
-    const int wave_form = f->stages <= 8 && seg_items >= min_items && llzs_tune(LLZS_TUNE_IIR_PIPE) != 1 &&
-                          (!f->float32_ok || f->d_pl32);
-    /* packed float32 form (or, for cascades that need it, the double form) with 32 samples per lane on the whole
-     * 2048-sample chunks, the 16-sample forms on what is left of
-     * the 1024-sample chunks; every launch reads d_state and writes d_state_alt, which then swap */
-    int done = 0;
-    if (rc == LLZ_OK && wave_form && f->float32_ok && f->d_ph32w && n_fast >= 2048) {
-        const int n32 = n_fast - n_fast % 2048;
-        rc = llzs_iir_cascade_wave32_f32(d_in, d_out, f->d_pd32w, f->d_pl32w, f->d_ph32w, f->d_state, f->d_state_alt,
-                                         f->channels, n32, frame_len, frame_len, f->stages, f->warm_chunks, f->in_gain32,
-                                         f->stream);
-        if (rc == LLZ_OK) {
-            double *t = f->d_state; f->d_state = f->d_state_alt; f->d_state_alt = t;
-            done = n32;
-        }
+    const int n_fast = aligned ? frame_len - frame_len % LLZS_IIR_PIPE_CHUNK : 0;
+    int path = iirm_path(f, n_fast), done = 0;
+    if (rc == LLZ_OK && path >= LLZS_IIR_WAVE32_F32) {
+        done = n_fast - n_fast % LLZS_IIR_WAVE_CHUNK(path);
+        rc = iirm_launch(f, path, d_in, d_out, done, frame_len);
+        path = path == LLZS_IIR_WAVE32_F32 ? LLZS_IIR_WAVE16_F32 : LLZS_IIR_WAVE16_F64;
     }
-    if (rc == LLZ_OK && wave_form && !f->float32_ok && f->d_cw64 && n_fast >= 2048) {
-        const int n32 = n_fast - n_fast % 2048;
-        rc = llzs_iir_cascade_wave32_f64(d_in, d_out, f->d_cw64, f->d_pd64w, f->d_pl64w, f->d_state, f->d_state_alt,
-                                         f->channels, n32, frame_len, frame_len, f->stages, f->warm_chunks, f->in_gain64,
-                                         f->stream);
-        if (rc == LLZ_OK) {
-            double *t = f->d_state; f->d_state = f->d_state_alt; f->d_state_alt = t;
-            done = n32;
-        }
-    }
-    const int n16 = n_fast - done;
-    if (rc == LLZ_OK && n16 > 0) {
-        if (wave_form && f->float32_ok)
-            rc = llzs_iir_cascade_wave_f32(d_in + done, d_out + done, f->d_coef32, f->d_pd32, f->d_pl32, f->d_ph32, f->d_state,
-                                           f->d_state_alt, f->channels, n16, frame_len, frame_len, f->stages, f->warm_chunks,
-                                           f->stream);
-        else if (wave_form)
-            rc = llzs_iir_cascade_wave_f64(d_in + done, d_out + done, f->d_coef, f->d_pd, f->d_pl, f->d_state, f->d_state_alt,
-                                           f->channels, n16, frame_len, frame_len, f->stages, f->warm_chunks, f->stream);
-        else
-            rc = llzs_iir_cascade_pipe_f32(d_in + done, d_out + done, f->d_coef, f->d_pd, f->d_pl, f->d_state, f->d_state_alt,
-                                           f->channels, n16, frame_len, frame_len, f->stages, f->warm_chunks, f->float32_ok,
-                                           f->stream);
-        if (rc == LLZ_OK) {
-            double *t = f->d_state; f->d_state = f->d_state_alt; f->d_state_alt = t;
-        }
-    }
+    if (rc == LLZ_OK && n_fast > done) rc = iirm_launch(f, path, d_in + done, d_out + done, n_fast - done, frame_len);
     if (rc == LLZ_OK && n_fast < frame_len)
         rc = llzs_iir_cascade_f32(d_in + n_fast, d_out + n_fast, f->d_coef, f->d_state, f->channels,
                                   frame_len - n_fast, frame_len, frame_len, f->stages, f->stream);

@@ -1141,6 +1141,47 @@ extern "C" int llzs_iir_cascade_f32(const float *in, float *out, const double *c
     return LLZ_OK;
 }
 
+// ---- time segments: one plan for the stage pipeline and every wave form ----
+
+// A channel may be split along time into (channel, segment) items; a later segment starts `warm` chunks early from the
+// zero state (the host measured how long the cascade remembers: warm_chunks, in chunks of 1024 samples whatever the form).
+constexpr int IIR_LONG_SEGMENT = 65536;     // samples: from here on the per-item cost of warm-up and table load (~1.4 K
+                                            // samples) stays small and the hardware balances several rounds of items
+struct iir_plan {
+    int segs, seg_chunks;       // segments per channel, chunks per segment (the last one may be shorter)
+    int warm;                   // the warm-up in chunks of the form's own size: what the kernel gets
+};
+
+// The wave forms' first choice.  `slots` = waves the chip holds of the kernel.  Measured on config 4 (1024 channels) and on
+// 128 channels: about three rounds of items are best while a segment stays long, otherwise exactly one round.
+static int iir_wave_first_segs(int chunk, int channels, int nchunks, long slots)
+{
+    int segs = 1;
+    for (int rounds = 3; rounds >= 1; rounds--) {
+        segs = (int)((rounds * slots + channels / 2) / channels);
+        if (segs < 1) segs = 1;
+        if (segs > 64) segs = 64;
+        if (rounds == 1 || nchunks / segs >= IIR_LONG_SEGMENT / chunk) break;
+    }
+    return segs;
+}
+
+// From a form's first choice to the launch, on the host alone: `tune` is the iir_segs override (-1: none).
+static iir_plan iir_plan_of(int chunk, int nchunks, int warm_chunks, int segs, int tune)
+{
+    iir_plan p;
+    p.warm = (warm_chunks * 1024 + chunk - 1) / chunk;
+    while (segs > 1 && nchunks / segs < 8 * p.warm) segs--;             // segments at least 8 x the warm-up
+    if (tune >= 1 && tune <= 64 && (tune == 1 || warm_chunks > 0)) segs = tune;
+    // A forced count too: a segment must hold its own warm-up, or its first chunk would lie in front of the row.  This
+    // compares chunks of the form's size with warm_chunks, which counts 1024 samples: with 2048-sample chunks it asks for
+    // twice the room p.warm needs.  Kept as it has always run (the tested and measured segment counts depend on it).
+    while (segs > 1 && nchunks / segs < warm_chunks) segs--;
+    p.seg_chunks = (nchunks + segs - 1) / segs;
+    p.segs = (nchunks + p.seg_chunks - 1) / p.seg_chunks;
+    return p;
+}
+
 // pd: [stages][6][4] = P^(2^d) row major, P = A^16; pl: [stages][64][12] = P^lane, P^(lane%16+1), P^(lane%32+1).  n must be a multiple of 1024 and
 // the rows 16-byte aligned (pitches % 4 == 0); the caller runs the remainder through llzs_iir_cascade_f32.
 extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const double *coef, const double *pd,
@@ -1167,20 +1208,16 @@ extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const doub
             LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_iir_cascade_pipe<double, 16>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    // time segments: only when the channels alone leave most of the chip idle (fewer than two workgroups per CU) and the
-    // warm-up stays a small part of a segment.  warm_chunks counts 1024-sample chunks.
+    // time segments: only when the channels alone leave most of the chip idle (fewer than two workgroups per CU); the rest
+    // is the one plan
     const int nchunks = n / chunk;
-    const int warm = (warm_chunks * 1024 + chunk - 1) / chunk;
-    int segs = 1;
+    int first = 1;
     if (warm_chunks > 0 && channels < 512) {
-        segs = (512 + channels - 1) / channels;
-        if (segs > 16) segs = 16;
-        while (segs > 1 && nchunks / segs < 8 * warm) segs--;
+        first = (512 + channels - 1) / channels;
+        if (first > 16) first = 16;
     }
-    if (const int v = llzs_tune(LLZS_TUNE_IIR_SEGS); v >= 1 && v <= 64 && (v == 1 || warm_chunks > 0)) segs = v;
-    while (segs > 1 && nchunks / segs < warm_chunks) segs--;        // (a forced count too must leave room for the warm-up)
-    const int seg_chunks = (nchunks + segs - 1) / segs;
-    segs = (nchunks + seg_chunks - 1) / seg_chunks;
+    const iir_plan p = iir_plan_of(chunk, nchunks, warm_chunks, first, llzs_tune(LLZS_TUNE_IIR_SEGS));
+    const int segs = p.segs, seg_chunks = p.seg_chunks, warm = p.warm;
     if (float32)
         hipLaunchKernelGGL((k_iir_cascade_pipe<float, 16>), dim3((unsigned)((long)channels * segs)), dim3(64 * stages), lds,
                            as_stream(stream), in, out, coef, pd, pl, state_in, state, nchunks, in_pitch, out_pitch, stages, segs,
@@ -1193,243 +1230,97 @@ extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const doub
     return LLZ_OK;
 }
 
-// wave-autonomous form (see k_iir_cascade_wave).  n a multiple of 1024, rows 16-byte aligned, warm_chunks > 0.
-template <typename R>
-static int launch_iir_wave(const float *in, float *out, const R *coef, const R *pd, const R *pl, const float *ph32,
-                           const double *state_in, double *state, int channels, int n, long in_pitch, long out_pitch,
-                           int stages, int warm_chunks, int pd_stride, void *stream)
+// ---- the wave-autonomous forms: one row each, one argument check, one slot query, one launch ----
+
+#define IIR_WAVE_INSTANCES(K)                                                                                          \
+    {(const void *)K<1>, (const void *)K<2>, (const void *)K<3>, (const void *)K<4>, (const void *)K<5>,              \
+     (const void *)K<6>, (const void *)K<7>, (const void *)K<8>}
+
+// One wave kernel: a wave owns a (channel, time segment) item and runs all of its 1..8 sections in registers (16 would
+// spill), four items per workgroup.  Parameters: in, out, three tables, state_in, state, nchunks, the pitches, the plan,
+// items and, where the b0 gains are folded out, their product.
+struct iir_wave_row {
+    const char *name;
+    const void *kernel[8];      // the instance for 1..8 sections
+    int run;                    // samples per lane: a chunk is 64 * run samples
+    unsigned lds;               // dynamic LDS bytes
+    bool cf_first;              // the tables' parameter order: (cf, pd, pl), else (pd, pl, cf)
+    int gain_bytes;             // the input gain is the last parameter, as a float (4) or a double (8); 0: none
+};
+static const iir_wave_row IIR_WAVE_ROWS[LLZS_IIR_WAVE_FORMS] = {        // by LLZS_IIR_WAVE16_F32 .. LLZS_IIR_WAVE32_F64
+    {"k_iir_cascade_wave_pk", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk), 16, 0, false, 0},
+    {"k_iir_cascade_wave_pf64", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pf64), 16, 4 * 1280 * sizeof(float), true, 0},
+    {"k_iir_cascade_wave_pk32", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk32), 32, 0, false, 4},
+    {"k_iir_cascade_wave_pf64w", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pf64w), 32, 0, true, 8},
+};
+#undef IIR_WAVE_INSTANCES
+
+// waves of a kernel the chip holds (queried once per kernel and process: same answer on every device of a node)
+static long iir_wave_slots(int form, int stages)
 {
-    if (!in || !out || !coef || !pd || !pl || !state || !state_in || state == state_in || channels <= 0 || n <= 0 || (n % 1024) || stages < 1 ||
-        stages > 8 /* 16 sections in registers spill */ || warm_chunks < 1 || in_pitch < n || out_pitch < n || (in_pitch & 3) || (out_pitch & 3) ||
-        (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) {
-        llzs_set_error("iir_cascade_wave: bad arguments");
-        return LLZ_ERR_ARG;
-    }
-    const int nchunks = n / 1024;
-    // Time segments per channel.  `slots` = waves the chip holds of this kernel.  Measured on config 4 (1024 channels) and
-    // on 128 channels: about three rounds of items are best while a segment stays long (>= 64 chunks: the per-item cost
-    // of warm-up and table load, ~1.4 chunks, stays small and the hardware balances the rounds), otherwise exactly one
-    // round; segments at least 8 x the warm-up.
-    // the one-section-ahead kernels: packed float32 (needs the h table) or double
-    if (std::is_same<R, float>::value && ph32 == nullptr) {
-        llzs_set_error("iir_cascade_wave: the float32 form needs its h table");
-        return LLZ_ERR_ARG;
-    }
-    const void *kfn = nullptr;
-    if constexpr (std::is_same<R, float>::value) {
-        static const void *const tab[8] = {
-            (const void *)k_iir_cascade_wave_pk<1>, (const void *)k_iir_cascade_wave_pk<2>, (const void *)k_iir_cascade_wave_pk<3>,
-            (const void *)k_iir_cascade_wave_pk<4>, (const void *)k_iir_cascade_wave_pk<5>, (const void *)k_iir_cascade_wave_pk<6>,
-            (const void *)k_iir_cascade_wave_pk<7>, (const void *)k_iir_cascade_wave_pk<8>};
-        kfn = tab[stages - 1];
-    } else {
-        static const void *const tab[8] = {
-            (const void *)k_iir_cascade_wave_pf64<1>, (const void *)k_iir_cascade_wave_pf64<2>, (const void *)k_iir_cascade_wave_pf64<3>,
-            (const void *)k_iir_cascade_wave_pf64<4>, (const void *)k_iir_cascade_wave_pf64<5>, (const void *)k_iir_cascade_wave_pf64<6>,
-            (const void *)k_iir_cascade_wave_pf64<7>, (const void *)k_iir_cascade_wave_pf64<8>};
-        kfn = tab[stages - 1];
-    }
-    // (queried once per kernel and process: same answer on every device of a node)
-    static struct { const void *fn; long slots; } seen[24];
-    static int nseen = 0;
+    static long seen[LLZS_IIR_WAVE_FORMS][8];
     static std::mutex seen_lock;
-    long slots = 0;
     std::lock_guard<std::mutex> guard(seen_lock);
-    for (int i = 0; i < nseen; i++)
-        if (seen[i].fn == kfn) slots = seen[i].slots;
+    long &slots = seen[form][stages - 1];
     if (!slots) {
-        int blocks_per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kfn, 256, 0) != hipSuccess || blocks_per_cu < 1) {
+        int blocks_per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, IIR_WAVE_ROWS[form].kernel[stages - 1], 256, 0) !=
+                hipSuccess || blocks_per_cu < 1) {
             (void)hipGetLastError();
             blocks_per_cu = 2;
         }
-        int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
             (void)hipGetLastError();
             cus = 256;
         }
         slots = 4L * blocks_per_cu * cus;
-        if (nseen < 24) { seen[nseen].slots = slots; seen[nseen].fn = kfn; nseen++; }
     }
-    int segs = 1;
-    for (int rounds = 3; rounds >= 1; rounds--) {
-        segs = (int)((rounds * slots + channels / 2) / channels);
-        if (segs < 1) segs = 1;
-        if (segs > 64) segs = 64;
-        if (rounds == 1 || nchunks / segs >= 64) break;
-    }
-    while (segs > 1 && nchunks / segs < 8 * warm_chunks) segs--;
-    if (const int v = llzs_tune(LLZS_TUNE_IIR_SEGS); v >= 1 && v <= 64) segs = v;
-    while (segs > 1 && nchunks / segs < warm_chunks) segs--;        // (a forced count too: a segment must hold its own warm-up,
-                                                                    //  or its first chunk would lie in front of the row)
-    const int seg_chunks = (nchunks + segs - 1) / segs;
-    segs = (nchunks + seg_chunks - 1) / seg_chunks;
-    const long items = (long)channels * segs;
-    const dim3 grid((unsigned)((items + 3) / 4));
-    {
-        if constexpr (std::is_same<R, float>::value) {
-#define LLZ_AHEAD_LAUNCH(S)                                                                                          \
-    hipLaunchKernelGGL((k_iir_cascade_wave_pk<S>), grid, dim3(256), 0, as_stream(stream), in, out, pd, pl, ph32, state_in, state, \
-                       nchunks, in_pitch, out_pitch, segs, seg_chunks, warm_chunks, items)
-            switch (stages) {
-            case 1: LLZ_AHEAD_LAUNCH(1); break; case 2: LLZ_AHEAD_LAUNCH(2); break; case 3: LLZ_AHEAD_LAUNCH(3); break;
-            case 4: LLZ_AHEAD_LAUNCH(4); break; case 5: LLZ_AHEAD_LAUNCH(5); break; case 6: LLZ_AHEAD_LAUNCH(6); break;
-            case 7: LLZ_AHEAD_LAUNCH(7); break; default: LLZ_AHEAD_LAUNCH(8); break;
-            }
-#undef LLZ_AHEAD_LAUNCH
-        } else {
-#define LLZ_AHEAD_LAUNCH(S)                                                                                          \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_iir_cascade_wave_pf64<S>),                            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 1280 * (int)sizeof(float));            \
-    hipLaunchKernelGGL((k_iir_cascade_wave_pf64<S>), grid, dim3(256), 4 * 1280 * sizeof(float), as_stream(stream), in, \
-                       out, coef, pd, pl, state_in, state, nchunks, in_pitch, out_pitch, segs, seg_chunks, warm_chunks, items)
-            switch (stages) {
-            case 1: LLZ_AHEAD_LAUNCH(1); break; case 2: LLZ_AHEAD_LAUNCH(2); break; case 3: LLZ_AHEAD_LAUNCH(3); break;
-            case 4: LLZ_AHEAD_LAUNCH(4); break; case 5: LLZ_AHEAD_LAUNCH(5); break; case 6: LLZ_AHEAD_LAUNCH(6); break;
-            case 7: LLZ_AHEAD_LAUNCH(7); break; default: LLZ_AHEAD_LAUNCH(8); break;
-            }
-#undef LLZ_AHEAD_LAUNCH
-        }
-        LLZ_LAUNCH_CHECK("k_iir_cascade_wave (one section ahead)");
-        return LLZ_OK;
-    }
+    return slots;
 }
 
-extern "C" int llzs_iir_cascade_wave_f32(const float *in, float *out, const float *coef32, const float *pd32,
-                                         const float *pl32, const float *ph32 /* NULL: unpacked kernel */,
-                                         const double *state_in, double *state, int channels, int n, long in_pitch,
-                                         long out_pitch, int stages, int warm_chunks, void *stream)
+static int iir_wave_check(int form, const llzs_iir_wave_tables *t, const float *in, float *out, const double *state_in,
+                          double *state, int channels, int n, long in_pitch, long out_pitch, int stages, int warm_chunks)
 {
-    return launch_iir_wave<float>(in, out, coef32, pd32, pl32, ph32, state_in, state, channels, n, in_pitch, out_pitch, stages,
-                                  warm_chunks, 16, stream);
-}
-
-// the same in double, from the pipelined kernel's own tables (pd: [S][6][4])
-extern "C" int llzs_iir_cascade_wave_f64(const float *in, float *out, const double *coef, const double *pd,
-                                         const double *pl, const double *state_in, double *state, int channels, int n,
-                                         long in_pitch, long out_pitch, int stages, int warm_chunks, void *stream)
-{
-    return launch_iir_wave<double>(in, out, coef, pd, pl, nullptr, state_in, state, channels, n, in_pitch, out_pitch, stages, warm_chunks,
-                                   24, stream);
-}
-
-// 32 samples per lane, b0 folded out (k_iir_cascade_wave_pk32): n a multiple of 2048, rows 16-byte aligned, 1..8 sections,
-// warm_chunks in units of 1024 samples as everywhere; tables for P = A^32: pd32 [S][16], pl32 [S][64][12], ph32 [S][40];
-// in_gain = the product of the b0's
-extern "C" int llzs_iir_cascade_wave32_f32(const float *in, float *out, const float *pd32, const float *pl32,
-                                           const float *ph32, const double *state_in, double *state, int channels, int n,
-                                           long in_pitch, long out_pitch, int stages, int warm_chunks, float in_gain,
-                                           void *stream)
-{
-    if (!in || !out || !pd32 || !pl32 || !ph32 || !state || !state_in || state == state_in || channels <= 0 || n <= 0 ||
-        (n % 2048) || stages < 1 || stages > 8 || warm_chunks < 1 || in_pitch < n || out_pitch < n || (in_pitch & 3) ||
-        (out_pitch & 3) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) {
-        llzs_set_error("iir_cascade_wave32_f32: bad arguments");
+    if (form < 0 || form >= LLZS_IIR_WAVE_FORMS) {
+        llzs_set_error("iir_cascade_wave: no form %d", form);
         return LLZ_ERR_ARG;
     }
-    static const void *const tab[8] = {
-        (const void *)k_iir_cascade_wave_pk32<1>, (const void *)k_iir_cascade_wave_pk32<2>, (const void *)k_iir_cascade_wave_pk32<3>,
-        (const void *)k_iir_cascade_wave_pk32<4>, (const void *)k_iir_cascade_wave_pk32<5>, (const void *)k_iir_cascade_wave_pk32<6>,
-        (const void *)k_iir_cascade_wave_pk32<7>, (const void *)k_iir_cascade_wave_pk32<8>};
-    const void *kfn = tab[stages - 1];
-    int blocks_per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kfn, 256, 0) != hipSuccess || blocks_per_cu < 1) {
-        (void)hipGetLastError();
-        blocks_per_cu = 2;
+    const char *name = IIR_WAVE_ROWS[form].name;
+    const int chunk = 64 * IIR_WAVE_ROWS[form].run;
+    if (!in || !out || !t || !t->cf || !t->pd || !t->pl || !state || !state_in || state == state_in || channels <= 0 || n <= 0 ||
+        (n % chunk) || stages < 1 || stages > 8 || warm_chunks < 1 || in_pitch < n || out_pitch < n || (in_pitch & 3) ||
+        (out_pitch & 3) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) {
+        llzs_set_error("%s: bad arguments (channels=%d, n=%d in chunks of %d, stages=%d of 1..8, warm_chunks=%d of at least 1, "
+                       "rows at %p / %p with pitches %ld / %ld 16-byte aligned, three tables, state read %p and written %p)",
+                       name, channels, n, chunk, stages, warm_chunks, (const void *)in, (void *)out, in_pitch, out_pitch,
+                       (const void *)state_in, (void *)state);
+        return LLZ_ERR_ARG;
     }
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    const long slots = 4L * blocks_per_cu * cus;
-    const int nchunks = n / 2048, warm = (warm_chunks + 1) / 2;
-    // time segments per channel as for the 16-sample kernels: about three rounds of (channel, segment) items while a
-    // segment stays long (>= 32 chunks of 2048), else one round; segments at least 8 x the warm-up
-    int segs = 1;
-    for (int rounds = 3; rounds >= 1; rounds--) {
-        segs = (int)((rounds * slots + channels / 2) / channels);
-        if (segs < 1) segs = 1;
-        if (segs > 64) segs = 64;
-        if (rounds == 1 || nchunks / segs >= 32) break;
-    }
-    while (segs > 1 && nchunks / segs < 8 * warm) segs--;
-    if (const int v = llzs_tune(LLZS_TUNE_IIR_SEGS); v >= 1 && v <= 64) segs = v;
-    while (segs > 1 && nchunks / segs < warm_chunks) segs--;        // (a forced count too: a segment must hold its own warm-up,
-                                                                    //  or its first chunk would lie in front of the row)
-    const int seg_chunks = (nchunks + segs - 1) / segs;
-    segs = (nchunks + seg_chunks - 1) / seg_chunks;
-    const long items = (long)channels * segs;
-    const dim3 grid((unsigned)((items + 3) / 4));
-#define LLZ_PK32_LAUNCH(S)                                                                                           \
-    hipLaunchKernelGGL((k_iir_cascade_wave_pk32<S>), grid, dim3(256), 0, as_stream(stream), in, out, pd32, pl32, ph32,  \
-                       state_in, state, nchunks, in_pitch, out_pitch, segs, seg_chunks, warm, items, in_gain)
-    switch (stages) {
-    case 1: LLZ_PK32_LAUNCH(1); break; case 2: LLZ_PK32_LAUNCH(2); break; case 3: LLZ_PK32_LAUNCH(3); break;
-    case 4: LLZ_PK32_LAUNCH(4); break; case 5: LLZ_PK32_LAUNCH(5); break; case 6: LLZ_PK32_LAUNCH(6); break;
-    case 7: LLZ_PK32_LAUNCH(7); break; default: LLZ_PK32_LAUNCH(8); break;
-    }
-#undef LLZ_PK32_LAUNCH
-    LLZ_LAUNCH_CHECK("k_iir_cascade_wave_pk32");
     return LLZ_OK;
 }
 
-// the double cascade with 32 samples per lane and b0 folded out (k_iir_cascade_wave_pf64w): n a multiple of 2048, rows
-// 16-byte aligned, 1..8 sections; cw [S][8], pd [S][16], plc [S][448] as described at the kernel; in_gain = the product of
-// the b0's
-extern "C" int llzs_iir_cascade_wave32_f64(const float *in, float *out, const double *cw, const double *pd,
-                                           const double *plc, const double *state_in, double *state, int channels, int n,
-                                           long in_pitch, long out_pitch, int stages, int warm_chunks, double in_gain,
-                                           void *stream)
+extern "C" int llzs_iir_cascade_wave(int form, const llzs_iir_wave_tables *t, const float *in, float *out,
+                                     const double *state_in, double *state, int channels, int n, long in_pitch,
+                                     long out_pitch, int stages, int warm_chunks, void *stream)
 {
-    if (!in || !out || !cw || !pd || !plc || !state || !state_in || state == state_in || channels <= 0 || n <= 0 ||
-        (n % 2048) || stages < 1 || stages > 8 || warm_chunks < 1 || in_pitch < n || out_pitch < n || (in_pitch & 3) ||
-        (out_pitch & 3) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) {
-        llzs_set_error("iir_cascade_wave32_f64: bad arguments");
-        return LLZ_ERR_ARG;
-    }
-    static const void *const tab[8] = {
-        (const void *)k_iir_cascade_wave_pf64w<1>, (const void *)k_iir_cascade_wave_pf64w<2>, (const void *)k_iir_cascade_wave_pf64w<3>,
-        (const void *)k_iir_cascade_wave_pf64w<4>, (const void *)k_iir_cascade_wave_pf64w<5>, (const void *)k_iir_cascade_wave_pf64w<6>,
-        (const void *)k_iir_cascade_wave_pf64w<7>, (const void *)k_iir_cascade_wave_pf64w<8>};
-    const void *kfn = tab[stages - 1];
-    int blocks_per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kfn, 256, 0) != hipSuccess || blocks_per_cu < 1) {
-        (void)hipGetLastError();
-        blocks_per_cu = 2;
-    }
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    const long slots = 4L * blocks_per_cu * cus;
-    const int nchunks = n / 2048, warm = (warm_chunks + 1) / 2;
-    int segs = 1;
-    for (int rounds = 3; rounds >= 1; rounds--) {
-        segs = (int)((rounds * slots + channels / 2) / channels);
-        if (segs < 1) segs = 1;
-        if (segs > 64) segs = 64;
-        if (rounds == 1 || nchunks / segs >= 32) break;
-    }
-    while (segs > 1 && nchunks / segs < 8 * warm) segs--;
-    if (const int v = llzs_tune(LLZS_TUNE_IIR_SEGS); v >= 1 && v <= 64) segs = v;
-    while (segs > 1 && nchunks / segs < warm_chunks) segs--;        // (a forced count too: a segment must hold its own warm-up,
-                                                                    //  or its first chunk would lie in front of the row)
-    const int seg_chunks = (nchunks + segs - 1) / segs;
-    segs = (nchunks + seg_chunks - 1) / seg_chunks;
-    const long items = (long)channels * segs;
-    const dim3 grid((unsigned)((items + 3) / 4));
-#define LLZ_PFW_LAUNCH(S)                                                                                            \
-    hipLaunchKernelGGL((k_iir_cascade_wave_pf64w<S>), grid, dim3(256), 0, as_stream(stream), in, out, cw, pd, plc,      \
-                       state_in, state, nchunks, in_pitch, out_pitch, segs, seg_chunks, warm, items, in_gain)
-    switch (stages) {
-    case 1: LLZ_PFW_LAUNCH(1); break; case 2: LLZ_PFW_LAUNCH(2); break; case 3: LLZ_PFW_LAUNCH(3); break;
-    case 4: LLZ_PFW_LAUNCH(4); break; case 5: LLZ_PFW_LAUNCH(5); break; case 6: LLZ_PFW_LAUNCH(6); break;
-    case 7: LLZ_PFW_LAUNCH(7); break; default: LLZ_PFW_LAUNCH(8); break;
-    }
-#undef LLZ_PFW_LAUNCH
-    LLZ_LAUNCH_CHECK("k_iir_cascade_wave_pf64w");
+    if (const int rc = iir_wave_check(form, t, in, out, state_in, state, channels, n, in_pitch, out_pitch, stages, warm_chunks))
+        return rc;
+    const iir_wave_row &row = IIR_WAVE_ROWS[form];
+    const void *kernel = row.kernel[stages - 1];
+    const int chunk = 64 * row.run;
+    int nchunks = n / chunk;
+    iir_plan p = iir_plan_of(chunk, nchunks, warm_chunks,
+                             iir_wave_first_segs(chunk, channels, nchunks, iir_wave_slots(form, stages)),
+                             llzs_tune(LLZS_TUNE_IIR_SEGS));
+    long items = (long)channels * p.segs;
+    const void *t0 = row.cf_first ? t->cf : t->pd, *t1 = row.cf_first ? t->pd : t->pl, *t2 = row.cf_first ? t->pl : t->cf;
+    float gain32 = (float)t->in_gain;
+    double gain64 = t->in_gain;
+    void *args[15] = {&in, &out, &t0, &t1, &t2, &state_in, &state, &nchunks, &in_pitch, &out_pitch, &p.segs, &p.seg_chunks,
+                      &p.warm, &items, row.gain_bytes == 4 ? (void *)&gain32 : (void *)&gain64};
+    if (row.lds) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)row.lds);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), args, row.lds, as_stream(stream));
+    LLZ_LAUNCH_CHECK(row.name);
     return LLZ_OK;
 }

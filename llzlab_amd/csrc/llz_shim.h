@@ -147,30 +147,29 @@ int llzs_iir_cascade_pipe_f32(const float *in, float *out, const double *coef, c
                               int warm_chunks /* 0: never split a channel along time */,
                               int float32 /* 1: float32 arithmetic (every section passed the host's noise-gain check) */,
                               void *stream);
+/* cascades of up to 8 sections with a short memory: a wave owns a (channel, time segment) and runs all sections in
+ * registers (iir.hip: one row of IIR_WAVE_ROWS per form).  n a multiple of the form's chunk, 16-byte aligned rows,
+ * warm_chunks >= 1 in units of 1024 samples whatever the form; state as above, read and written in different buffers.
+ * Tables (powers of P = A^16 or A^32, A = [[-a1,-a2],[1,0]]; the 32-sample forms fold the b0 gains out: b' = b / b0,
+ * xfac_s = prod_{t >= s} b0_t, yfac_s = xfac_(s+1), in_gain = xfac_0):
+ *   WAVE16_F32  k_iir_cascade_wave_pk    floats: cf [S][24] = (h1[k], h2[k]) k < 8, the outputs at k of the unit start states,
+ *                                        then b0 b1 b2 a1 a2 and 3 pad; pd [S][16] = P^(2^d) d < 4; pl [S][64][12]
+ *   WAVE16_F64  k_iir_cascade_wave_pf64  the stage pipeline's own tables: cf = coef [S][5], pd [S][6][4], pl [S][64][12]
+ *   WAVE32_F32  k_iir_cascade_wave_pk32  floats: cf [S][40] = (h1[k], h2[k]) k < 16, then 1 b1' b2' a1 a2 xfac yfac pad; pd, pl
+ *                                        as for WAVE16_F32
+ *   WAVE32_F64  k_iir_cascade_wave_pf64w doubles: cf [S][8] = b1', b2', a1, a2, xfac, yfac, 0, 0; pd [S][16]; pl [S][448] =
+ *                                        P^lane for 64 lanes, P^(i+1) i < 16, P^(i+1) i < 32 */
+enum { LLZS_IIR_WAVE16_F32, LLZS_IIR_WAVE16_F64, LLZS_IIR_WAVE32_F32, LLZS_IIR_WAVE32_F64, LLZS_IIR_WAVE_FORMS };
+#define LLZS_IIR_WAVE_CHUNK(form) ((form) >= LLZS_IIR_WAVE32_F32 ? 2048 : 1024)
+typedef struct {
+    const void *cf, *pd, *pl;
+    double in_gain;             /* the 32-sample forms scale the input once */
+} llzs_iir_wave_tables;
+int llzs_iir_cascade_wave(int form, const llzs_iir_wave_tables *t, const float *in, float *out, const double *state_in,
+                          double *state_out, int channels, int n, long in_pitch, long out_pitch, int stages, int warm_chunks,
+                          void *stream);
 /* general direct form I, one channel, double, the reference's exact operation order (llz_iir.c:103-132).
  * xs: N+1 doubles, ys: M+1 doubles (delay lines, read and written) */
-/* float32 cascades with a short memory: a wave owns a (channel, time segment) and runs all sections in registers.
- * coef32: [S][5], pd32: [S][16] = P^(2^d) d<4, pl32: [S][64][12], all float; state as above (double). */
-int llzs_iir_cascade_wave_f32(const float *in, float *out, const float *coef32, const float *pd32, const float *pl32,
-                              const float *ph32 /* [S][24]: (h1[k], h2[k]) k < 8, the outputs at k of the unit start
-                                                   * states, then b0 b1 b2 a1 a2 and 3 pad; NULL = the
-                                                   * unpacked kernel */,
-                              const double *state_in, double *state_out, int channels, int n, long in_pitch, long out_pitch, int stages,
-                              int warm_chunks, void *stream);
-/* the same with 32 samples per lane and the b0 gains folded into in_gain (iir.hip: k_iir_cascade_wave_pk32): n % 2048 == 0;
- * tables for P = A^32; ph32 [S][40] = (h1[k], h2[k]) k < 16, then 1 b1/b0 b2/b0 a1 a2 xfac yfac pad */
-int llzs_iir_cascade_wave32_f32(const float *in, float *out, const float *pd32, const float *pl32, const float *ph32,
-                                const double *state_in, double *state_out, int channels, int n, long in_pitch,
-                                long out_pitch, int stages, int warm_chunks, float in_gain, void *stream);
-/* the same in double for cascades float32 arithmetic is not good enough for (k_iir_cascade_wave_pf64w): cw [S][8] = b1/b0,
- * b2/b0, a1, a2, xfac, yfac, 0, 0; pd [S][16]; plc [S][448] (powers of A^32, see the kernel) */
-int llzs_iir_cascade_wave32_f64(const float *in, float *out, const double *cw, const double *pd, const double *plc,
-                                const double *state_in, double *state, int channels, int n, long in_pitch, long out_pitch,
-                                int stages, int warm_chunks, double in_gain, void *stream);
-/* the same in double from the pipelined kernel's tables; at most 8 sections */
-int llzs_iir_cascade_wave_f64(const float *in, float *out, const double *coef, const double *pd, const double *pl,
-                              const double *state_in, double *state_out, int channels, int n, long in_pitch, long out_pitch, int stages,
-                              int warm_chunks, void *stream);
 int llzs_iir_df1_f64(const double *in, double *out, const double *a, const double *b, double *xs, double *ys,
                      int M, int N, int n, void *stream);
 /* the same recurrence for many channels (iir_df1.hip): float32 in / out, double arithmetic in the reference's order; ab =

@@ -97,6 +97,29 @@ int main(void)
         CHECK(llz_iir_cascade_mc(h, fx, fy, 2048) == 2048);
         llz_iir_cascade_mc_uninit(h);
     }
+    {   /* what else the cascade's table builders and path chooser must handle */
+        const int n = 4096 + 1024 + 7;                                   /* 2048-sample chunks, a 1024-sample one, a ragged rest */
+        double lq[12][6];
+        for (int s = 0; s < 12; s++) { lq[s][0] = 0.2; lq[s][1] = 0.4; lq[s][2] = 0.2; lq[s][3] = 1; lq[s][4] = -0.84 + 0.01 * s; lq[s][5] = 0.1936; }
+        h = llz_iir_cascade_mc_init(4, 12, &lq[0][0]); CHECK(h != BAD);  /* 9..16 sections: stage pipeline only, no wave tables */
+        CHECK(llz_iir_cascade_mc_precision(h) == 32);
+        CHECK(llz_iir_cascade_mc(h, fx, fy, n) == n);
+        llz_iir_cascade_mc_uninit(h);
+        h = llz_iir_cascade_mc_init(4, 8, &lq[0][0]); CHECK(h != BAD);   /* 8 float32 sections: the folded float tables */
+        CHECK(llz_iir_cascade_mc_precision(h) == 32);
+        CHECK(llz_iir_cascade_mc(h, fx, fy, n) == n && llz_iir_cascade_mc(h, fx, fy, 2048) == 2048);
+        llz_iir_cascade_mc_uninit(h);
+        for (int s = 0; s < 8; s++) { lq[s][0] = 1e-4; lq[s][1] = 2e-4; lq[s][2] = 1e-4; }
+        h = llz_iir_cascade_mc_init(4, 8, &lq[0][0]); CHECK(h != BAD);   /* partial products of b0 down to 1e-32: outside the */
+        CHECK(llz_iir_cascade_mc_precision(h) == 32);                    /* float limits, 16-sample tables only */
+        CHECK(llz_iir_cascade_mc(h, fx, fy, n) == n);
+        llz_iir_cascade_mc_uninit(h);
+        lq[2][0] = 0.2; lq[2][1] = 0.4; lq[2][2] = 0.2; lq[2][4] = -1.9; lq[2][5] = 1.0;
+        h = llz_iir_cascade_mc_init(4, 3, &lq[0][0]); CHECK(h != BAD);   /* an undamped section: it never forgets (no warm-up */
+        CHECK(llz_iir_cascade_mc_precision(h) == 64);                    /* length), so no time segments and no wave form */
+        CHECK(llz_iir_cascade_mc(h, fx, fy, n) == n);
+        llz_iir_cascade_mc_uninit(h);
+    }
     /* resamplers: the reference's three and the batch forms (int16 screen tables, matrix-core band tables) */
     h = llz_resample_filter_init(147, 160, 1.0, BLACKMAN); CHECK(h != BAD);
     int nb = llz_get_resample_framelen_bytes(h), ob = 0;
