@@ -301,7 +301,7 @@ void llz_synthesis_mdct(unsigned long handle, double *X, double *x)
 }
 
 /* ---- Part 2: batch extension ----
- * fft_len up to 4096: one launch per direction (kernels/fft.hip).  Above 4096, and at 4096 under the fft_generic tune: the
+ * fft_len up to 4096: one launch per direction (kernels/stft.hip).  Above 4096, and at 4096 under the fft_generic tune: the
  * composed form -- framing kernel, the float32 batch transform of llz_fft_batch on a scratch buffer, framing kernel
  * (kernels/stft_large.hip) -- over chunks of at most LLZS_STFT_CHUNK_POINTS points, so the scratch stays bounded whatever
  * a call's frame count.  (A one-launch form of 8192 on the staged LDS kernels measured slower than the composed form:

@@ -1,5 +1,7 @@
-// fft_core.hpp -- device code shared by the FFT-based kernels (fft.hip, mdct.hip): complex type, the three arithmetic
-// flavours, the LDS image and twiddle-table layout, and the fused radix-2 passes.  See fft.hip for the dataflow.
+// fft_core.hpp -- code shared by the staged FFT-based kernels (fft.hip, acf_fft.hip, stft.hip, mdct.hip, mdct_q15.hip,
+// fft_large.hip): complex type, the three arithmetic flavours, the LDS image and twiddle-table layout, the fused radix-2
+// passes with their one pass loop (fft_run) and pass split (fft_groups), and the host side's workgroup geometry
+// (fft_make_plan) and compile-time launch dispatch (fft_pick).  See fft.hip for the dataflow.
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -301,25 +303,62 @@ static inline unsigned fft_groups(int log2n)
     return groups;
 }
 
-// all passes of one direction over the workgroup's ntr float32 transforms (barrier after each pass)
-template <bool INVERSE>
-__device__ __forceinline__ void fft_run_f32(cpx<float> *s, int ntr, int size, int log2n, int tstride,
-                                            const cpx<float> *tw, unsigned groups, int tid)
+// all passes of one direction over the workgroup's ntr transforms (barrier after each pass): the only pass loop.
+// forward: the first stage of a pass has half-span size >> (done+1), its elements are step = that >> (G-1) apart;
+// inverse: the first stage has half-span 1 << done = step
+template <typename A, bool INVERSE>
+__device__ __forceinline__ void fft_run(cpx<typename A::data_t> *s, int ntr, int size, int log2n, int tstride,
+                                        const cpx<typename A::tw_t> *tw, unsigned groups, int tid)
 {
-    int done = 0;
+    int done = 0;                                          // stages finished so far
 #pragma unroll 1
     for (int pss = 0; pss < 4; pss++) {
         const int G = (groups >> (4 * pss)) & 15;
         if (G == 0) break;
         const int log2step = INVERSE ? done : (log2n - done - G);
         switch (G) {
-        case 1: fft_pass_f32<1, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
-        case 2: fft_pass_f32<2, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
-        case 3: fft_pass_f32<3, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
-        default: fft_pass_f32<4, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
+        case 1: fft_pass_any<A, 1, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
+        case 2: fft_pass_any<A, 2, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
+        case 3: fft_pass_any<A, 3, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
+        default: fft_pass_any<A, 4, INVERSE>(s, ntr, size, log2n, log2step, tstride, tw, tid); break;
         }
         done += G;
     }
+}
+
+// Geometry of the staged kernels.  Transforms of a workgroup are tstride elements apart in LDS: the padded image
+// (fft_phys) and one element more, so that equal positions of neighbouring transforms fall into different banks.
+__host__ __device__ constexpr int fft_tstride(int size) { return size + (size >> 5) + 1; }
+
+// A workgroup passes over 2048 points (256 lanes x 8): tpw transforms share it, at most `count`, one from 2048 points on.
+// lds: the tpw images and the twiddle table of flavour A, then `extra` bytes and `extra_per_tr` bytes per transform.
+struct fft_plan {
+    int tpw, tstride;
+    size_t lds;
+    long blocks;                                           // ceil(count / tpw)
+};
+template <typename A>
+static inline fft_plan fft_make_plan(int size, long count, size_t extra = 0, size_t extra_per_tr = 0)
+{
+    fft_plan p;
+    p.tpw = size < 2048 ? 2048 / size : 1;
+    if (p.tpw > count) p.tpw = (int)count;
+    p.tstride = fft_tstride(size);
+    p.lds = (size_t)p.tpw * p.tstride * 2 * sizeof(typename A::data_t) +
+            (size_t)tw_entries(size) * 2 * sizeof(typename A::tw_t) + extra + (size_t)p.tpw * extra_per_tr;
+    p.blocks = (count + p.tpw - 1) / p.tpw;
+    return p;
+}
+
+// Compile-time dispatch of the launchers: f is called with std::true_type / std::false_type for a run-time flag, or with
+// the std::integral_constant of the first E among E0, Es... that equals e (the last one if none does).
+template <typename F>
+static inline auto fft_pick(bool flag, F f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+template <int E0, int... Es, typename F>
+static inline auto fft_pick_e(int e, F f)
+{
+    if constexpr (sizeof...(Es) == 0) return f(std::integral_constant<int, E0>{});
+    else return e == E0 ? f(std::integral_constant<int, E0>{}) : fft_pick_e<Es...>(e, f);
 }
 
 } // namespace

@@ -136,7 +136,7 @@ k_mdct4_f32(const float *__restrict__ in, float *__restrict__ out, int count, in
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int N2 = N >> 1, N4 = N >> 2;
-    const int tstride = fft_phys(N4) + 1;
+    const int tstride = fft_tstride(N4);
     cpx<float> *s = reinterpret_cast<cpx<float> *>(smem_raw);
     cpx<float> *tw = s + (size_t)tpw * tstride;
     float *buf = reinterpret_cast<float *>(tw + tw_entries(N4));            // [tpw][N] staging of rows
@@ -171,7 +171,7 @@ k_mdct4_f32(const float *__restrict__ in, float *__restrict__ out, int count, in
         s[tr * tstride + fft_phys(k)] = z;
     }
     __syncthreads();
-    fft_run_f32<false>(s, ntr, N4, log2n4, tstride, tw, groups, tid);       // both directions use the FORWARD transform
+    fft_run<arith_f32, false>(s, ntr, N4, log2n4, tstride, tw, groups, tid); // both directions use the FORWARD transform
     // post-twiddle from bit-reversed positions into the staging rows, in output order
     for (int e = tid; e < ntr * N4; e += FFT_THREADS) {
         const int tr = e >> log2n4, k = e & (N4 - 1);
@@ -252,26 +252,17 @@ extern "C" int llzs_mdct4_f32(const float *in, float *out, int count, int N, con
         if (rc != LLZ_ERR_RANGE) return rc;
     }
     const int N4 = N >> 2, log2n4 = log2n - 2;
-    int tpw = 2048 / N4;
-    if (tpw > count) tpw = count;
-    const int tstride = N4 + (N4 >> 5) + 1;
-    const size_t lds = (size_t)tpw * tstride * 2 * sizeof(float) + (size_t)tw_entries(N4) * 2 * sizeof(float) +
-                       (size_t)tpw * N * sizeof(float);
-    const unsigned blocks = (unsigned)((count + tpw - 1) / tpw);
+    const fft_plan pl = fft_make_plan<arith_f32>(N4, count, 0, (size_t)N * sizeof(float));    // + the rows' staging
     const float sqrt_cof = (float)(1.0 / sqrt((double)N));
-    if (inverse) {
-        if (lds >= 64 * 1024)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct4_f32<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mdct4_f32<true>, dim3(blocks), dim3(FFT_THREADS), lds, as_stream(stream), in, out, count, N,
-                           log2n4, tc, ts, cs, tpw, fft_groups(log2n4), sqrt_cof);
-    } else {
-        if (lds >= 64 * 1024)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct4_f32<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mdct4_f32<false>, dim3(blocks), dim3(FFT_THREADS), lds, as_stream(stream), in, out, count, N,
-                           log2n4, tc, ts, cs, tpw, fft_groups(log2n4), sqrt_cof);
-    }
+    const int rc = fft_pick(inverse != 0, [&](auto inv) {
+        if (pl.lds >= 64 * 1024)
+            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct4_f32<inv()>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(k_mdct4_f32<inv()>, dim3((unsigned)pl.blocks), dim3(FFT_THREADS), pl.lds, as_stream(stream), in,
+                           out, count, N, log2n4, tc, ts, cs, pl.tpw, fft_groups(log2n4), sqrt_cof);
+        return LLZ_OK;
+    });
+    if (rc != LLZ_OK) return rc;
     LLZ_LAUNCH_CHECK("k_mdct4_f32");
     return LLZ_OK;
 }

@@ -145,7 +145,7 @@ k_mdct4_q15(const int *__restrict__ in, int *__restrict__ out, int count, int N,
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int N2 = N >> 1, N4 = N >> 2;
-    const int tstride = fft_phys(N4) + 1;
+    const int tstride = fft_tstride(N4);
     cpx<int> *s = reinterpret_cast<cpx<int> *>(smem_raw);
     cpx<short> *tw = reinterpret_cast<cpx<short> *>(s + (size_t)tpw * tstride);
     int *buf = reinterpret_cast<int *>(tw + tw_entries(N4) + (tw_entries(N4) & 1));      // [tpw][N] rows
@@ -184,22 +184,7 @@ k_mdct4_q15(const int *__restrict__ in, int *__restrict__ out, int count, int N,
         s[tr * tstride + fft_phys(k)] = z;
     }
     __syncthreads();
-    {
-        int done = 0;                                                     // (both directions run the FORWARD transform)
-#pragma unroll 1
-        for (int p = 0; p < 4; p++) {
-            const int G = (groups >> (4 * p)) & 15;
-            if (G == 0) break;
-            const int log2step = log2n4 - done - G;
-            switch (G) {
-            case 1: fft_pass<arith_q15, 1, false>(s, ntr, N4, log2n4, log2step, tstride, tw, tid); break;
-            case 2: fft_pass<arith_q15, 2, false>(s, ntr, N4, log2n4, log2step, tstride, tw, tid); break;
-            case 3: fft_pass<arith_q15, 3, false>(s, ntr, N4, log2n4, log2step, tstride, tw, tid); break;
-            default: fft_pass<arith_q15, 4, false>(s, ntr, N4, log2n4, log2step, tstride, tw, tid); break;
-            }
-            done += G;
-        }
-    }
+    fft_run<arith_q15, false>(s, ntr, N4, log2n4, tstride, tw, groups, tid);   // (both directions run the FORWARD transform)
     for (int e = tid; e < ntr * N4; e += FFT_THREADS) {
         const int tr = e >> log2n4, m = e & (N4 - 1);
         const cpx<int> v = s[tr * tstride + fft_phys((int)(__brev((unsigned)m) >> (32 - log2n4)))];   // bin m
@@ -247,7 +232,7 @@ k_mdct1_q15(const int *__restrict__ in, int *__restrict__ out, int count, int N,
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int N2 = N >> 1;
-    const int tstride = fft_phys(N) + 1;
+    const int tstride = fft_tstride(N);
     cpx<int> *s = reinterpret_cast<cpx<int> *>(smem_raw);
     cpx<short> *tw = reinterpret_cast<cpx<short> *>(s + (size_t)tpw * tstride);
     const int tid = threadIdx.x;
@@ -270,22 +255,7 @@ k_mdct1_q15(const int *__restrict__ in, int *__restrict__ out, int count, int N,
         s[tr * tstride + fft_phys(at)] = z;
     }
     __syncthreads();
-    {
-        int done = 0;
-#pragma unroll 1
-        for (int p = 0; p < 4; p++) {
-            const int G = (groups >> (4 * p)) & 15;
-            if (G == 0) break;
-            const int log2step = INVERSE ? done : (log2n - done - G);
-            switch (G) {
-            case 1: fft_pass<arith_q15, 1, INVERSE>(s, ntr, N, log2n, log2step, tstride, tw, tid); break;
-            case 2: fft_pass<arith_q15, 2, INVERSE>(s, ntr, N, log2n, log2step, tstride, tw, tid); break;
-            case 3: fft_pass<arith_q15, 3, INVERSE>(s, ntr, N, log2n, log2step, tstride, tw, tid); break;
-            default: fft_pass<arith_q15, 4, INVERSE>(s, ntr, N, log2n, log2step, tstride, tw, tid); break;
-            }
-            done += G;
-        }
-    }
+    fft_run<arith_q15, INVERSE>(s, ntr, N, log2n, tstride, tw, groups, tid);
     for (int e = tid; e < ntr * out_len; e += FFT_THREADS) {
         const int tr = e / out_len, k = e - tr * out_len;
         // forward: bin k sits at the bit-reversed position; inverse: sample k in place, scaled by 2^-log2n
@@ -313,26 +283,17 @@ extern "C" int llzs_mdct1_q15(const int *in, int *out, int count, int N, const s
         llzs_set_error("mdct1_q15: bad arguments (N=%d must be a power of two in 4..4096, count=%d)", N, count);
         return LLZ_ERR_ARG;
     }
-    int tpw = 2048 / N;
-    if (tpw < 1) tpw = 1;
-    if (tpw > count) tpw = count;
-    const int tstride = N + (N >> 5) + 1;
-    const size_t lds = (size_t)tpw * tstride * 2 * sizeof(int) + (size_t)tw_entries(N) * 2 * sizeof(short);
-    const unsigned blocks = (unsigned)((count + tpw - 1) / tpw);
+    const fft_plan pl = fft_make_plan<arith_q15>(N, count);
     const short2 *p2 = reinterpret_cast<const short2 *>(pre), *q2 = reinterpret_cast<const short2 *>(post);
-    if (inverse) {
-        if (lds >= 64 * 1024)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct1_q15<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mdct1_q15<true>, dim3(blocks), dim3(FFT_THREADS), lds, as_stream(stream), in, out, count, N, log2n,
-                           p2, q2, cs, tpw, fft_groups(log2n));
-    } else {
-        if (lds >= 64 * 1024)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct1_q15<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mdct1_q15<false>, dim3(blocks), dim3(FFT_THREADS), lds, as_stream(stream), in, out, count, N, log2n,
-                           p2, q2, cs, tpw, fft_groups(log2n));
-    }
+    const int rc = fft_pick(inverse != 0, [&](auto inv) {
+        if (pl.lds >= 64 * 1024)
+            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct1_q15<inv()>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(k_mdct1_q15<inv()>, dim3((unsigned)pl.blocks), dim3(FFT_THREADS), pl.lds, as_stream(stream), in, out,
+                           count, N, log2n, p2, q2, cs, pl.tpw, fft_groups(log2n));
+        return LLZ_OK;
+    });
+    if (rc != LLZ_OK) return rc;
     LLZ_LAUNCH_CHECK("k_mdct1_q15");
     return LLZ_OK;
 }
@@ -349,27 +310,19 @@ extern "C" int llzs_mdct4_q15(const int *in, int *out, int count, int N, const s
         return LLZ_ERR_ARG;
     }
     const int N4 = N >> 2, log2n4 = log2n - 2;
-    int tpw = 2048 / N4;
-    if (tpw < 1) tpw = 1;
-    if (tpw > count) tpw = count;
-    const int tstride = N4 + (N4 >> 5) + 1;
-    const int twe = tw_entries(N4) + (tw_entries(N4) & 1);
-    const size_t lds = (size_t)tpw * tstride * 2 * sizeof(int) + (size_t)twe * 2 * sizeof(short) + (size_t)tpw * N * sizeof(int);
-    const unsigned blocks = (unsigned)((count + tpw - 1) / tpw);
+    // (the kernel pads the table to an even count of entries in front of the rows)
+    const fft_plan pl = fft_make_plan<arith_q15>(N4, count, (size_t)(tw_entries(N4) & 1) * 2 * sizeof(short),
+                                                 (size_t)N * sizeof(int));
     const short2 *p2 = reinterpret_cast<const short2 *>(pre), *q2 = reinterpret_cast<const short2 *>(post);
-    if (inverse) {
-        if (lds >= 64 * 1024)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct4_q15<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mdct4_q15<true>, dim3(blocks), dim3(FFT_THREADS), lds, as_stream(stream), in, out, count, N,
-                           log2n4, p2, q2, cs, tpw, fft_groups(log2n4), cof);
-    } else {
-        if (lds >= 64 * 1024)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct4_q15<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mdct4_q15<false>, dim3(blocks), dim3(FFT_THREADS), lds, as_stream(stream), in, out, count, N,
-                           log2n4, p2, q2, cs, tpw, fft_groups(log2n4), cof);
-    }
+    const int rc = fft_pick(inverse != 0, [&](auto inv) {
+        if (pl.lds >= 64 * 1024)
+            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mdct4_q15<inv()>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(k_mdct4_q15<inv()>, dim3((unsigned)pl.blocks), dim3(FFT_THREADS), pl.lds, as_stream(stream), in, out,
+                           count, N, log2n4, p2, q2, cs, pl.tpw, fft_groups(log2n4), cof);
+        return LLZ_OK;
+    });
+    if (rc != LLZ_OK) return rc;
     LLZ_LAUNCH_CHECK("k_mdct4_q15");
     return LLZ_OK;
 }

@@ -1,5 +1,5 @@
 // stft_large.hip -- the framing half of the composed float32 STFT batch (llz_stft_mc_*) for frames the one-launch kernels
-// of fft.hip do not take: fft_len above 4096 (up to LLZS_FFT_MAX), and 4096 under the fft_generic tune.  The host
+// of stft.hip do not take: fft_len above 4096 (up to LLZS_FFT_MAX), and 4096 under the fft_generic tune.  The host
 // (llz_asmodel_host.c) walks a call's frames in chunks of at most LLZS_STFT_CHUNK_POINTS points and, per chunk, runs
 //
 //   analysis  : k_stft_frames_large (windowed frames -> complex scratch), the float32 batch transform of llz_fft_batch on

@@ -253,7 +253,7 @@ int llzs_autocorr_mc_f32(const float *x, float *r, int frames, int n, int p, voi
 int llzs_acf_pack(const float *x, float *z, int frames, int n, int F, void *stream);
 int llzs_acf_power(float *z, int frames, int n, int F, void *stream);
 int llzs_acf_extract(const float *z, float *r, int frames, int p, int F, void *stream);
-/* the same five steps fused in LDS (fft.hip): one read of the frames, p+1 floats written per frame */
+/* the same five steps fused in LDS (acf_fft.hip): one read of the frames, p+1 floats written per frame */
 int llzs_acf_fused_f32(const float *x, float *r, int frames, int n, int p, int size, const float *cs, void *stream);
 
 /* ---- linear prediction (lpc.hip) ---- */
