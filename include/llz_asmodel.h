@@ -57,7 +57,8 @@ unsigned long llz_stft_mc_init(int channels, int overlap_hint, int frame_len, wi
 void          llz_stft_mc_uninit(unsigned long handle);
 int           llz_stft_mc_bins(unsigned long handle);          /* fft_len/2 + 1 */
 int           llz_stft_mc_set_stream(unsigned long handle, void *stream);
-/* x: planar [channels][frames*frame_len]; re, im: [channels][frames][bins].  Returns frames or < 0. */
+/* x: planar [channels][frames*frame_len]; re, im: [channels][frames][bins].  out may not overlap in (device memory): x
+ * against re and im, either way round, is refused with LLZ_ERR_ARG.  Returns frames or < 0. */
 int           llz_stft_mc_analysis(unsigned long handle, const float *x, float *re, float *im, int frames);
 int           llz_stft_mc_synthesis(unsigned long handle, const float *re, const float *im, float *x, int frames);
 
@@ -66,7 +67,8 @@ int           llz_stft_mc_synthesis(unsigned long handle, const float *re, const
  * added).  One handle serves both directions and keeps per channel the previous input frame (analysis) and the overlap-add
  * tail (synthesis), so consecutive calls continue the streams; analysis followed by synthesis returns the input delayed by
  * one frame.  frame_len a power of two in 128..4096.  x: planar [channels][frames*frame_len]; X: [channels][frames]
- * [frame_len].  Pointers may be device or host memory (x and X distinct).  Return frames or < 0. */
+ * [frame_len].  Pointers may be device or host memory (x and X distinct).  out may not overlap in (device memory):
+ * refused with LLZ_ERR_ARG; a device pointer off a 16-byte boundary is staged like host memory.  Return frames or < 0. */
 unsigned long llz_mdct_frames_mc_init(int channels, int frame_len, mdct_win_t win_type);
 void          llz_mdct_frames_mc_uninit(unsigned long handle);
 int           llz_mdct_frames_mc_set_stream(unsigned long handle, void *stream);

@@ -27,9 +27,10 @@ void          llz_autocorr_fast(unsigned long handle, double *x, int n, int p, d
 
 /* ---- Part 2: batch extension, float32 ---- */
 /* direct form for `frames` independent frames of n samples: r[f][k] = sum_i x[f][i]*x[f][i+k], k = 0..p.
- * x: planar [frames][n], r: planar [frames][p+1]; device or host pointers; p < n, p <= 255. Returns 0 or < 0. */
+ * x: planar [frames][n], r: planar [frames][p+1]; device or host pointers; p < n, p <= 255. out may not overlap in
+ * (device memory): r overlapping x is refused with LLZ_ERR_ARG. Returns 0 or < 0. */
 int llz_autocorr_mc(const float *x, float *r, int frames, int n, int p, void *stream);
-/* FFT form with the reference's definition (first n bins, doubled), n <= 2048 */
+/* FFT form with the reference's definition (first n bins, doubled), n <= 2048; out may not overlap in (device memory) */
 unsigned long llz_autocorr_fast_mc_init(int frames, int n);
 void          llz_autocorr_fast_mc_uninit(unsigned long handle);
 int           llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p);

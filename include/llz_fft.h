@@ -20,7 +20,8 @@ void          llz_ifft(unsigned long handle, double *data);
 
 unsigned long llz_fft_batch_init(int size);    /* float32; size: power of two, 8..16777216 (2^24) */
 void          llz_fft_batch_uninit(unsigned long handle);
-/* data: `count` transforms back to back, each 2*size floats (re,im interleaved); device or host pointer; in place */
+/* data: `count` transforms back to back, each 2*size floats (re,im interleaved); device or host pointer; in place
+ * (a device pointer off a 16-byte boundary is staged through the handle's own buffer, like host memory) */
 int           llz_fft_batch(unsigned long handle, float *data, int count);
 int           llz_ifft_batch(unsigned long handle, float *data, int count);
 int           llz_fft_batch_set_stream(unsigned long handle, void *stream);

@@ -18,7 +18,8 @@ void          llz_fft_fixed_uninit(unsigned long handle);
 void          llz_fft_fixed(unsigned long handle, int *data);
 void          llz_ifft_fixed(unsigned long handle, int *data);
 
-/* batched: `count` transforms back to back in device (or host) memory */
+/* batched: `count` transforms back to back in device (or host) memory, in place (a device pointer off a 16-byte boundary is
+ * staged through the handle's own buffer, like host memory) */
 int           llz_fft_fixed_batch(unsigned long handle, int *data, int count);
 int           llz_ifft_fixed_batch(unsigned long handle, int *data, int count);
 int           llz_fft_fixed_set_stream(unsigned long handle, void *stream);

@@ -83,7 +83,8 @@ unsigned long llz_fir_filter_mc_bandpass_init(int channels, int frame_len, int f
 unsigned long llz_fir_filter_mc_bandstop_init(int channels, int frame_len, int flt_len, double fc1, double fc2, win_t win_type);
 void          llz_fir_filter_mc_uninit(unsigned long handle);
 
-/* planar [channels][frame_len] float32 in and out (out may not alias in). Pointers may be device memory
+/* planar [channels][frame_len] float32 in and out (out may not alias in; out may not overlap in (device memory): refused
+ * with LLZ_ERR_ARG). Pointers may be device memory
  * (used in place, asynchronous on the handle's stream) or host memory (staged through the GPU, synchronous).
  * frame_len must equal the init frame_len. Returns frame_len, or a negative LLZ_ERR_* code. */
 int llz_fir_filter_mc(unsigned long handle, const float *in, float *out, int frame_len);

@@ -24,7 +24,9 @@ int           llz_iir_filter_flush(unsigned long handle, double *y);            
  * State (2 x + 2 y values per stage and channel) is kept in double on the device between calls. */
 unsigned long llz_iir_cascade_mc_init(int channels, int stages, const double *coef);
 void          llz_iir_cascade_mc_uninit(unsigned long handle);
-/* planar [channels][frame_len] float32, device or host pointers; any frame_len >= 1. Returns frame_len. */
+/* planar [channels][frame_len] float32, device or host pointers; any frame_len >= 1. out may not overlap in (device
+ * memory): a later time segment reads x where an earlier one writes y, so y overlapping x is refused with LLZ_ERR_ARG
+ * (host x == y is staged through the handle's own buffers and works in place). Returns frame_len. */
 int           llz_iir_cascade_mc(unsigned long handle, const float *x, float *y, int frame_len);
 int           llz_iir_cascade_mc_set_stream(unsigned long handle, void *stream);
 /* working precision of the pipelined kernel for this coefficient set: 64, or 32 when every section's rounding-noise gain
@@ -45,7 +47,8 @@ void          llz_iir_mc_uninit(unsigned long handle);
  * 1e-13 of peak before its first kept sample; segments are at least 8 warm-ups long, and a filter that has not decayed within
  * the probe is never split.  The output then equals the one-segment (reference-order) double sequence to about 1e-13
  * relative before the rounding to float32, not bit for bit, and may depend on frame_len.  llz_hip_tune("iir_segs", 1)
- * opts out: one segment per channel, bit for bit the reference's sequence rounded once. */
+ * opts out: one segment per channel, bit for bit the reference's sequence rounded once.
+ * out may not overlap in (device memory), and x == y is refused for host memory too: LLZ_ERR_ARG. */
 int           llz_iir_mc(unsigned long handle, const float *x, float *y, int frame_len);
 int           llz_iir_mc_flush(unsigned long handle, float *y);         /* N more samples of x = 0 per channel: [channels][N]; returns N */
 int           llz_iir_mc_set_stream(unsigned long handle, void *stream);

@@ -36,7 +36,8 @@ double        llz_lpc(unsigned long handle, double *x, int x_len, double *lpc_co
  * ...], kcof = 0, err = 0, gain = 0 -- unlike llz_lpc there is no handle, so no value carries over from another frame.
  * Nothing else is guarded: a recursion that divides by a zero error gives what the arithmetic gives, as in the reference.
  * p <= 32 computes the correlation and the recursion in one launch; 33 <= p <= 64 (and llz_hip_tune("lpc_split", 1))
- * runs llz_autocorr_mc's kernel and then the recursion as a second launch -- the same bits either way. */
+ * runs llz_autocorr_mc's kernel and then the recursion as a second launch -- the same bits either way.
+ * out may not overlap in (device memory): acof, kcof, err, gain or r overlapping x is refused with LLZ_ERR_ARG. */
 int llz_lpc_mc(const float *x, const float *win, float *acof, float *kcof, float *err, float *gain, float *r,
                int frames, int n, int p, void *stream);
 

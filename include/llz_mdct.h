@@ -38,7 +38,9 @@ int           llz_mdct_sine(double *w, int N);                           /* sin(
 int           llz_mdct_kbd(double *w, int N, double alpha);              /* Kaiser-Bessel derived: llz_mdct.c:156-182 */
 
 /* ---- Part 2: batch extension, float32, N/4-point-FFT algorithm ---- */
-/* len a power of two in 32..8192.  x: [count][len], X: [count][len/2], contiguous rows, device or host pointers. */
+/* len a power of two in 32..8192.  x: [count][len], X: [count][len/2], contiguous rows, device or host pointers.
+ * out may not overlap in (device memory): refused with LLZ_ERR_ARG.  A device pointer off a 16-byte boundary is staged
+ * through the handle's own buffer, like host memory. */
 unsigned long llz_mdct_batch_init(int len);
 void          llz_mdct_batch_uninit(unsigned long handle);
 int           llz_mdct_batch_set_stream(unsigned long handle, void *stream);

@@ -27,7 +27,8 @@ void          llz_mdct_fixed(unsigned long handle, int *x, int *X);      /* x: l
 void          llz_imdct_fixed(unsigned long handle, int *X, int *x);     /* X: len/2 -> x: len */
 
 /* ---- batch extension: `count` frames per call, rows contiguous: x [count][len], X [count][len/2].
- * Host or device pointers (device pointers are used in place, asynchronously on the handle's stream); out of place.
+ * Host or device pointers (device pointers are used in place, asynchronously on the handle's stream); out of place:
+ * out may not overlap in (device memory), refused with LLZ_ERR_ARG.
  * Returns count, or a negative LLZ_ERR_* code. ---- */
 int           llz_mdct_fixed_batch(unsigned long handle, const int *x, int *X, int count);
 int           llz_imdct_fixed_batch(unsigned long handle, const int *X, int *x, int count);

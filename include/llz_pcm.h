@@ -14,7 +14,8 @@ extern "C" {
 #endif
 
 /* out[c][i] = (float)in[i*channels + c] * scale   (scale = 1/32768 maps int16 onto [-1, 1): exact in float32).
- * in: n*channels int16, out: planar [channels][n] float32; device or host pointers. Returns 0 or < 0. */
+ * in: n*channels int16, out: planar [channels][n] float32; device or host pointers. out may not overlap in (device
+ * memory): refused with LLZ_ERR_ARG, here and in llz_pcm_interleave_f32_i16. Returns 0 or < 0. */
 int llz_pcm_deinterleave_i16_f32(const short *in, float *out, int channels, long n, float scale, void *stream);
 /* out[i*channels + c] = (short)clamp(in[c][i] * scale, -32768, 32767): the reference's own float->int16 rule
  * (clamp, then C truncation toward zero: llz_resample.c:596-601). */

@@ -53,7 +53,8 @@ void          llz_resample_mc_uninit(unsigned long handle);
 int  llz_resample_mc_sub_len(unsigned long handle);                 /* Q */
 long llz_resample_mc_out_len(unsigned long handle, long n_in);      /* n_in*L/M; n_in*L must divide by M, else -1 */
 /* in: planar [channels][n_in]; out: planar [channels][n_in*L/M]; device or host pointers of the handle's
- * sample format. History (Q-1 samples per channel) carries across calls. Returns outputs per channel or <0. */
+ * sample format. History (Q-1 samples per channel) carries across calls. out may not overlap in (device memory):
+ * refused with LLZ_ERR_ARG. Returns outputs per channel or <0. */
 long llz_resample_mc(unsigned long handle, const void *in, long n_in, void *out);
 int  llz_resample_mc_set_stream(unsigned long handle, void *stream);
 /* the L x Q tap matrix in float32 (what LLZ_PCM_F32 uses), for broadcast to other ranks: copies to host dst */

@@ -418,6 +418,12 @@ static int asmm_stage(asmm_t *f, const float *x, const float *re, const float *i
     *dx = (float *)x; *dre = (float *)re; *dim = (float *)im;
     const int x_dev = llzs_is_device_ptr(x), re_dev = llzs_is_device_ptr(re), im_dev = llzs_is_device_ptr(im);
     if (x_dev < 0 || re_dev < 0 || im_dev < 0) return LLZ_ERR_ARG;
+    const char *who = x_is_input ? "llz_stft_mc_analysis" : "llz_stft_mc_synthesis";
+    if (x_is_input ? (llz_refuse_device_overlap(who, "x", x, xb, x_dev, "re", re, sb, re_dev) ||
+                      llz_refuse_device_overlap(who, "x", x, xb, x_dev, "im", im, sb, im_dev))
+                   : (llz_refuse_device_overlap(who, "re", re, sb, re_dev, "x", x, xb, x_dev) ||
+                      llz_refuse_device_overlap(who, "im", im, sb, im_dev, "x", x, xb, x_dev)))
+        return LLZ_ERR_ARG;
     if (!x_dev) {
         *dx = (float *)llz_stage_reserve(&f->st_x, xb);
         if (!*dx) return LLZ_ERR_NOMEM;
@@ -661,11 +667,13 @@ static int amdm_run(unsigned long handle, const float *in, float *out, int frame
     const float *d_in = in;
     float *d_out = out;
     int rc = (in_dev < 0 || out_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;
-    if (rc == LLZ_OK && !in_dev) {
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap(who, "in", in, bytes, in_dev, "out", out, bytes, out_dev);
+    const int in_place = llz_in_place(in, in_dev), out_place = llz_in_place(out, out_dev);
+    if (rc == LLZ_OK && !in_place) {                        /* host memory, or device memory off a 16-byte boundary */
         d_in = (const float *)llz_stage_reserve(inverse ? &f->st_X : &f->st_x, bytes);
-        rc = d_in ? llzs_h2d((void *)d_in, in, bytes, f->stream) : LLZ_ERR_NOMEM;
+        rc = d_in ? llz_stage_load((void *)d_in, in, bytes, in_dev, f->stream) : LLZ_ERR_NOMEM;
     }
-    if (rc == LLZ_OK && !out_dev) {
+    if (rc == LLZ_OK && !out_place) {
         d_out = (float *)llz_stage_reserve(inverse ? &f->st_x : &f->st_X, bytes);
         if (!d_out) rc = LLZ_ERR_NOMEM;
     }
@@ -675,7 +683,7 @@ static int amdm_run(unsigned long handle, const float *in, float *out, int frame
         rc = llzs_mdct4_frames_f32(d_in, d_out, f->channels, frames, f->mdct_len, f->d_tc, f->d_ts, f->d_cs, f->d_w, st[*cur],
                                    st[*cur ^ 1], inverse, f->stream);
     if (rc == LLZ_OK) *cur ^= 1;
-    if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
+    if (rc == LLZ_OK && !out_place) rc = llz_stage_store(out, d_out, bytes, out_dev, f->stream);
     llzs_device_leave(prev);
     return rc == LLZ_OK ? frames : rc;
 }

@@ -124,6 +124,7 @@ int llz_autocorr_mc(const float *x, float *r, int frames, int n, int p, void *st
     const size_t xb = sizeof(float) * (size_t)frames * n, rb = sizeof(float) * (size_t)frames * (p + 1);
     const int x_dev = llzs_is_device_ptr(x), r_dev = llzs_is_device_ptr(r);
     if (x_dev < 0 || r_dev < 0) return LLZ_ERR_ARG;               /* device memory of a GPU that is not current */
+    if (llz_refuse_device_overlap("llz_autocorr_mc", "x", x, xb, x_dev, "r", r, rb, r_dev)) return LLZ_ERR_ARG;
     float *d_x = (float *)x, *d_r = r;
     int rc = LLZ_OK;
     if (!x_dev) {
@@ -220,6 +221,7 @@ int llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p)
     const float *d_x = x;
     float *d_r = r;
     int rc = (x_dev < 0 || r_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;     /* a buffer of another GPU: refused, message set */
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_autocorr_fast_mc", "x", x, xb, x_dev, "r", r, rb, r_dev);
     if (rc == LLZ_OK && !x_dev) {
         d_x = (const float *)llz_stage_reserve(&f->st_in, xb);
         rc = d_x ? llzs_h2d((void *)d_x, x, xb, f->stream) : LLZ_ERR_NOMEM;

@@ -168,13 +168,13 @@ static int fftb_run(unsigned long handle, float *data, int count, int inverse)
     const int prev = llzs_device_enter(f->device);
     const int on_dev = llzs_is_device_ptr(data);
     int rc = on_dev < 0 ? LLZ_ERR_ARG : LLZ_OK;
-    if (rc == LLZ_OK && on_dev) {
+    if (rc == LLZ_OK && llz_in_place(data, on_dev)) {
         rc = fftb_launch(f, data, count, inverse);
-    } else if (rc == LLZ_OK) {
+    } else if (rc == LLZ_OK) {                              /* host memory, or device memory off a 16-byte boundary */
         float *d = (float *)llz_stage_reserve(&f->st, bytes);
-        rc = d ? llzs_h2d(d, data, bytes, f->stream) : LLZ_ERR_NOMEM;
+        rc = d ? llz_stage_load(d, data, bytes, on_dev, f->stream) : LLZ_ERR_NOMEM;
         if (rc == LLZ_OK) rc = fftb_launch(f, d, count, inverse);
-        if (rc == LLZ_OK) rc = llzs_d2h(data, d, bytes, f->stream);
+        if (rc == LLZ_OK) rc = llz_stage_store(data, d, bytes, on_dev, f->stream);
     }
     llzs_device_leave(prev);
     return rc;
@@ -256,13 +256,13 @@ static int fftx_run(unsigned long handle, int *data, int count, int inverse)
     const int prev = llzs_device_enter(f->device);
     const int on_dev = llzs_is_device_ptr(data);
     int rc = on_dev < 0 ? LLZ_ERR_ARG : LLZ_OK;
-    if (rc == LLZ_OK && on_dev) {
+    if (rc == LLZ_OK && llz_in_place(data, on_dev)) {
         rc = llzs_fft_fixed(data, count, f->size, f->d_cs, inverse, f->stream);
-    } else if (rc == LLZ_OK) {
+    } else if (rc == LLZ_OK) {                              /* host memory, or device memory off a 16-byte boundary */
         int *d = (int *)llz_stage_reserve(&f->st, bytes);
-        rc = d ? llzs_h2d(d, data, bytes, f->stream) : LLZ_ERR_NOMEM;
+        rc = d ? llz_stage_load(d, data, bytes, on_dev, f->stream) : LLZ_ERR_NOMEM;
         if (rc == LLZ_OK) rc = llzs_fft_fixed(d, count, f->size, f->d_cs, inverse, f->stream);
-        if (rc == LLZ_OK) rc = llzs_d2h(data, d, bytes, f->stream);
+        if (rc == LLZ_OK) rc = llz_stage_store(data, d, bytes, on_dev, f->stream);
     }
     llzs_device_leave(prev);
     return rc;

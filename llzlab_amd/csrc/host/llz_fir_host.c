@@ -444,6 +444,7 @@ static int firm_process(firm_t *f, const float *in, float *out, int frame_len)
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
+    if (llz_refuse_device_overlap("llz_fir_filter_mc", "in", in, bytes, in_dev, "out", out, bytes, out_dev)) return LLZ_ERR_ARG;
     const float *d_in = in;
     float *d_out = out;
     int rc = LLZ_OK;

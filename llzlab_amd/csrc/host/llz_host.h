@@ -32,6 +32,26 @@ double *llz_host_fft_table_f64(int size);
  * (staged through the GPU) and LLZ_ERR_ARG, with a message, for device memory that lives on another device -- a handle
  * binds its device before it looks at the caller's pointers, so a buffer of the wrong GPU is refused instead of faulting. */
 
+/* 1 when the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share at least one byte (an empty range shares none) */
+int llz_ranges_intersect(const void *a, size_t a_bytes, const void *b, size_t b_bytes);
+/* The out-of-place batch entry points call this before they stage or launch anything: LLZ_ERR_ARG, with the message
+ * "<who>: <out_name> may not overlap <in_name> (device memory)", when both buffers are device memory (in_dev / out_dev as
+ * llzs_is_device_ptr() answered) and their ranges intersect -- a kernel reads and writes such a pair in no defined order;
+ * LLZ_OK otherwise.  Host buffers are staged through the library's own device memory, so they are never refused here. */
+int llz_refuse_device_overlap(const char *who, const char *in_name, const void *in, size_t in_bytes, int in_dev,
+                              const char *out_name, const void *out, size_t out_bytes, int out_dev);
+
+/* The register transforms (fft.hip: llz_fft_batch, llz_fft_fixed_batch, llz_mdct_batch, llz_mdct_frames_mc_*) move 8 or 16
+ * bytes per lane and take their rows on a 16-byte boundary; the headers ask no more of a caller's pointer than its element's
+ * alignment.  llz_in_place() is 1 for device memory (dev as llzs_is_device_ptr() answered) such a kernel may use where it
+ * lies; everything else -- host memory, and device memory at a lesser alignment -- goes through the handle's staging buffer
+ * with llz_stage_load() / llz_stage_store() (a copy from / to host memory waits for the stream, one between device buffers
+ * is ordered on it). */
+enum { LLZ_VEC_ALIGN = 16 };
+int llz_in_place(const void *p, int dev);
+int llz_stage_load(void *d_stage, const void *user, size_t bytes, int user_dev, void *stream);
+int llz_stage_store(void *user, const void *d_stage, size_t bytes, int user_dev, void *stream);
+
 /* staging buffers for callers that hand over host memory */
 typedef struct {
     void *dev;

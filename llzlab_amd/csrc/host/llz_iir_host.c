@@ -486,6 +486,8 @@ static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len)
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
     const int in_dev = llzs_is_device_ptr(x), out_dev = llzs_is_device_ptr(y);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
+    /* a later time segment reads its warm-up chunks from x while the segment before it writes them to y */
+    if (llz_refuse_device_overlap("llz_iir_cascade_mc", "x", x, bytes, in_dev, "y", y, bytes, out_dev)) return LLZ_ERR_ARG;
     const float *d_in = x;
     float *d_out = y;
     int rc = LLZ_OK;
@@ -649,6 +651,7 @@ int llz_iir_mc(unsigned long handle, const float *x, float *y, int frame_len)
     const float *d_in = x;
     float *d_out = y;
     int rc = (in_dev < 0 || out_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_iir_mc", "x", x, bytes, in_dev, "y", y, bytes, out_dev);
     if (rc == LLZ_OK && !in_dev) {
         d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
         rc = d_in ? llzs_h2d((void *)d_in, x, bytes, f->stream) : LLZ_ERR_NOMEM;

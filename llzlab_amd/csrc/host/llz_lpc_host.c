@@ -219,6 +219,15 @@ int llz_lpc_mc(const float *x, const float *win, float *acof, float *kcof, float
     lpc_buf b[NB];
     memset(b, 0, sizeof(b));
     const int split = p > 32 || llzs_tune(LLZS_TUNE_LPC_SPLIT) == 1;
+    /* no output may overlap x on the device: checked for all of them before anything is staged */
+    const struct { const char *name; const float *ptr; size_t bytes; } outs[5] = {
+        {"acof", acof, fb * F * P1}, {"kcof", p ? kcof : NULL, fb * F * p}, {"err", err, fb * F}, {"gain", gain, fb * F},
+        {"r", r, fb * F * P1}};
+    const int x_dev = llzs_is_device_ptr(x);
+    for (int i = 0; i < 5 && x_dev == 1; i++)
+        if (outs[i].ptr && llz_refuse_device_overlap("llz_lpc_mc", "x", x, fb * F * n, x_dev, outs[i].name, outs[i].ptr,
+                                                     outs[i].bytes, llzs_is_device_ptr(outs[i].ptr)))
+            return LLZ_ERR_ARG;
     int rc = lpc_bind(&b[BX], x, fb * F * n, 1, stream);
     if (rc == LLZ_OK) rc = lpc_bind(&b[BW], win, fb * n, 1, stream);
     if (rc == LLZ_OK) rc = lpc_bind(&b[BA], acof, fb * F * P1, 0, stream);

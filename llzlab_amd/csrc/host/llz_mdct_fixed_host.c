@@ -229,6 +229,7 @@ static int mdcx_run(unsigned long handle, const int *in, int *out, int count, in
     const int *d_in = in;
     int *d_out = out;
     int rc = (in_dev < 0 || out_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap(who, "in", in, ib, in_dev, "out", out, ob, out_dev);
     if (rc == LLZ_OK && !in_dev) {
         d_in = (const int *)llz_stage_reserve(inverse ? &f->bins : &f->time, ib);
         rc = d_in ? llzs_h2d((void *)d_in, in, ib, f->stream) : LLZ_ERR_NOMEM;

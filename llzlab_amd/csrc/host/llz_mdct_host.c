@@ -354,16 +354,18 @@ static int mdcb_run(unsigned long handle, const float *in, float *out, int count
     const float *d_in = in;
     float *d_out = out;
     int rc = (in_dev < 0 || out_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;
-    if (rc == LLZ_OK && !in_dev) {
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap(who, "in", in, ib, in_dev, "out", out, ob, out_dev);
+    const int in_place = llz_in_place(in, in_dev), out_place = llz_in_place(out, out_dev);
+    if (rc == LLZ_OK && !in_place) {                        /* host memory, or device memory off a 16-byte boundary */
         d_in = (const float *)llz_stage_reserve(&f->st_in, ib);
-        rc = d_in ? llzs_h2d((void *)d_in, in, ib, f->stream) : LLZ_ERR_NOMEM;
+        rc = d_in ? llz_stage_load((void *)d_in, in, ib, in_dev, f->stream) : LLZ_ERR_NOMEM;
     }
-    if (rc == LLZ_OK && !out_dev) {
+    if (rc == LLZ_OK && !out_place) {
         d_out = (float *)llz_stage_reserve(&f->st_out, ob);
         if (!d_out) rc = LLZ_ERR_NOMEM;
     }
     if (rc == LLZ_OK) rc = llzs_mdct4_f32(d_in, d_out, count, f->length, f->d_tc, f->d_ts, f->d_cs, inverse, f->stream);
-    if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, ob, f->stream);
+    if (rc == LLZ_OK && !out_place) rc = llz_stage_store(out, d_out, ob, out_dev, f->stream);
     llzs_device_leave(prev);
     return rc == LLZ_OK ? count : rc;
 }

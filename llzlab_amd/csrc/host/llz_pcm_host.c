@@ -2,7 +2,7 @@
 #include "../../../include/llz_pcm.h"
 #include "llz_host.h"
 
-static int pcm_run(int deint, const void *in, void *out, int channels, long n, float scale, void *stream)
+static int pcm_run(const char *who, int deint, const void *in, void *out, int channels, long n, float scale, void *stream)
 {
     if (!in || !out || channels < 1 || n < 1) {
         llzs_set_error("llz_pcm_*: bad arguments");
@@ -13,6 +13,7 @@ static int pcm_run(int deint, const void *in, void *out, int channels, long n, f
     const size_t out_bytes = count * (deint ? sizeof(float) : sizeof(short));
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* device memory of a GPU that is not current */
+    if (llz_refuse_device_overlap(who, "in", in, in_bytes, in_dev, "out", out, out_bytes, out_dev)) return LLZ_ERR_ARG;
     void *d_in = (void *)in, *d_out = out;
     int rc = LLZ_OK;
     if (!in_dev) {
@@ -34,10 +35,10 @@ static int pcm_run(int deint, const void *in, void *out, int channels, long n, f
 
 int llz_pcm_deinterleave_i16_f32(const short *in, float *out, int channels, long n, float scale, void *stream)
 {
-    return pcm_run(1, in, out, channels, n, scale, stream);
+    return pcm_run("llz_pcm_deinterleave_i16_f32", 1, in, out, channels, n, scale, stream);
 }
 
 int llz_pcm_interleave_f32_i16(const float *in, short *out, int channels, long n, float scale, void *stream)
 {
-    return pcm_run(0, in, out, channels, n, scale, stream);
+    return pcm_run("llz_pcm_interleave_f32_i16", 0, in, out, channels, n, scale, stream);
 }

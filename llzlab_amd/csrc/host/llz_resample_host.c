@@ -700,6 +700,7 @@ static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_i
     const size_t out_bytes = sb * (size_t)r->channels * (size_t)n_out;
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
+    if (llz_refuse_device_overlap("llz_resample_mc", "in", in, in_bytes, in_dev, "out", out, out_bytes, out_dev)) return LLZ_ERR_ARG;
     const void *d_in = in;
     void *d_out = out;
     int rc = LLZ_OK;

@@ -218,7 +218,7 @@ k_synth_f32(float *__restrict__ dst, long n, long pitch, uint32_t seed, int chan
         uint32_t u = llz_synth_u32(seed, (uint32_t)(c + chan0), (uint32_t)(i0 + j));
         v[j] = (float)(u >> 8) * (1.0f / 8388608.0f) - 1.0f;
     }
-    if (i0 + 4 <= n && ((pitch & 3) == 0)) {
+    if (i0 + 4 <= n && ((pitch & 3) == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
         *reinterpret_cast<float4 *>(row + i0) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
         for (int j = 0; j < 4 && i0 + j < n; j++) row[i0 + j] = v[j];
@@ -238,7 +238,7 @@ k_synth_i16(short *__restrict__ dst, long n, long pitch, uint32_t seed, int chan
         uint32_t u = llz_synth_u32(seed, (uint32_t)(c + chan0), (uint32_t)(i0 + j));
         v[j] = (short)((int32_t)(u >> 17) - 16384);
     }
-    if (i0 + 4 <= n && ((pitch & 3) == 0)) {
+    if (i0 + 4 <= n && ((pitch & 3) == 0) && ((reinterpret_cast<uintptr_t>(dst) & 7) == 0)) {
         *reinterpret_cast<short4 *>(row + i0) = make_short4(v[0], v[1], v[2], v[3]);
     } else {
         for (int j = 0; j < 4 && i0 + j < n; j++) row[i0 + j] = v[j];

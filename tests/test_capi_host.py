@@ -112,3 +112,30 @@ def test_argument_errors_are_reported_not_fatal(L):
     assert L.llz_get_resample_framelen_bytes(capi.BAD_HANDLE) < 0
     L.llz_fir_filter_uninit(capi.BAD_HANDLE)                                   # harmless
     L.llz_fft_uninit(0)
+
+
+def test_range_and_alignment_helpers_of_the_host_layer(L):
+    """llz_ranges_intersect / llz_refuse_device_overlap / llz_in_place (llz_host.h): what every out-of-place batch entry point
+    decides its aliasing refusal on, and the register transforms their staging of under-aligned device buffers"""
+    vp, sz = C.c_void_p, C.c_size_t
+    L.llz_ranges_intersect.restype, L.llz_ranges_intersect.argtypes = C.c_int, [vp, sz, vp, sz]
+    hit = lambda a, na, b, nb: L.llz_ranges_intersect(a, na, b, nb)  # noqa: E731
+    base = 1 << 20
+    assert hit(base, 64, base, 64) == 1                                   # exact alias
+    assert hit(base, 64, base + 4, 64) == 1 and hit(base + 4, 64, base, 64) == 1
+    assert hit(base, 64, base + 63, 1) == 1 and hit(base + 63, 1, base, 64) == 1
+    assert hit(base, 64, base + 64, 64) == 0 and hit(base + 64, 64, base, 64) == 0     # back to back: no byte shared
+    assert hit(base, 4096, base + 100, 4) == 1 and hit(base + 100, 4, base, 4096) == 1  # one inside the other
+    assert hit(base, 0, base, 64) == 0 and hit(base, 64, base + 8, 0) == 0             # an empty range shares nothing
+    top = (1 << 64) - 64
+    assert hit(top, 64, top - 64, 64) == 0 and hit(top, 64, top - 64, 65) == 1         # no wrap-around at the top of the space
+    refuse = L.llz_refuse_device_overlap
+    refuse.restype, refuse.argtypes = C.c_int, [C.c_char_p, C.c_char_p, vp, sz, C.c_int, C.c_char_p, vp, sz, C.c_int]
+    assert refuse(b"llz_some_entry", b"x", base, 64, 1, b"y", base + 60, 64, 1) == -1
+    assert capi.last_error() == "llz_some_entry: y may not overlap x (device memory)"
+    assert refuse(b"e", b"x", base, 64, 1, b"y", base + 64, 64, 1) == 0                 # disjoint
+    assert refuse(b"e", b"x", base, 64, 0, b"y", base, 64, 1) == 0                      # a host buffer is staged: never refused here
+    assert refuse(b"e", b"x", base, 64, 1, b"y", base, 64, 0) == 0 and refuse(b"e", b"x", base, 64, 0, b"y", base, 64, 0) == 0
+    L.llz_in_place.restype, L.llz_in_place.argtypes = C.c_int, [vp, C.c_int]
+    assert [L.llz_in_place(base + k, 1) for k in (0, 4, 8, 16)] == [1, 0, 0, 1]
+    assert L.llz_in_place(base, 0) == 0 and L.llz_in_place(base, -1) == 0

@@ -761,12 +761,12 @@ def test_correlation_reference_symbols_exact(dev):
                                         (6, 61, 24), (40, 2048, 25), (3, 10, 9), (2, 4096, 32)])
 def test_autocorr_mc_direct_vs_oracle(dev, oracle, frames, n, p):
     x = oracle.synth_f32(frames, n, seed=n + p)
-    ref = np.stack([oracle.autocorr(row.astype(np.float64), p) for row in x[:64]])
+    ref = np.stack([oracle.autocorr(row.astype(np.float64), p) for row in x])     # every frame, the partial last workgroup too
     xd = torch.from_numpy(x).to(dev)
     rd = torch.empty(frames, p + 1, dtype=torch.float32, device=dev)
     filters.autocorr_mc(xd, rd, p)
     got = rd.cpu().numpy().astype(np.float64)
-    assert np.max(np.abs(got[:64] - ref)) <= 1e-5 * ref[:, 0].max()    # relative to the zero-lag energy
+    assert np.max(np.abs(got - ref)) <= 1e-5 * ref[:, 0].max()         # relative to the zero-lag energy
     if p <= 32:
         # the LDS-window kernel (every p) must agree with the register form on every frame
         with capi.tuned(acf_lds=1):
