@@ -7,6 +7,7 @@
  * reference CPU path for identical taps).
  * Part 2 is the multi-channel float32 batch extension of the same init / process / flush / uninit shape
  *  -- the path the MI355X kernels are built for.
+ * Part 3 is the same batch with a tap set per channel: the filter bank.
  */
 #ifndef LLZ_FIR_H
 #define LLZ_FIR_H
@@ -94,6 +95,31 @@ int llz_fir_filter_mc_flt_len(unsigned long handle);
 int llz_fir_filter_mc_algo(unsigned long handle);
 /* stream: a hipStream_t passed as void* (NULL = default stream) */
 int llz_fir_filter_mc_set_stream(unsigned long handle, void *stream);
+
+/* ---- Part 3: the filter bank -- the batch of part 2 with one tap set PER CHANNEL --------------------- */
+
+/* channels independent filters, one tap set EACH (equaliser and crossover banks, per-microphone calibration, HRTF sets,
+ * per-channel fractional delays).  taps: HOST pointer, planar [channels][flt_len] (the double variant rounds to float once).
+ * channels 1..65535.  algo: LLZ_FIR_ALGO_TIME (any flt_len the time-domain kernel holds), LLZ_FIR_ALGO_OVERLAP_SAVE
+ * (1024-point, 1..257 taps) or LLZ_FIR_ALGO_AUTO (time domain up to 32 taps, overlap-save for 33..257, time domain above);
+ * the matrix-core form and the longer transforms are not built for a bank and are refused.
+ * Returns (unsigned long)-1 on failure (llz_hip_last_error() says why). */
+unsigned long llz_fir_bank_mc_init(int channels, int frame_len, const float *taps, int flt_len, int algo);
+unsigned long llz_fir_bank_mc_init_f64taps(int channels, int frame_len, const double *taps, int flt_len, int algo);
+void          llz_fir_bank_mc_uninit(unsigned long handle);
+/* the contract of llz_fir_filter_mc / llz_fir_filter_mc_flush: planar [channels][frame_len] float32, device memory (in
+ * place, asynchronous on the handle's stream) or host memory (staged, synchronous), frame_len as at init, out may not
+ * alias or overlap in (LLZ_ERR_ARG), flt_len-1 samples of history per channel carried from call to call; the flush
+ * writes [channels][flt_len-1] */
+int llz_fir_bank_mc(unsigned long handle, const float *in, float *out, int frame_len);
+int llz_fir_bank_mc_flush(unsigned long handle, float *out);
+/* replace the taps of channels [first, first+count) between calls; taps: HOST [count][flt_len], flt_len as at init.
+ * Ordered on the handle's stream after the calls already issued; the history is kept: the next call filters
+ * concat(history, frame) with the new taps.  A range outside [0, channels) is refused with LLZ_ERR_ARG. */
+int llz_fir_bank_mc_set_taps(unsigned long handle, int first, int count, const float *taps);
+int llz_fir_bank_mc_flt_len(unsigned long handle);
+int llz_fir_bank_mc_algo(unsigned long handle);
+int llz_fir_bank_mc_set_stream(unsigned long handle, void *stream);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,16 @@ def lib():
     sig("llz_fir_filter_mc_flt_len", i, ul)
     sig("llz_fir_filter_mc_algo", i, ul)
     sig("llz_fir_filter_mc_set_stream", i, ul, vp)
+    # llz_fir.h part 3
+    sig("llz_fir_bank_mc_init", ul, i, i, vp, i, i)
+    sig("llz_fir_bank_mc_init_f64taps", ul, i, i, vp, i, i)
+    sig("llz_fir_bank_mc_uninit", None, ul)
+    sig("llz_fir_bank_mc", i, ul, vp, vp, i)
+    sig("llz_fir_bank_mc_flush", i, ul, vp)
+    sig("llz_fir_bank_mc_set_taps", i, ul, i, i, vp)
+    sig("llz_fir_bank_mc_flt_len", i, ul)
+    sig("llz_fir_bank_mc_algo", i, ul)
+    sig("llz_fir_bank_mc_set_stream", i, ul, vp)
     # llz_iir.h
     sig("llz_iir_filter_init", ul, i, dp, i, dp)
     sig("llz_iir_filter_uninit", None, ul)

@@ -143,11 +143,13 @@ int llz_fir_filter_flush(unsigned long handle, double *buf_out)
  * ===================================================================================================== */
 
 typedef struct {
-    int tag;
+    int tag;                    /* LLZ_TAG_FIRM: one tap set for every channel; LLZ_TAG_FIRB: the filter bank of part 3 */
+    const char *who;            /* the process symbol's name, for messages */
     int device;                 /* the device the handle's buffers live on: every call binds it */
     int channels, frame_len, flt_len, algo;
-    float *d_taps;              /* flt_len floats zero-padded to a multiple of 16 */
-    llzs_ols_tables ols;        /* overlap-save tables (all NULL for the time-domain algorithms) */
+    float *d_taps;              /* flt_len floats zero-padded to a multiple of 16; a bank: [channels] such rows */
+    llzs_ols_tables ols;        /* overlap-save tables (all NULL for the time-domain algorithms); a bank: twid alone */
+    float *d_hbank;             /* a bank on overlap-save: [channels][LLZS_BANK_PITCH] complex, bins 0..512 of each spectrum */
     float *d_hist[2];           /* [channels][flt_len-1], ping-pong */
     int cur;
     float *d_zero;              /* [channels][flt_len-1] zeros: flush input */
@@ -158,7 +160,7 @@ typedef struct {
 static void firm_destroy(firm_t *f)
 {
     if (!f) return;
-    llzs_free(f->d_taps); llzs_free(f->ols.hfreq); llzs_free(f->ols.twid); llzs_free(f->ols.tw2k); llzs_free(f->ols.tw4k);
+    llzs_free(f->d_taps); llzs_free(f->d_hbank); llzs_free(f->ols.hfreq); llzs_free(f->ols.twid); llzs_free(f->ols.tw2k); llzs_free(f->ols.tw4k);
     llzs_free(f->d_hist[0]); llzs_free(f->d_hist[1]); llzs_free(f->d_zero);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     f->tag = 0;
@@ -285,6 +287,7 @@ unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *t
     firm_t *f = (firm_t *)calloc(1, sizeof(*f));
     if (!f) return LLZ_BAD_HANDLE;
     f->tag = LLZ_TAG_FIRM;
+    f->who = "llz_fir_filter_mc";
     f->device = llzs_device_get();
     f->channels = channels; f->frame_len = frame_len; f->flt_len = flt_len; f->algo = algo;
 
@@ -398,7 +401,12 @@ static int firm_launch(firm_t *f, const float *d_in, float *d_out, int n, long p
     const float *hist = f->flt_len > 1 ? f->d_hist[f->cur] : NULL;
     const struct firm_ols_rung *ols = firm_ols_rung(algo);
     int rc;
-    if (ols)
+    if (f->tag == LLZ_TAG_FIRB)
+        rc = ols ? llzs_fir_bank_ols_f32(f->d_hbank, f->ols.twid, d_in, d_out, hist, f->channels, n, pitch_in, pitch_out,
+                                         f->flt_len, f->stream)
+                 : llzs_fir_td_bank_f32(d_in, d_out, hist, f->d_taps, f->channels, n, pitch_in, pitch_out, f->flt_len,
+                                        f->stream);
+    else if (ols)
         rc = llzs_fir_ols_f32(ols->nfft, &f->ols, d_in, d_out, hist, f->channels, n, pitch_in, pitch_out, f->flt_len,
                               f->stream);
     else if (algo == LLZ_FIR_ALGO_TIME_MFMA)
@@ -434,17 +442,17 @@ int llz_fir_filter_mc(unsigned long handle, const float *in, float *out, int fra
 static int firm_process(firm_t *f, const float *in, float *out, int frame_len)
 {
     if (frame_len != f->frame_len) {
-        llzs_set_error("llz_fir_filter_mc: frame_len %d != init frame_len %d", frame_len, f->frame_len);
+        llzs_set_error("%s: frame_len %d != init frame_len %d", f->who, frame_len, f->frame_len);
         return LLZ_ERR_ARG;
     }
     if (in == out) {
-        llzs_set_error("llz_fir_filter_mc: in-place filtering is not supported");
+        llzs_set_error("%s: in-place filtering is not supported", f->who);
         return LLZ_ERR_ARG;
     }
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
-    if (llz_refuse_device_overlap("llz_fir_filter_mc", "in", in, bytes, in_dev, "out", out, bytes, out_dev)) return LLZ_ERR_ARG;
+    if (llz_refuse_device_overlap(f->who, "in", in, bytes, in_dev, "out", out, bytes, out_dev)) return LLZ_ERR_ARG;
     const float *d_in = in;
     float *d_out = out;
     int rc = LLZ_OK;
@@ -491,4 +499,230 @@ static int firm_flush(firm_t *f, float *out)
     int rc = firm_launch(f, f->d_zero, d_out, keep, keep, keep, LLZ_FIR_ALGO_TIME);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? keep : rc;
+}
+
+/* =====================================================================================================
+ * Part 3: the filter bank -- the batch of part 2 with a tap set per channel (kernels k_fir_td_f32<true> and K4c
+ * k_fir_bank_ols_f32).  A bank is a firm_t under its own tag: staging, history, tail update and flush are part 2's.
+ * ===================================================================================================== */
+
+enum { FIRB_N = 1024 };
+
+/* cos / sin of 2 pi i / 1024 with exact quadrant values, as firm_build_ols_tables makes them */
+static void firb_cs_table(double *cs)
+{
+    for (int i = 0; i < FIRB_N; i++) {
+        const double ang = 2.0 * M_PI * (double)i / (double)FIRB_N;
+        cs[2 * i] = (i == FIRB_N / 4 || i == 3 * FIRB_N / 4) ? 0.0 : cos(ang);
+        cs[2 * i + 1] = (i == 0 || i == FIRB_N / 2) ? 0.0 : sin(ang);
+    }
+}
+
+/* dst[0 .. 512] = DFT_1024(taps)[k] / 1024 as float pairs: a radix-2 transform in double (decimation in time, twiddles from
+ * the table), rounded once.  The direct DFT of firm_build_ols_tables costs 513 x flt_len terms per filter here: 4096 filters
+ * of 257 taps took 0.54 s of host time that way and 0.09 s this way, with every float32 entry equal in 256 random filters
+ * (profiles/fir_bank/time_fir_bank.txt).  z: 2 x 1024 doubles. */
+static void firb_spectrum(float *dst, const float *taps, int flt_len, const double *cs, double *z)
+{
+    for (int i = 0; i < FIRB_N; i++) {
+        int r = 0;
+        for (int b = 0; b < 10; b++) r |= ((i >> b) & 1) << (9 - b);
+        z[2 * r] = i < flt_len ? (double)taps[i] : 0.0;
+        z[2 * r + 1] = 0.0;
+    }
+    for (int half = 1; half < FIRB_N; half *= 2) {
+        const int step = FIRB_N / (2 * half);
+        for (int base = 0; base < FIRB_N; base += 2 * half)
+            for (int j = 0; j < half; j++) {
+                const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
+                double *a = z + 2 * (base + j), *b = a + 2 * half;
+                const double tr = b[0] * wr - b[1] * wi, ti = b[0] * wi + b[1] * wr;
+                b[0] = a[0] - tr; b[1] = a[1] - ti;
+                a[0] += tr; a[1] += ti;
+            }
+    }
+    for (int k = 0; k < LLZS_BANK_BINS; k++) {
+        dst[2 * k] = (float)(z[2 * k] / FIRB_N);
+        dst[2 * k + 1] = (float)(z[2 * k + 1] / FIRB_N);
+    }
+}
+
+/* build the table rows of channels [first, first + count) from taps [count][flt_len] and upload them: at init as tables
+ * (stream NULL), from set_taps on the handle's stream behind the calls already issued */
+static int firb_load_rows(firm_t *f, int first, int count, const float *taps, int at_init)
+{
+    const int tpad = (f->flt_len + 15) & ~15;
+    const size_t tbytes = sizeof(float) * (size_t)count * (size_t)tpad;
+    const size_t hbytes = f->d_hbank ? sizeof(float) * 2 * (size_t)count * LLZS_BANK_PITCH : 0;
+    float *pt = (float *)calloc((size_t)count * (size_t)tpad, sizeof(float));
+    float *hb = hbytes ? (float *)calloc((size_t)count * LLZS_BANK_PITCH * 2, sizeof(float)) : NULL;
+    double *work = hbytes ? (double *)malloc(sizeof(double) * 4 * FIRB_N) : NULL;
+    int rc = (pt && (!hbytes || (hb && work))) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {
+        if (hbytes) firb_cs_table(work + 2 * FIRB_N);
+        for (int c = 0; c < count; c++) {
+            const float *row = taps + (size_t)c * (size_t)f->flt_len;
+            memcpy(pt + (size_t)c * (size_t)tpad, row, sizeof(float) * (size_t)f->flt_len);
+            if (hbytes) firb_spectrum(hb + (size_t)c * LLZS_BANK_PITCH * 2, row, f->flt_len, work + 2 * FIRB_N, work);
+        }
+        float *d_t = f->d_taps + (size_t)first * (size_t)tpad;
+        float *d_h = hbytes ? f->d_hbank + (size_t)first * LLZS_BANK_PITCH * 2 : NULL;
+        rc = at_init ? llzs_h2d_table(d_t, pt, tbytes) : llzs_h2d(d_t, pt, tbytes, f->stream);
+        if (rc == LLZ_OK && hbytes) rc = at_init ? llzs_h2d_table(d_h, hb, hbytes) : llzs_h2d(d_h, hb, hbytes, f->stream);
+    }
+    free(pt); free(hb); free(work);
+    return rc;
+}
+
+unsigned long llz_fir_bank_mc_init(int channels, int frame_len, const float *taps, int flt_len, int algo)
+{
+    if (channels < 1 || channels > 65535 || frame_len < 1 || !taps || flt_len < 1) {
+        llzs_set_error("llz_fir_bank_mc_init: channels %d frame_len %d flt_len %d%s", channels, frame_len, flt_len,
+                       taps ? "" : ", no taps");
+        return LLZ_BAD_HANDLE;
+    }
+    if (!llzs_fir_td_f32_fits(flt_len)) {
+        llzs_set_error("llz_fir_bank_mc_init: %d taps exceed the time-domain kernel's LDS tile", flt_len);
+        return LLZ_BAD_HANDLE;
+    }
+    /* AUTO: the crossover of the shared form, confirmed for the bank on 4096 ch x 2^20 (tools/time_fir_bank.py,
+     * profiles/fir_bank/time_fir_bank.txt, runs A / B): time domain 5.97 / 6.17 ms at 9 taps, 6.48 / 6.58 at 32, 8.03 / 8.07 at
+     * 33 (K1 pads to 48) and 9.72 / 9.96 at 63, overlap-save 6.47 / 6.70 ms at every length up to 257 */
+    if (algo == LLZ_FIR_ALGO_AUTO) algo = (flt_len > 32 && flt_len <= 257) ? LLZ_FIR_ALGO_OVERLAP_SAVE : LLZ_FIR_ALGO_TIME;
+    if (algo != LLZ_FIR_ALGO_TIME && algo != LLZ_FIR_ALGO_OVERLAP_SAVE) {
+        llzs_set_error("llz_fir_bank_mc_init: algo %d is not built for a bank; accepted: LLZ_FIR_ALGO_AUTO (0), LLZ_FIR_ALGO_TIME "
+                       "(1), LLZ_FIR_ALGO_OVERLAP_SAVE (2, 1..257 taps)", algo);
+        return LLZ_BAD_HANDLE;
+    }
+    if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE && flt_len > 257) {
+        llzs_set_error("llz_fir_bank_mc_init: the 1024-point overlap-save takes 1..257 taps, not %d (LLZ_FIR_ALGO_TIME does)",
+                       flt_len);
+        return LLZ_BAD_HANDLE;
+    }
+    firm_t *f = (firm_t *)calloc(1, sizeof(*f));
+    if (!f) return LLZ_BAD_HANDLE;
+    f->tag = LLZ_TAG_FIRB;
+    f->who = "llz_fir_bank_mc";
+    f->device = llzs_device_get();
+    f->channels = channels; f->frame_len = frame_len; f->flt_len = flt_len; f->algo = algo;
+
+    const int tpad = (flt_len + 15) & ~15;
+    const size_t hist_bytes = sizeof(float) * (size_t)channels * (size_t)(flt_len > 1 ? flt_len - 1 : 1);
+    int rc = LLZ_OK;
+    f->d_taps = (float *)llzs_malloc(sizeof(float) * (size_t)channels * (size_t)tpad);
+    f->d_hist[0] = (float *)llzs_malloc(hist_bytes);
+    f->d_hist[1] = (float *)llzs_malloc(hist_bytes);
+    f->d_zero = (float *)llzs_malloc(hist_bytes);
+    if (!f->d_taps || !f->d_hist[0] || !f->d_hist[1] || !f->d_zero) rc = LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_OVERLAP_SAVE) {
+        f->d_hbank = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)channels * LLZS_BANK_PITCH);
+        f->ols.twid = (float *)llzs_malloc(sizeof(float) * 2 * 1024);
+        double *cs = (double *)malloc(sizeof(double) * 2 * FIRB_N);
+        float *tw = (float *)malloc(sizeof(float) * 2 * 1024);
+        if (!f->d_hbank || !f->ols.twid || !cs || !tw) rc = LLZ_ERR_NOMEM;
+        if (rc == LLZ_OK) {
+            firb_cs_table(cs);
+            for (int a = 0; a < 32; a++)
+                for (int b = 0; b < 32; b++) firm_w(&tw[2 * (a * 32 + b)], cs, (a * b) % FIRB_N);
+            rc = llzs_h2d_table(f->ols.twid, tw, sizeof(float) * 2 * 1024);
+        }
+        free(cs); free(tw);
+    }
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[0], 0, hist_bytes, NULL);
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[1], 0, hist_bytes, NULL);
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_zero, 0, hist_bytes, NULL);
+    if (rc == LLZ_OK) rc = firb_load_rows(f, 0, channels, taps, 1);
+    if (rc == LLZ_OK) rc = llzs_sync(NULL);
+    if (rc != LLZ_OK) {
+        firm_destroy(f);
+        return LLZ_BAD_HANDLE;
+    }
+    return (unsigned long)f;
+}
+
+unsigned long llz_fir_bank_mc_init_f64taps(int channels, int frame_len, const double *taps, int flt_len, int algo)
+{
+    if (!taps || flt_len < 1 || channels < 1 || channels > 65535) {
+        llzs_set_error("llz_fir_bank_mc_init_f64taps: channels %d flt_len %d%s", channels, flt_len, taps ? "" : ", no taps");
+        return LLZ_BAD_HANDLE;
+    }
+    const size_t count = (size_t)channels * (size_t)flt_len;
+    float *t = (float *)malloc(sizeof(float) * count);
+    if (!t) return LLZ_BAD_HANDLE;
+    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
+    unsigned long h = llz_fir_bank_mc_init(channels, frame_len, t, flt_len, algo);
+    free(t);
+    return h;
+}
+
+void llz_fir_bank_mc_uninit(unsigned long handle)
+{
+    if (LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB)) {
+        firm_t *f = (firm_t *)handle;
+        const int prev = llzs_device_enter(f->device);
+        llzs_sync(f->stream);
+        firm_destroy(f);
+        llzs_device_leave(prev);
+    }
+}
+
+int llz_fir_bank_mc(unsigned long handle, const float *in, float *out, int frame_len)
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB) || !in || !out) {
+        llzs_set_error("llz_fir_bank_mc: bad handle or NULL buffer");
+        return LLZ_ERR_ARG;
+    }
+    firm_t *f = (firm_t *)handle;
+    const int prev = llzs_device_enter(f->device);
+    const int rc = firm_process(f, in, out, frame_len);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_fir_bank_mc_flush(unsigned long handle, float *out)
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB) || !out) {
+        llzs_set_error("llz_fir_bank_mc_flush: bad handle or NULL buffer");
+        return LLZ_ERR_ARG;
+    }
+    firm_t *f = (firm_t *)handle;
+    const int prev = llzs_device_enter(f->device);
+    const int rc = firm_flush(f, out);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_fir_bank_mc_set_taps(unsigned long handle, int first, int count, const float *taps)
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB) || !taps) {
+        llzs_set_error("llz_fir_bank_mc_set_taps: bad handle or NULL taps");
+        return LLZ_ERR_ARG;
+    }
+    firm_t *f = (firm_t *)handle;
+    if (first < 0 || count < 1 || first >= f->channels || count > f->channels - first) {
+        llzs_set_error("llz_fir_bank_mc_set_taps: channels [%d, %d + %d) outside the bank's [0, %d)", first, first, count,
+                       f->channels);
+        return LLZ_ERR_ARG;
+    }
+    const int prev = llzs_device_enter(f->device);
+    const int rc = firb_load_rows(f, first, count, taps, 0);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_fir_bank_mc_flt_len(unsigned long handle)
+{
+    return LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB) ? ((firm_t *)handle)->flt_len : LLZ_ERR_ARG;
+}
+
+int llz_fir_bank_mc_algo(unsigned long handle)
+{
+    return LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB) ? ((firm_t *)handle)->algo : LLZ_ERR_ARG;
+}
+
+int llz_fir_bank_mc_set_stream(unsigned long handle, void *stream)
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB)) return LLZ_ERR_ARG;
+    ((firm_t *)handle)->stream = stream;
+    return LLZ_OK;
 }

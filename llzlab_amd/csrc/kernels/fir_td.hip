@@ -24,12 +24,19 @@ constexpr int TD_TILE = TD_R * TD_THREADS; // 2048 outputs per workgroup
 // addresses 12 dwords apart: conflict-free within each 16-lane service group (MI355X LDS: 64 banks for b128).
 __device__ __forceinline__ int td_phys(int p) { return p + ((p >> 3) << 2); }
 
+// BANK = false: one tap set for every channel (llz_fir_filter_mc).  BANK = true: the filter bank (llz_fir_bank_mc), channel c
+// filters with its own row taps[c][tpad] -- still wave-uniform, still through the scalar cache.  Two instances rather than a
+// tap pitch argument, so that the shared-taps instance keeps its arguments and its code (profiles/fir_bank/resource_usage.txt).
+// The bank instance lives here and not in fir_bank.hip because it needs this file's -fno-slp-vectorize (Makefile), which the
+// overlap-save kernels there must not get.
+template <bool BANK>
 __global__ void __launch_bounds__(TD_THREADS)
 k_fir_td_f32(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ hist,
              const float *__restrict__ taps, int n, long in_pitch, long out_pitch, int flt_len, int tpad)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int c = blockIdx.y;
+    if (BANK) taps += (size_t)c * tpad;
     const int tile0 = blockIdx.x * TD_TILE;
     const int tid = threadIdx.x;
     const float *row = in + (size_t)c * in_pitch;
@@ -173,12 +180,36 @@ extern "C" int llzs_fir_td_f32(const float *in, float *out, const float *hist, c
         return LLZ_ERR_RANGE;
     }
     if (lds_bytes > 64 * 1024)
-        LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_td_f32),
+        LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_td_f32<false>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     dim3 grid((unsigned)((n + TD_TILE - 1) / TD_TILE), (unsigned)channels);
-    hipLaunchKernelGGL(k_fir_td_f32, grid, dim3(TD_THREADS), lds_bytes, as_stream(stream), in, out, hist,
+    hipLaunchKernelGGL(k_fir_td_f32<false>, grid, dim3(TD_THREADS), lds_bytes, as_stream(stream), in, out, hist,
                        taps_padded, n, in_pitch, out_pitch, flt_len, tpad);
     LLZ_LAUNCH_CHECK("k_fir_td_f32");
+    return LLZ_OK;
+}
+
+extern "C" int llzs_fir_td_bank_f32(const float *in, float *out, const float *hist, const float *taps_bank, int channels,
+                                    int n, long in_pitch, long out_pitch, int flt_len, void *stream)
+{
+    if (!in || !out || !taps_bank || channels <= 0 || n <= 0 || flt_len <= 0 || in_pitch < n || out_pitch < n ||
+        channels > 65535) {
+        llzs_set_error("fir_td_bank_f32: bad arguments (channels=%d n=%d flt_len=%d)", channels, n, flt_len);
+        return LLZ_ERR_ARG;
+    }
+    const int tpad = (flt_len + 15) & ~15;
+    const size_t lds_bytes = td_lds_bytes(flt_len);
+    if (lds_bytes > 160 * 1024) {
+        llzs_set_error("fir_td_bank_f32: %d taps need %zu B of LDS", flt_len, lds_bytes);
+        return LLZ_ERR_RANGE;
+    }
+    if (lds_bytes > 64 * 1024)
+        LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fir_td_f32<true>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    dim3 grid((unsigned)((n + TD_TILE - 1) / TD_TILE), (unsigned)channels);
+    hipLaunchKernelGGL(k_fir_td_f32<true>, grid, dim3(TD_THREADS), lds_bytes, as_stream(stream), in, out, hist, taps_bank, n,
+                       in_pitch, out_pitch, flt_len, tpad);
+    LLZ_LAUNCH_CHECK("k_fir_td_f32<bank>");
     return LLZ_OK;
 }
 

@@ -56,6 +56,8 @@ enum {
     LLZS_TUNE_ACF_LDS,              /* 1: direct autocorrelation always on the LDS-window kernel (no register form for p <= 32) */
     LLZS_TUNE_STFT_FULL,            /* 1: STFT synthesis frames of 512 / 2048 points on the full-size complex inverse transform */
     LLZS_TUNE_LPC_SPLIT,            /* 1: batch LPC with p <= 32 as two launches (correlation, then recursion) like p > 32 */
+    LLZS_TUNE_BANK_GLOBAL_H,        /* 1: filter-bank overlap-save reads each spectrum bin from global memory per job (the form
+                                     * measured against and dropped: fir_bank.hip) instead of a half-wave's own LDS image */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -98,6 +100,9 @@ int  llzs_tables_broadcast_ranks(void);     /* ranks of the RCCL communicator th
 int llzs_fir_td_f32(const float *in, float *out, const float *hist, const float *taps_padded,
                     int channels, int n, long in_pitch, long out_pitch, int flt_len, void *stream);
 int llzs_fir_td_f32_fits(int flt_len);      /* 1 when the taps fit the time-domain kernel's LDS tile */
+/* the filter bank: the same with a tap row per channel, taps_bank = [channels][tpad], tpad = flt_len rounded up to 16 */
+int llzs_fir_td_bank_f32(const float *in, float *out, const float *hist, const float *taps_bank, int channels, int n,
+                         long in_pitch, long out_pitch, int flt_len, void *stream);
 /* overlap-save with nfft = 1024, 2048, 4096 or 8192 points (fir_ols.hip): 1..257, 2..1025, 2..3073 or 2..6145 taps.  The
  * tables, all complex floats: hfreq = DFT_nfft(taps) / nfft as P = nfft / 1024 planes of 1024 (bin k in plane k mod P, row
  * k / P; P = 1 is natural order), twid = [32][32] W_1024^(ab), tw2k = [1024] W_2048^n (2048 and 4096 points, else NULL),
@@ -107,6 +112,13 @@ typedef struct {
 } llzs_ols_tables;
 int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float *in, float *out, const float *hist, int channels,
                      int n, long in_pitch, long out_pitch, int flt_len, void *stream);
+/* 1024-point overlap-save with a spectrum per channel (fir_bank.hip), 1..257 taps: hbank = [channels][LLZS_BANK_PITCH] complex
+ * floats, row c = bins 0..512 of DFT_1024(taps of channel c) / 1024 (the taps are real: the kernel mirrors the rest), the
+ * row's tail unused; twid as above */
+#define LLZS_BANK_BINS 513
+#define LLZS_BANK_PITCH 520
+int llzs_fir_bank_ols_f32(const float *hbank, const float *twid, const float *in, float *out, const float *hist, int channels,
+                          int n, long in_pitch, long out_pitch, int flt_len, void *stream);
 /* time domain on the fp32 matrix cores (v_mfma_f32_16x16x4_f32), with optional decimation:
  * y[c][i] = gain * sum_{k<T} taps[k] * x[c][i*M - k], x[c][<0] = hist[c][T-1+idx] (hist NULL = zeros); n_out outputs
  * per channel from n_in inputs, (n_out-1)*M < n_in.  taps: T floats (no padding needed). */

@@ -164,6 +164,55 @@ class FirFilterMC:
     __del__ = close
 
 
+class FirBankMC:
+    """channels x frame_len float32, planar, one tap set per channel: llz_fir_bank_mc_*.  taps: [channels, flt_len]."""
+
+    def __init__(self, channels, frame_len, taps, algo=FIR_ALGO_AUTO, stream=None):
+        self._L = capi.lib()
+        taps = _f64(taps)
+        if taps.ndim != 2 or taps.shape[0] != channels or taps.shape[1] < 1:
+            raise LlzError(f"FirBankMC: taps must be [channels = {channels}, flt_len], got {taps.shape} "
+                           "(one tap set for every channel is FirFilterMC)")
+        self.handle = check_handle(
+            self._L.llz_fir_bank_mc_init_f64taps(channels, frame_len, taps.ctypes.data, taps.shape[1], algo),
+            "llz_fir_bank_mc_init")
+        self.channels, self.frame_len, self.flt_len = channels, frame_len, taps.shape[1]
+        self.algo = self._L.llz_fir_bank_mc_algo(self.handle)
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_fir_bank_mc_set_stream(self.handle, _stream_ptr(stream)), "set_stream")
+
+    def set_taps(self, first, taps):
+        """replace the taps of channels first .. first + len(taps) - 1; taps: [count, flt_len]"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        if taps.ndim != 2 or taps.shape[1] != self.flt_len:
+            raise LlzError(f"FirBankMC.set_taps: taps must be [count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_fir_bank_mc_set_taps(self.handle, first, taps.shape[0], taps.ctypes.data),
+              "llz_fir_bank_mc_set_taps")
+
+    def filter(self, x, out):
+        """x, out: [channels, frame_len] float32 (torch device tensors or numpy). Returns out."""
+        count = self.channels * self.frame_len
+        check(self._L.llz_fir_bank_mc(self.handle, _typed(x, "float32", count, "FirBankMC.filter x"),
+                                      _typed(out, "float32", count, "FirBankMC.filter out"), self.frame_len),
+              "llz_fir_bank_mc")
+        return out
+
+    def flush(self, out):
+        check(self._L.llz_fir_bank_mc_flush(self.handle, _typed(out, "float32", self.channels * (self.flt_len - 1),
+                                                                "FirBankMC.flush out")), "llz_fir_bank_mc_flush")
+        return out
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_fir_bank_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
