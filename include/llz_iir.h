@@ -32,6 +32,18 @@ int           llz_iir_cascade_mc_set_stream(unsigned long handle, void *stream);
 /* working precision of the pipelined kernel for this coefficient set: 64, or 32 when every section's rounding-noise gain
  * (sum of squares of the impulse response of 1/A(z), measured at init) is at most 16 -- poles of radius up to about 0.8 */
 int           llz_iir_cascade_mc_precision(unsigned long handle);
+/* what a call with this frame_len would run as, under the current llz_hip_tune settings: out = {form, precision, segs,
+ * seg_chunks, warm} for the launch that takes the frame's whole chunks -- form one of LLZ_IIR_FORM_* (chunks of 1024, 1024,
+ * 2048 samples), precision 32 or 64, segs time segments per channel of seg_chunks chunks (the last may be shorter), a later
+ * one started warm chunks early from the zero state; chunks of the form's own size.  The rest of the frame (with WAVE32 an
+ * odd 1024-sample chunk, then up to 1023 samples through the per-channel kernel) runs as one segment.  Computed by the
+ * functions the call itself plans with; launches nothing and reads no device memory.  Assumes 16-byte aligned rows, as
+ * every frame_len % 4 == 0 of an aligned buffer gives; a frame without a whole chunk reports segs = seg_chunks = warm = 0.
+ * Returns 0 or LLZ_ERR_ARG. */
+#define LLZ_IIR_FORM_PIPE   0   /* the stage pipeline */
+#define LLZ_IIR_FORM_WAVE16 1   /* a wave per (channel, segment), 16 samples per lane */
+#define LLZ_IIR_FORM_WAVE32 2   /* the same with 32 samples per lane */
+int           llz_iir_cascade_mc_plan(unsigned long handle, int frame_len, int out[5]);
 
 /* ---- Part 3: multi-channel GENERAL direct form I -- llz_iir_filter itself for many channels (llz_iir.c:103-156): any pole
  * order M and zero order N up to 8 (the reference's only in-tree caller uses order 3: libllzaudio/llz_musicpitch.c:1277-1285),
@@ -50,6 +62,9 @@ void          llz_iir_mc_uninit(unsigned long handle);
  * opts out: one segment per channel, bit for bit the reference's sequence rounded once.
  * out may not overlap in (device memory), and x == y is refused for host memory too: LLZ_ERR_ARG. */
 int           llz_iir_mc(unsigned long handle, const float *x, float *y, int frame_len);
+/* the number of time segments per channel a call with this frame_len would run with, under the current llz_hip_tune
+ * settings (the launch's own computation; nothing is launched): segments of ceil(frame_len / segments) samples */
+int           llz_iir_mc_segments(unsigned long handle, int frame_len);
 int           llz_iir_mc_flush(unsigned long handle, float *y);         /* N more samples of x = 0 per channel: [channels][N]; returns N */
 int           llz_iir_mc_set_stream(unsigned long handle, void *stream);
 

@@ -156,6 +156,7 @@ def lib():
     sig("llz_iir_cascade_mc", i, ul, vp, vp, i)
     sig("llz_iir_cascade_mc_set_stream", i, ul, vp)
     sig("llz_iir_cascade_mc_precision", i, ul)
+    sig("llz_iir_cascade_mc_plan", i, ul, i, C.POINTER(C.c_int))
     # llz_resample.h
     sig("llz_decimate_init", ul, i, d, i)
     sig("llz_decimate_uninit", None, ul)
@@ -228,6 +229,7 @@ def lib():
     sig("llz_iir_mc_uninit", None, ul)
     sig("llz_iir_mc", i, ul, vp, vp, i)
     sig("llz_iir_mc_flush", i, ul, vp)
+    sig("llz_iir_mc_segments", i, ul, i)
     sig("llz_iir_mc_set_stream", i, ul, vp)
     sig("llz_mdct_frames_mc_init", ul, i, i, i)
     sig("llz_mdct_frames_mc_uninit", None, ul)

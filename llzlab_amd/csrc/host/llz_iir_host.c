@@ -465,6 +465,41 @@ static int iirm_path(const iirm_t *f, int n_fast)
     return (f->wave[w32].pl && n_fast >= LLZS_IIR_WAVE_CHUNK(w32)) ? w32 : w16;
 }
 
+/* The frame's main launch: the path's kernel and the samples it takes of the n_fast in whole 1024-sample chunks (a 32-sample
+ * form: the whole 2048-sample chunks).  The call and the plan query both start here. */
+static int iirm_main_launch(const iirm_t *f, int n_fast, int *n)
+{
+    const int path = iirm_path(f, n_fast);
+    *n = path >= LLZS_IIR_WAVE32_F32 ? n_fast - n_fast % LLZS_IIR_WAVE_CHUNK(path) : n_fast;
+    return path;
+}
+
+/* the samples of a frame that whole 1024-sample chunks take, given rows the chunked kernels can read (16-byte aligned) */
+static int iirm_fast_samples(int frame_len, int rows_aligned)
+{
+    return (rows_aligned && frame_len % 4 == 0) ? frame_len - frame_len % LLZS_IIR_PIPE_CHUNK : 0;
+}
+
+int llz_iir_cascade_mc_plan(unsigned long handle, int frame_len, int out[5])
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRM) || !out || frame_len < 1) {
+        llzs_set_error("llz_iir_cascade_mc_plan: bad handle, NULL out or frame_len");
+        return LLZ_ERR_ARG;
+    }
+    const iirm_t *f = (const iirm_t *)handle;
+    int n = 0, p[3] = {0, 0, 0}, rc = LLZ_OK;
+    const int path = iirm_main_launch(f, iirm_fast_samples(frame_len, 1), &n);
+    if (n > 0) {
+        const int prev = llzs_device_enter(f->device);      /* a wave form's first choice asks how many waves this chip holds */
+        rc = llzs_iir_cascade_plan(path, f->channels, n, f->stages, f->warm_chunks, p);
+        llzs_device_leave(prev);
+    }
+    out[0] = path == IIRM_PIPE ? LLZ_IIR_FORM_PIPE : path >= LLZS_IIR_WAVE32_F32 ? LLZ_IIR_FORM_WAVE32 : LLZ_IIR_FORM_WAVE16;
+    out[1] = f->float32_ok ? 32 : 64;
+    out[2] = p[0]; out[3] = p[1]; out[4] = p[2];
+    return rc;
+}
+
 /* every launch reads d_state and writes d_state_alt (segments of one launch are not ordered), which then swap */
 static int iirm_launch(iirm_t *f, int path, const float *d_in, float *d_out, int n, int pitch)
 {
@@ -503,11 +538,10 @@ static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len)
     /* whole 1024-sample chunks go through the path's kernel (needs 16-byte aligned rows): with a 32-sample form the whole
      * 2048-sample chunks, then its 16-sample counterpart what is left; the ragged remainder through the one-lane-per-channel
      * kernel.  All read and write the same per-section state. */
-    const int aligned = (frame_len % 4 == 0) && (((size_t)d_in | (size_t)d_out) % 16 == 0);
-    const int n_fast = aligned ? frame_len - frame_len % LLZS_IIR_PIPE_CHUNK : 0;
-    int path = iirm_path(f, n_fast), done = 0;
+    const int n_fast = iirm_fast_samples(frame_len, ((size_t)d_in | (size_t)d_out) % 16 == 0);
+    int main_n = 0, done = 0, path = iirm_main_launch(f, n_fast, &main_n);
     if (rc == LLZ_OK && path >= LLZS_IIR_WAVE32_F32) {
-        done = n_fast - n_fast % LLZS_IIR_WAVE_CHUNK(path);
+        done = main_n;
         rc = iirm_launch(f, path, d_in, d_out, done, frame_len);
         path = path == LLZS_IIR_WAVE32_F32 ? LLZS_IIR_WAVE16_F32 : LLZS_IIR_WAVE16_F64;
     }
@@ -621,9 +655,10 @@ int llz_iir_mc_set_stream(unsigned long handle, void *stream)
     return LLZ_OK;
 }
 
-static int iirg_launch(iirg_t *f, const float *d_in, float *d_out, int n)
+/* time segments of an n-sample launch: enough (channel, segment) lanes to fill the chip (~64 K), each at least 8 x the filter's
+ * memory long; what the launcher is asked for */
+static int iirg_segs(const iirg_t *f, int n)
 {
-    /* time segments: enough (channel, segment) lanes to fill the chip (~64 K), each at least 8 x the filter's memory long */
     int segs = 1;
     if (f->warm > 0) {
         const int tune = llzs_tune(LLZS_TUNE_IIR_SEGS);
@@ -632,6 +667,22 @@ static int iirg_launch(iirg_t *f, const float *d_in, float *d_out, int n)
         segs = (int)(want < most ? want : most);
         if (segs < 1) segs = 1;
     }
+    return segs;
+}
+
+int llz_iir_mc_segments(unsigned long handle, int frame_len)
+{
+    if (!LLZ_HANDLE_OK(handle, iirg_t, LLZ_TAG_IIRG) || frame_len < 1) {
+        llzs_set_error("llz_iir_mc_segments: bad handle or frame_len %d", frame_len);
+        return LLZ_ERR_ARG;
+    }
+    const iirg_t *f = (const iirg_t *)handle;
+    return llzs_iir_df1_mc_segments(frame_len, iirg_segs(f, frame_len), f->warm);     /* the launcher's own last word */
+}
+
+static int iirg_launch(iirg_t *f, const float *d_in, float *d_out, int n)
+{
+    const int segs = iirg_segs(f, n);
     const int rc = llzs_iir_df1_mc_f32(d_in, d_out, f->d_ab, f->d_state[f->cur], f->d_state[f->cur ^ 1], f->channels, n, n, n,
                                        f->M, f->N, segs, f->warm, f->stream);
     if (rc == LLZ_OK) f->cur ^= 1;

@@ -1182,6 +1182,18 @@ static iir_plan iir_plan_of(int chunk, int nchunks, int warm_chunks, int segs, i
     return p;
 }
 
+// The stage pipeline's plan.  Time segments only when the channels alone leave most of the chip idle (fewer than two
+// workgroups per CU); the rest is the one plan.
+static iir_plan iir_pipe_plan(int channels, int nchunks, int warm_chunks)
+{
+    int first = 1;
+    if (warm_chunks > 0 && channels < 512) {
+        first = (512 + channels - 1) / channels;
+        if (first > 16) first = 16;
+    }
+    return iir_plan_of(LLZS_IIR_PIPE_CHUNK, nchunks, warm_chunks, first, llzs_tune(LLZS_TUNE_IIR_SEGS));
+}
+
 // pd: [stages][6][4] = P^(2^d) row major, P = A^16; pl: [stages][64][12] = P^lane, P^(lane%16+1), P^(lane%32+1).  n must be a multiple of 1024 and
 // the rows 16-byte aligned (pitches % 4 == 0); the caller runs the remainder through llzs_iir_cascade_f32.
 extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const double *coef, const double *pd,
@@ -1208,15 +1220,8 @@ extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const doub
             LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_iir_cascade_pipe<double, 16>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    // time segments: only when the channels alone leave most of the chip idle (fewer than two workgroups per CU); the rest
-    // is the one plan
     const int nchunks = n / chunk;
-    int first = 1;
-    if (warm_chunks > 0 && channels < 512) {
-        first = (512 + channels - 1) / channels;
-        if (first > 16) first = 16;
-    }
-    const iir_plan p = iir_plan_of(chunk, nchunks, warm_chunks, first, llzs_tune(LLZS_TUNE_IIR_SEGS));
+    const iir_plan p = iir_pipe_plan(channels, nchunks, warm_chunks);
     const int segs = p.segs, seg_chunks = p.seg_chunks, warm = p.warm;
     if (float32)
         hipLaunchKernelGGL((k_iir_cascade_pipe<float, 16>), dim3((unsigned)((long)channels * segs)), dim3(64 * stages), lds,
@@ -1279,6 +1284,33 @@ static long iir_wave_slots(int form, int stages)
     return slots;
 }
 
+// A wave form's plan: its first choice from the waves the chip holds of its kernel, then the one plan.
+static iir_plan iir_wave_plan(int form, int channels, int nchunks, int stages, int warm_chunks)
+{
+    const int chunk = 64 * IIR_WAVE_ROWS[form].run;
+    return iir_plan_of(chunk, nchunks, warm_chunks,
+                       iir_wave_first_segs(chunk, channels, nchunks, iir_wave_slots(form, stages)),
+                       llzs_tune(LLZS_TUNE_IIR_SEGS));
+}
+
+// What a launch of n samples would run as, without launching: out = {segments per channel, chunks per segment, warm-up
+// chunks}, chunks of the form's own size.  form < 0: the stage pipeline (llzs_iir_cascade_pipe_f32), else a wave form
+// (llzs_iir_cascade_wave).  The launchers call the same two functions.
+extern "C" int llzs_iir_cascade_plan(int form, int channels, int n, int stages, int warm_chunks, int out[3])
+{
+    const int chunk = form < 0 ? LLZS_IIR_PIPE_CHUNK : LLZS_IIR_WAVE_CHUNK(form);
+    if (form >= LLZS_IIR_WAVE_FORMS || !out || channels <= 0 || n <= 0 || (n % chunk) || stages < 1 ||
+        stages > (form < 0 ? 16 : 8) || (form >= 0 && warm_chunks < 1)) {
+        llzs_set_error("iir_cascade_plan: bad arguments (form=%d channels=%d n=%d in chunks of %d, stages=%d, warm_chunks=%d)",
+                       form, channels, n, chunk, stages, warm_chunks);
+        return LLZ_ERR_ARG;
+    }
+    const iir_plan p = form < 0 ? iir_pipe_plan(channels, n / chunk, warm_chunks)
+                                : iir_wave_plan(form, channels, n / chunk, stages, warm_chunks);
+    out[0] = p.segs; out[1] = p.seg_chunks; out[2] = p.warm;
+    return LLZ_OK;
+}
+
 static int iir_wave_check(int form, const llzs_iir_wave_tables *t, const float *in, float *out, const double *state_in,
                           double *state, int channels, int n, long in_pitch, long out_pitch, int stages, int warm_chunks)
 {
@@ -1310,9 +1342,7 @@ extern "C" int llzs_iir_cascade_wave(int form, const llzs_iir_wave_tables *t, co
     const void *kernel = row.kernel[stages - 1];
     const int chunk = 64 * row.run;
     int nchunks = n / chunk;
-    iir_plan p = iir_plan_of(chunk, nchunks, warm_chunks,
-                             iir_wave_first_segs(chunk, channels, nchunks, iir_wave_slots(form, stages)),
-                             llzs_tune(LLZS_TUNE_IIR_SEGS));
+    iir_plan p = iir_wave_plan(form, channels, nchunks, stages, warm_chunks);
     long items = (long)channels * p.segs;
     const void *t0 = row.cf_first ? t->cf : t->pd, *t1 = row.cf_first ? t->pd : t->pl, *t2 = row.cf_first ? t->pl : t->cf;
     float gain32 = (float)t->in_gain;

@@ -127,6 +127,17 @@ k_iir_df1_mc(const float *__restrict__ in, float *__restrict__ out, const double
 
 extern "C" int llzs_iir_df1_mc_max_order(void) { return DF1_MAX; }
 
+// the segment count a launch runs with: every segment non-empty and at least `warm` long (seg_len = ceil(n / segs))
+extern "C" int llzs_iir_df1_mc_segments(long n, int segs, int warm)
+{
+    long seg_len = (n + segs - 1) / segs;
+    while (segs > 1 && (seg_len < warm || (long)(segs - 1) * seg_len >= n)) {
+        segs--;
+        seg_len = (n + segs - 1) / segs;
+    }
+    return segs;
+}
+
 // ab: DF1_MAX + 1 doubles a[] then DF1_MAX + 1 doubles b[] (zero padded); state_in / state_out: [channels][2][DF1_MAX + 1],
 // two different buffers (segment 0 reads the start state while the last segment writes the end state); segs >= 1 time
 // segments per channel, each warmed up over `warm` samples (ignored when segs == 1)
@@ -139,11 +150,8 @@ extern "C" int llzs_iir_df1_mc_f32(const float *in, float *out, const double *ab
         llzs_set_error("iir_df1_mc_f32: bad arguments (channels=%d n=%ld M=%d N=%d segs=%d)", channels, n, M, N, segs);
         return LLZ_ERR_ARG;
     }
-    long seg_len = (n + segs - 1) / segs;
-    while (segs > 1 && (seg_len < warm || (long)(segs - 1) * seg_len >= n)) {       // every segment non-empty and >= warm
-        segs--;
-        seg_len = (n + segs - 1) / segs;
-    }
+    segs = llzs_iir_df1_mc_segments(n, segs, warm);
+    const long seg_len = (n + segs - 1) / segs;
     const long items = (long)channels * segs;
     // (ORD: the orders the unrolled loops run to; the tables keep the stride of DF1_MAX)
     if (M <= 4 && N <= 4)

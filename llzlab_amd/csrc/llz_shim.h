@@ -180,6 +180,9 @@ typedef struct {
 int llzs_iir_cascade_wave(int form, const llzs_iir_wave_tables *t, const float *in, float *out, const double *state_in,
                           double *state_out, int channels, int n, long in_pitch, long out_pitch, int stages, int warm_chunks,
                           void *stream);
+/* the plan such a launch of n samples would run with, nothing launched: form < 0 the stage pipeline, else a wave form;
+ * out = {segments per channel, chunks per segment, warm-up chunks} in chunks of the form's own size */
+int llzs_iir_cascade_plan(int form, int channels, int n, int stages, int warm_chunks, int out[3]);
 /* general direct form I, one channel, double, the reference's exact operation order (llz_iir.c:103-132).
  * xs: N+1 doubles, ys: M+1 doubles (delay lines, read and written) */
 int llzs_iir_df1_f64(const double *in, double *out, const double *a, const double *b, double *xs, double *ys,
@@ -191,6 +194,8 @@ int llzs_iir_df1_f64(const double *in, double *out, const double *a, const doubl
 int llzs_iir_df1_mc_f32(const float *in, float *out, const double *ab, const double *state_in, double *state_out, int channels,
                         long n, long in_pitch, long out_pitch, int M, int N, int segs, int warm, void *stream);
 int llzs_iir_df1_mc_max_order(void);
+/* the segment count llzs_iir_df1_mc_f32 runs with when asked for `segs` (every segment non-empty and at least `warm` long) */
+int llzs_iir_df1_mc_segments(long n, int segs, int warm);
 
 /* ---- resample ---- */
 /* y[c][i] = gain * sum_{k<Q} x[c][(i0+i)*M/L - k - in0] * g[(i0+i)%L][k], x before the call start comes from

@@ -249,6 +249,9 @@ class IirFilter:
     __del__ = close
 
 
+IIR_FORMS = ("pipe", "wave16", "wave32")      # LLZ_IIR_FORM_* (include/llz_iir.h)
+
+
 class IirCascadeMC:
     """channels x n float32 through a fused cascade of biquads; coef rows {b0,b1,b2,a0,a1,a2}."""
 
@@ -269,6 +272,14 @@ class IirCascadeMC:
                                          _typed(out, "float32", self.channels * n, "IirCascadeMC.filter out"), n),
               "llz_iir_cascade_mc")
         return out
+
+    def plan(self, n):
+        """what filter() would run a frame of n samples as, under the tunes set now (llz_iir_cascade_mc_plan; nothing is
+        launched): dict of form ("pipe" / "wave16" / "wave32"), chunk (its chunk in samples), precision, segs, seg_chunks, warm"""
+        out = (C.c_int * 5)()
+        check(self._L.llz_iir_cascade_mc_plan(self.handle, int(n), out), "llz_iir_cascade_mc_plan")
+        return {"form": IIR_FORMS[out[0]], "chunk": 2048 if out[0] == 2 else 1024, "precision": out[1], "segs": out[2],
+                "seg_chunks": out[3], "warm": out[4]}
 
     def close(self):
         if getattr(self, "handle", 0):
@@ -296,6 +307,10 @@ class IirMC:
         check(self._L.llz_iir_mc(self.handle, _typed(x, "float32", self.channels * n, "x"), _typed(out, "float32", self.channels * n, "y"), n),
               "llz_iir_mc")
         return out
+
+    def segments(self, n):
+        """time segments per channel filter() would run a frame of n samples with (llz_iir_mc_segments; nothing is launched)"""
+        return check(self._L.llz_iir_mc_segments(self.handle, int(n)), "llz_iir_mc_segments")
 
     def flush(self, out):
         """N more outputs per channel into out [channels][N] (N = 0: nothing to flush, out is not touched)"""

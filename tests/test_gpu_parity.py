@@ -591,6 +591,9 @@ def test_iir_cascade_low_q_float32_path(dev, oracle, radius, theta, channels, n)
     ref = oracle.iir_cascade_batch_f32(x, coef)
     f = filters.IirCascadeMC(channels, coef)
     assert f.precision == (64 if radius >= 0.9 else 32)
+    plan = f.plan(n)
+    assert plan["form"] == "pipe" and plan["precision"] == f.precision, plan
+    assert plan["segs"] >= 3 if channels == 2 else plan["segs"] == 1, plan          # 2 x 200 chunks: split along time
     outs = []
     for (o, e) in ((0, n), (n, n + 2048)):
         xi = torch.from_numpy(np.ascontiguousarray(x[:, o:e])).to(dev)
@@ -708,6 +711,8 @@ def test_iir_cascade_few_channels_split_along_time(dev, oracle):
     x = oracle.synth_f32(channels, n + 4096, seed=5)
     ref = oracle.iir_cascade_batch_f32(x, coef)
     f = filters.IirCascadeMC(channels, coef)
+    plan = f.plan(n)
+    assert plan["form"] == "pipe" and plan["precision"] == 64 and plan["segs"] >= 3 and plan["warm"] >= 1, plan
     xd = torch.from_numpy(np.ascontiguousarray(x[:, :n])).to(dev)
     yd = torch.empty_like(xd)
     f.filter(xd, yd)
@@ -1396,9 +1401,13 @@ def test_iir_forced_segment_count_is_clamped(dev, oracle):
     filters.synth_f32(x, seed=11)
     sel = [0, 1000, 2047]
     ref = oracle.iir_cascade_batch_f32(x[sel].cpu().numpy(), coef)
-    for tuned in ({"iir_segs": 64}, {"iir_segs": 64, "iir_unpacked": 2}, {"iir_segs": 64, "iir_pipe": 1}):
+    for tuned, form in (({"iir_segs": 64}, "wave32"), ({"iir_segs": 64, "iir_unpacked": 2}, "wave16"),
+                        ({"iir_segs": 64, "iir_pipe": 1}, "pipe")):
         with capi.tuned(**tuned):
             f = filters.IirCascadeMC(channels, coef)
+            plan = f.plan(n)
+            # the forced 64 was reduced, to segments that hold their own warm-up, in the form the tunes select
+            assert plan["form"] == form and 1 < plan["segs"] < 64 and plan["seg_chunks"] >= plan["warm"] >= 1, (tuned, plan)
             y = torch.empty_like(x)
             f.filter(x, y)
             f.close()
@@ -1423,6 +1432,9 @@ def test_iir_time_segments_stream_across_calls(dev, oracle, form, segs):
     channels, n = 24, 1024 * (2048 if form == "wave64" else 256)
     with capi.tuned(iir_segs=segs, iir_pipe=1 if form == "pipe" else -1, iir_wave_min_items=0):
         f = filters.IirCascadeMC(channels, coef)
+        plan = f.plan(n)
+        assert (plan["form"], plan["precision"], plan["segs"]) == \
+            {"pipe": ("pipe", 32, segs), "wave32": ("wave32", 32, segs), "wave64": ("wave32", 64, segs)}[form], plan
         xs, ys = [], []
         for call in range(2):
             x = torch.empty(channels, n, dtype=torch.float32, device=dev)
