@@ -4,6 +4,7 @@
  * Part 2: multi-channel float32 cascade of second-order sections, fused in one kernel (SURVEY.md M4:
  * an "8-biquad cascade" is 8 chained reference handles with M=N=2).
  * Part 3: multi-channel float32 form of the general direct-form-I filter itself (any orders up to 8).
+ * Part 4: the biquad bank: the cascade of part 2 with a coefficient set per channel.
  */
 #ifndef LLZ_IIR_H
 #define LLZ_IIR_H
@@ -67,6 +68,49 @@ int           llz_iir_mc(unsigned long handle, const float *x, float *y, int fra
 int           llz_iir_mc_segments(unsigned long handle, int frame_len);
 int           llz_iir_mc_flush(unsigned long handle, float *y);         /* N more samples of x = 0 per channel: [channels][N]; returns N */
 int           llz_iir_mc_set_stream(unsigned long handle, void *stream);
+
+/* ---- Part 4: the biquad bank -- llz_iir_cascade_mc with a coefficient set per channel (an equaliser per channel, crossover
+ * networks, per-microphone correction, different weightings in one batch) ----
+ * Arguments: channels >= 1; stages 1..16, the same for every channel: a channel that needs fewer sections pads with identity
+ *   sections {1,0,0,1,0,0}.  coef is a HOST pointer, [channels][stages][6] doubles {b0,b1,b2,a0,a1,a2}, a0 ignored (taken as
+ *   1).  Every refusal returns (unsigned long)-1 (init) or LLZ_ERR_ARG with a message that names the function.
+ * Buffers: the contract of llz_iir_cascade_mc: planar [channels][frame_len] float32, any frame_len >= 1; device memory is
+ *   used in place and asynchronously on the handle's stream, host memory is staged and the call synchronous, host x == y
+ *   works in place; device x and y that overlap are refused with LLZ_ERR_ARG.  The state, [channels][stages][x1,x2,y1,y2]
+ *   in double, stays on the device between calls.
+ * Precision is the handle's: 32 only if EVERY channel's set passes the criterion of llz_iir_cascade_mc_precision (and the
+ *   iir_f64 tune is not 1); one channel that needs double puts the whole handle in double.
+ * Warm-up (time segments, part 3) is the handle's: the maximum over the channels of the memory probe run on each channel's
+ *   own cascade.  If one channel's probe says "not decayed within 64 chunks" the handle is never split along time, exactly as
+ *   a shared handle with such a cascade.
+ * Path and plan are chosen by the functions llz_iir_cascade_mc chooses with, under the same tunes (iir_segs, iir_pipe,
+ *   iir_wave_min_items, iir_unpacked, iir_f64).  The 32-samples-per-lane forms fold the b0 gains into one input gain, which in
+ *   a bank is a decision and a gain per channel: the bank does not take them, and llz_iir_bank_mc_plan reports
+ *   LLZ_IIR_FORM_WAVE16 where llz_iir_cascade_mc_plan would report LLZ_IIR_FORM_WAVE32.  A bank in double precision has no
+ *   wave form at all (its pipeline measured faster): its plan always reports LLZ_IIR_FORM_PIPE.  A bank whose rows are all equal
+ *   holds the table values of llz_iir_cascade_mc and gives the same bits wherever the two plans are equal and the shared
+ *   handle runs the same form: on the stage pipeline, and on the float32 16-sample wave form (the shared handle under
+ *   iir_unpacked = 2) with the same iir_segs forced on both, since the two kinds of workgroup hold different numbers of
+ *   waves and so choose different segment counts by themselves.
+ * Host cost of init: each DISTINCT set is probed once (equal rows are common in banks), single-threaded, and the answer is
+ *   the probe's own number, never an estimate of it: a plant's run is cut short only where the rest is known exactly (the
+ *   sections in front of the plant are not stepped; the run ends when the state repeats).  Measured per distinct 8-section
+ *   set: 4.2 ms for low-Q sections, 26 ms for 0.99-radius ones (the plain probe: 170 and 300 ms), so a bank of 4096 distinct
+ *   high-Q sets takes 105 s to initialise and llz_iir_bank_mc_set_coef 4 .. 33 ms per distinct set given. */
+unsigned long llz_iir_bank_mc_init(int channels, int stages, const double *coef);
+void          llz_iir_bank_mc_uninit(unsigned long handle);
+int           llz_iir_bank_mc(unsigned long handle, const float *x, float *y, int frame_len);   /* returns frame_len */
+/* replace the sets of channels [first, first + count) between calls; coef: HOST [count][stages][6].  Ordered on the handle's
+ * stream after the calls already issued (the caller waits for them).  The delay-line state is KEPT: the next call continues
+ * every section's x1, x2, y1, y2 under the new coefficients, which is what a direct-form-I parameter change means.  The
+ * handle's precision and warm-up are evaluated again over all channels (llz_iir_bank_mc_precision may answer differently
+ * afterwards).  A range outside [0, channels) returns LLZ_ERR_ARG and changes nothing.  A call that fails later (out of
+ * memory, a device error) puts the host's record of the given rows back, so precision and warm-up stay those of sets the
+ * handle has run with; the device tables of the given rows may then hold either version: repeat the call or drop the handle. */
+int           llz_iir_bank_mc_set_coef(unsigned long handle, int first, int count, const double *coef);
+int           llz_iir_bank_mc_set_stream(unsigned long handle, void *stream);
+int           llz_iir_bank_mc_precision(unsigned long handle);                       /* 32 or 64 */
+int           llz_iir_bank_mc_plan(unsigned long handle, int frame_len, int out[5]); /* as llz_iir_cascade_mc_plan */
 
 #ifdef __cplusplus
 }

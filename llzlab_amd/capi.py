@@ -157,6 +157,13 @@ def lib():
     sig("llz_iir_cascade_mc_set_stream", i, ul, vp)
     sig("llz_iir_cascade_mc_precision", i, ul)
     sig("llz_iir_cascade_mc_plan", i, ul, i, C.POINTER(C.c_int))
+    sig("llz_iir_bank_mc_init", ul, i, i, vp)
+    sig("llz_iir_bank_mc_uninit", None, ul)
+    sig("llz_iir_bank_mc", i, ul, vp, vp, i)
+    sig("llz_iir_bank_mc_set_coef", i, ul, i, i, vp)
+    sig("llz_iir_bank_mc_set_stream", i, ul, vp)
+    sig("llz_iir_bank_mc_precision", i, ul)
+    sig("llz_iir_bank_mc_plan", i, ul, i, C.POINTER(C.c_int))
     # llz_resample.h
     sig("llz_decimate_init", ul, i, d, i)
     sig("llz_decimate_uninit", None, ul)

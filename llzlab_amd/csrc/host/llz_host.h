@@ -17,7 +17,7 @@ int llz_host_design(int kind, double **out, int n, double fc1, double fc2, win_t
 enum {
     LLZ_TAG_FIR1 = 0x4c5a4631, LLZ_TAG_FIRM = 0x4c5a464d, LLZ_TAG_IIR1 = 0x4c5a4931, LLZ_TAG_IIRM = 0x4c5a494d,
     LLZ_TAG_RS1 = 0x4c5a5231, LLZ_TAG_RSM = 0x4c5a524d, LLZ_TAG_FFT1 = 0x4c5a5431, LLZ_TAG_FFTB = 0x4c5a5442,
-    LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642
+    LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))

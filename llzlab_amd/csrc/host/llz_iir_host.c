@@ -120,11 +120,18 @@ typedef struct {
     void *stream;
     int device;          /* the device the handle's buffers live on: every call binds it */
     llz_stage_t st_in, st_out;
+    /* Part 4, the bank (tag LLZ_TAG_IIRB): d_coef and the tables of wave[LLZS_IIR_BANK16_*] hold a row per channel, float32_ok
+     * and warm_chunks are the handle's verdicts over all channels, and the host keeps what llz_iir_bank_mc_set_coef needs */
+    double *h_c5;            /* [channels][stages][5] */
+    unsigned char *h_f32ok;  /* per channel: iirm_float32_ok */
+    int *h_warm;             /* per channel: iirm_memory_chunks */
+    int f32_rows;            /* the float tables hold every channel's current set */
 } iirm_t;
 
 static void iirm_destroy(iirm_t *f)
 {
     if (!f) return;
+    free(f->h_c5); free(f->h_f32ok); free(f->h_warm);
     for (int i = 0; i < f->ntab; i++) llzs_free(f->d_tab[i]);
     llzs_free(f->d_state); llzs_free(f->d_state_alt);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
@@ -214,6 +221,22 @@ static int iirm_fold(const double *c5, int S, const iirm_fold_t *lim, double *xf
     return 1;
 }
 
+/* one cascade's tables for 16 samples per lane: pd [S][6][4], pl [S][64][12] in double and their float copies pd32 [S][16],
+ * pl32 [S][64][12] with cf32 [S][24] = the h responses and the coefficients (layouts: llz_shim.h) */
+static void iirm_run16_rows(const double *c5, size_t S, double *pd, double *pl, float *pd32, float *pl32, float *ph32)
+{
+    for (size_t s = 0; s < S; s++) {
+        iirm_pow_t w;
+        iirm_powers(c5[5 * s + 3], c5[5 * s + 4], 16, &w);
+        memcpy(pd + 24 * s, w.p2, sizeof(w.p2));
+        memcpy(pl + 768 * s, w.pl, sizeof(w.pl));
+        for (int i = 0; i < 16; i++) pd32[16 * s + i] = (float)pd[24 * s + i];
+        for (int i = 0; i < 768; i++) pl32[768 * s + i] = (float)pl[768 * s + i];
+        iirm_h_responses(c5[5 * s + 3], c5[5 * s + 4], 8, ph32 + 24 * s);
+        for (int k = 0; k < 8; k++) ph32[24 * s + 16 + k] = k < 5 ? (float)c5[5 * s + k] : 0.f;
+    }
+}
+
 /* 16 samples per lane: the stage pipeline's double tables (any section count; WAVE16_F64 reads them too) and, where float32
  * arithmetic is good enough, float copies with the h responses and the coefficients for WAVE16_F32 */
 static int iirm_build_run16(iirm_t *f, const double *c5)
@@ -225,16 +248,7 @@ static int iirm_build_run16(iirm_t *f, const double *c5)
     if (rc == LLZ_OK) {
         double *pl = pd + 24 * S;
         float *pl32 = pd32 + 16 * S, *ph32 = pl32 + 768 * S;
-        for (size_t s = 0; s < S; s++) {
-            iirm_pow_t w;
-            iirm_powers(c5[5 * s + 3], c5[5 * s + 4], 16, &w);
-            memcpy(pd + 24 * s, w.p2, sizeof(w.p2));
-            memcpy(pl + 768 * s, w.pl, sizeof(w.pl));
-            for (int i = 0; i < 16; i++) pd32[16 * s + i] = (float)pd[24 * s + i];
-            for (int i = 0; i < 768; i++) pl32[768 * s + i] = (float)pl[768 * s + i];
-            iirm_h_responses(c5[5 * s + 3], c5[5 * s + 4], 8, ph32 + 24 * s);
-            for (int k = 0; k < 8; k++) ph32[24 * s + 16 + k] = k < 5 ? (float)c5[5 * s + k] : 0.f;
-        }
+        iirm_run16_rows(c5, S, pd, pl, pd32, pl32, ph32);
         llzs_iir_wave_tables *d = &f->wave[LLZS_IIR_WAVE16_F64], *d32 = &f->wave[LLZS_IIR_WAVE16_F32];
         const iirm_up_t up[2] = {{&d->pd, pd, sizeof(double) * 24 * S}, {&d->pl, pl, sizeof(double) * 768 * S}};
         const iirm_up_t up32[3] = {{&d32->pd, pd32, sizeof(float) * 16 * S}, {&d32->pl, pl32, sizeof(float) * 768 * S},
@@ -434,7 +448,7 @@ int llz_iir_cascade_mc_set_stream(unsigned long handle, void *stream)
     return LLZ_OK;
 }
 
-static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len);
+static int iirm_process(iirm_t *f, const char *who, const float *x, float *y, int frame_len);
 
 int llz_iir_cascade_mc(unsigned long handle, const float *x, float *y, int frame_len)
 {
@@ -444,7 +458,7 @@ int llz_iir_cascade_mc(unsigned long handle, const float *x, float *y, int frame
     }
     iirm_t *f = (iirm_t *)handle;
     const int prev = llzs_device_enter(f->device);
-    const int rc = iirm_process(f, x, y, frame_len);
+    const int rc = iirm_process(f, "llz_iir_cascade_mc", x, y, frame_len);
     llzs_device_leave(prev);
     return rc;
 }
@@ -459,9 +473,13 @@ static int iirm_path(const iirm_t *f, int n_fast)
 {
     const long seg_items = f->warm_chunks > 0 ? (long)f->channels * (n_fast / LLZS_IIR_PIPE_CHUNK / (8 * f->warm_chunks)) : 0;
     const int min_items = llzs_tune(LLZS_TUNE_IIR_WAVE_MIN_ITEMS) >= 0 ? llzs_tune(LLZS_TUNE_IIR_WAVE_MIN_ITEMS) : 2048;
-    const int w16 = f->float32_ok ? LLZS_IIR_WAVE16_F32 : LLZS_IIR_WAVE16_F64;
+    const int bank = f->tag == LLZ_TAG_IIRB;      /* its own 16-sample forms, and no 32-sample ones: wave[w32].pl stays NULL */
+    const int w16 = f->float32_ok ? (bank ? LLZS_IIR_BANK16_F32 : LLZS_IIR_WAVE16_F32) : LLZS_IIR_WAVE16_F64;
     const int w32 = f->float32_ok ? LLZS_IIR_WAVE32_F32 : LLZS_IIR_WAVE32_F64;
-    if (f->stages > 8 || seg_items < min_items || llzs_tune(LLZS_TUNE_IIR_PIPE) == 1 || !f->wave[w16].pl) return IIRM_PIPE;
+    /* (a bank with a channel that never decays has no warm-up: the wave forms take none such, whatever the crossover is tuned to) */
+    if (f->stages > 8 || seg_items < min_items || llzs_tune(LLZS_TUNE_IIR_PIPE) == 1 || !f->wave[w16].pl ||
+        (bank && (f->warm_chunks < 1 || !f->float32_ok)))     /* a bank in double: the pipeline measured faster */
+        return IIRM_PIPE;
     return (f->wave[w32].pl && n_fast >= LLZS_IIR_WAVE_CHUNK(w32)) ? w32 : w16;
 }
 
@@ -470,7 +488,7 @@ static int iirm_path(const iirm_t *f, int n_fast)
 static int iirm_main_launch(const iirm_t *f, int n_fast, int *n)
 {
     const int path = iirm_path(f, n_fast);
-    *n = path >= LLZS_IIR_WAVE32_F32 ? n_fast - n_fast % LLZS_IIR_WAVE_CHUNK(path) : n_fast;
+    *n = LLZS_IIR_WAVE_IS32(path) ? n_fast - n_fast % LLZS_IIR_WAVE_CHUNK(path) : n_fast;
     return path;
 }
 
@@ -480,13 +498,8 @@ static int iirm_fast_samples(int frame_len, int rows_aligned)
     return (rows_aligned && frame_len % 4 == 0) ? frame_len - frame_len % LLZS_IIR_PIPE_CHUNK : 0;
 }
 
-int llz_iir_cascade_mc_plan(unsigned long handle, int frame_len, int out[5])
+static int iirm_plan(const iirm_t *f, int frame_len, int out[5])
 {
-    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRM) || !out || frame_len < 1) {
-        llzs_set_error("llz_iir_cascade_mc_plan: bad handle, NULL out or frame_len");
-        return LLZ_ERR_ARG;
-    }
-    const iirm_t *f = (const iirm_t *)handle;
     int n = 0, p[3] = {0, 0, 0}, rc = LLZ_OK;
     const int path = iirm_main_launch(f, iirm_fast_samples(frame_len, 1), &n);
     if (n > 0) {
@@ -494,20 +507,30 @@ int llz_iir_cascade_mc_plan(unsigned long handle, int frame_len, int out[5])
         rc = llzs_iir_cascade_plan(path, f->channels, n, f->stages, f->warm_chunks, p);
         llzs_device_leave(prev);
     }
-    out[0] = path == IIRM_PIPE ? LLZ_IIR_FORM_PIPE : path >= LLZS_IIR_WAVE32_F32 ? LLZ_IIR_FORM_WAVE32 : LLZ_IIR_FORM_WAVE16;
+    out[0] = path == IIRM_PIPE ? LLZ_IIR_FORM_PIPE : LLZS_IIR_WAVE_IS32(path) ? LLZ_IIR_FORM_WAVE32 : LLZ_IIR_FORM_WAVE16;
     out[1] = f->float32_ok ? 32 : 64;
     out[2] = p[0]; out[3] = p[1]; out[4] = p[2];
     return rc;
 }
 
+int llz_iir_cascade_mc_plan(unsigned long handle, int frame_len, int out[5])
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRM) || !out || frame_len < 1) {
+        llzs_set_error("llz_iir_cascade_mc_plan: bad handle, NULL out or frame_len");
+        return LLZ_ERR_ARG;
+    }
+    return iirm_plan((const iirm_t *)handle, frame_len, out);
+}
+
 /* every launch reads d_state and writes d_state_alt (segments of one launch are not ordered), which then swap */
 static int iirm_launch(iirm_t *f, int path, const float *d_in, float *d_out, int n, int pitch)
 {
-    const llzs_iir_wave_tables *pipe = &f->wave[LLZS_IIR_WAVE16_F64];
+    const int bank = f->tag == LLZ_TAG_IIRB;
+    const llzs_iir_wave_tables *pipe = &f->wave[LLZS_IIR_WAVE16_F64];     /* the pipeline's tables, shared or per channel */
     const int rc = path == IIRM_PIPE
-        ? llzs_iir_cascade_pipe_f32(d_in, d_out, f->d_coef, (const double *)pipe->pd, (const double *)pipe->pl, f->d_state,
-                                    f->d_state_alt, f->channels, n, pitch, pitch, f->stages, f->warm_chunks, f->float32_ok,
-                                    f->stream)
+        ? (bank ? llzs_iir_bank_pipe_f32 : llzs_iir_cascade_pipe_f32)(
+              d_in, d_out, f->d_coef, (const double *)pipe->pd, (const double *)pipe->pl, f->d_state, f->d_state_alt,
+              f->channels, n, pitch, pitch, f->stages, f->warm_chunks, f->float32_ok, f->stream)
         : llzs_iir_cascade_wave(path, &f->wave[path], d_in, d_out, f->d_state, f->d_state_alt, f->channels, n, pitch, pitch,
                                 f->stages, f->warm_chunks, f->stream);
     if (rc == LLZ_OK) {
@@ -516,13 +539,13 @@ static int iirm_launch(iirm_t *f, int path, const float *d_in, float *d_out, int
     return rc;
 }
 
-static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len)
+static int iirm_process(iirm_t *f, const char *who, const float *x, float *y, int frame_len)
 {
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
     const int in_dev = llzs_is_device_ptr(x), out_dev = llzs_is_device_ptr(y);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
     /* a later time segment reads its warm-up chunks from x while the segment before it writes them to y */
-    if (llz_refuse_device_overlap("llz_iir_cascade_mc", "x", x, bytes, in_dev, "y", y, bytes, out_dev)) return LLZ_ERR_ARG;
+    if (llz_refuse_device_overlap(who, "x", x, bytes, in_dev, "y", y, bytes, out_dev)) return LLZ_ERR_ARG;
     const float *d_in = x;
     float *d_out = y;
     int rc = LLZ_OK;
@@ -540,17 +563,321 @@ static int iirm_process(iirm_t *f, const float *x, float *y, int frame_len)
      * kernel.  All read and write the same per-section state. */
     const int n_fast = iirm_fast_samples(frame_len, ((size_t)d_in | (size_t)d_out) % 16 == 0);
     int main_n = 0, done = 0, path = iirm_main_launch(f, n_fast, &main_n);
-    if (rc == LLZ_OK && path >= LLZS_IIR_WAVE32_F32) {
+    if (rc == LLZ_OK && LLZS_IIR_WAVE_IS32(path)) {
         done = main_n;
         rc = iirm_launch(f, path, d_in, d_out, done, frame_len);
         path = path == LLZS_IIR_WAVE32_F32 ? LLZS_IIR_WAVE16_F32 : LLZS_IIR_WAVE16_F64;
     }
     if (rc == LLZ_OK && n_fast > done) rc = iirm_launch(f, path, d_in + done, d_out + done, n_fast - done, frame_len);
     if (rc == LLZ_OK && n_fast < frame_len)
-        rc = llzs_iir_cascade_f32(d_in + n_fast, d_out + n_fast, f->d_coef, f->d_state, f->channels,
-                                  frame_len - n_fast, frame_len, frame_len, f->stages, f->stream);
+        rc = (f->tag == LLZ_TAG_IIRB ? llzs_iir_bank_f32 : llzs_iir_cascade_f32)(
+                 d_in + n_fast, d_out + n_fast, f->d_coef, f->d_state, f->channels, frame_len - n_fast, frame_len, frame_len,
+                 f->stages, f->stream);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(y, d_out, bytes, f->stream);
     return rc == LLZ_OK ? frame_len : rc;
+}
+
+
+/* ---- Part 4: the biquad bank: a coefficient set per channel (include/llz_iir.h).  An iirm_t with its own tag: staging, state
+ * ping-pong, path choice, plan and process are the shared handle's; the tables hold a row per channel. ---- */
+
+/* iirm_memory_chunks for a bank of many sets: the same number by less work.  For the plant in section s0 only the sections
+ * s >= s0 are stepped (the earlier ones see zero input from zero state: their outputs are zeros, which neither raise a
+ * maximum nor change a later section's sums).  And a plant's run ends once the state, i <= 1024 samples into a chunk, equals
+ * bit for bit the state at the chunk's start: with zero input the cascade is a deterministic map of its state, so from
+ * there on the outputs repeat with period i, the chunk's remaining samples and every later chunk (1024 >= i consecutive
+ * samples: every phase) have exactly the maximum of these i samples.  That covers the state that has decayed to exactly
+ * 0.0 (period 1, maximum 0) and the cycles among the smallest subnormals that round-to-nearest leaves a decaying section
+ * in, where the plain probe spends the rest of its 64 chunks in subnormal arithmetic (0.17 s for 8 low-Q sections, 0.3 s
+ * for 8 of radius 0.99).  All of it holds for finite coefficients only (0 x inf is not 0): any other set goes to the probe
+ * itself. */
+static int iirm_memory_chunks_bank(const double *c5, int S)
+{
+    enum { MAXC = 64, CH = 1024 };
+    for (int i = 0; i < 5 * S; i++) if (!(fabs(c5[i]) < INFINITY)) return iirm_memory_chunks(c5, S);
+    double env[MAXC];
+    for (int k = 0; k < MAXC; k++) env[k] = 0.0;
+    for (int s0 = 0; s0 < S; s0++) {
+        double x1[16] = {0}, x2[16] = {0}, y1[16] = {0}, y2[16] = {0}, was[4][16];
+        const size_t live = sizeof(double) * (size_t)(S - s0);
+        y1[s0] = 1.0; y2[s0] = 1.0;
+        for (int k = 0; k < MAXC; k++) {
+            double m = 0.0;
+            int repeats = 0;
+            memcpy(was[0], x1, sizeof(x1)); memcpy(was[1], x2, sizeof(x2)); memcpy(was[2], y1, sizeof(y1)); memcpy(was[3], y2, sizeof(y2));
+            for (int i = 0; i < CH && !repeats; i++) {
+                double v = 0.0;
+                for (int s = s0; s < S; s++) {
+                    double acc = c5[5 * s] * v + c5[5 * s + 1] * x1[s] + c5[5 * s + 2] * x2[s]
+                                 - c5[5 * s + 3] * y1[s] - c5[5 * s + 4] * y2[s];
+                    x2[s] = x1[s]; x1[s] = v; y2[s] = y1[s]; y1[s] = acc;
+                    v = acc;
+                    const double a = fabs(acc);
+                    if (a > m) m = a;
+                }
+                repeats = !memcmp(was[2] + s0, y1 + s0, live) && !memcmp(was[3] + s0, y2 + s0, live) &&
+                          !memcmp(was[0] + s0, x1 + s0, live) && !memcmp(was[1] + s0, x2 + s0, live);
+            }
+            if (!(m < 1e300)) return 0;                              /* unstable */
+            if (m > env[k]) env[k] = m;
+            if (repeats) {
+                for (int j = k + 1; j < MAXC; j++) if (m > env[j]) env[j] = m;
+                break;
+            }
+        }
+    }
+    double peak = 1.0;
+    for (int k = 0; k < MAXC; k++) if (env[k] > peak) peak = env[k];
+    int last_loud = -1;
+    for (int k = 0; k < MAXC; k++) if (env[k] >= 1e-13 * peak) last_loud = k;
+    if (last_loud >= MAXC - 2) return 0;
+    return last_loud + 2;
+}
+
+/* the two verdicts of channels [first, first + count), each distinct coefficient set examined once (equal rows are common
+ * in a bank): an open-addressed table of the channels whose sets have been examined, keyed by the row's bytes */
+static int iirb_verdicts(iirm_t *f, int first, int count)
+{
+    const size_t row = 5 * (size_t)f->stages;
+    size_t cap = 16;
+    while (cap < 2 * (size_t)count) cap *= 2;
+    int *seen = (int *)malloc(sizeof(int) * cap);
+    if (!seen) return LLZ_ERR_NOMEM;
+    for (size_t i = 0; i < cap; i++) seen[i] = -1;
+    for (int c = first; c < first + count; c++) {
+        const double *c5 = f->h_c5 + row * (size_t)c;
+        const unsigned char *b = (const unsigned char *)c5;
+        unsigned long long h = 1469598103934665603ULL;                /* FNV-1a */
+        for (size_t i = 0; i < row * sizeof(double); i++) h = (h ^ b[i]) * 1099511628211ULL;
+        size_t at = (size_t)h & (cap - 1);
+        while (seen[at] >= 0 && memcmp(f->h_c5 + row * (size_t)seen[at], c5, row * sizeof(double)) != 0) at = (at + 1) & (cap - 1);
+        if (seen[at] >= 0) {
+            f->h_f32ok[c] = f->h_f32ok[seen[at]]; f->h_warm[c] = f->h_warm[seen[at]];
+        } else {
+            seen[at] = c;
+            f->h_f32ok[c] = (unsigned char)iirm_float32_ok(c5, f->stages);
+            f->h_warm[c] = iirm_memory_chunks_bank(c5, f->stages);
+        }
+    }
+    free(seen);
+    return LLZ_OK;
+}
+
+/* the handle's precision and warm-up from the channels': float32 only if every set passes, the longest memory, and no split
+ * along time at all if one channel's probe gave 0 */
+static void iirb_handle_verdicts(iirm_t *f)
+{
+    int ok = llzs_tune(LLZS_TUNE_IIR_F64) != 1, warm = f->h_warm[0];
+    for (int c = 0; c < f->channels; c++) {
+        ok = ok && f->h_f32ok[c];
+        if (warm > 0) warm = f->h_warm[c] == 0 ? 0 : (f->h_warm[c] > warm ? f->h_warm[c] : warm);
+    }
+    f->float32_ok = ok; f->warm_chunks = warm;
+}
+
+/* build the table rows of channels [first, first + count) with the shared handle's builder and copy them to the device,
+ * ordered on the handle's stream; with32: the float tables too.  Batches of 16 channels bound the host buffer. */
+static int iirb_upload_rows(iirm_t *f, int first, int count, int with32)
+{
+    enum { BATCH = 16 };
+    const size_t S = (size_t)f->stages;
+    double *pd = (double *)malloc(sizeof(double) * BATCH * S * (24 + 768));
+    float *pd32 = (float *)malloc(sizeof(float) * BATCH * S * (16 + 768 + 24));
+    int rc = (pd && pd32) ? LLZ_OK : LLZ_ERR_NOMEM;
+    const llzs_iir_wave_tables *d = &f->wave[LLZS_IIR_WAVE16_F64], *d32 = &f->wave[LLZS_IIR_BANK16_F32];
+    for (int c0 = first; c0 < first + count && rc == LLZ_OK; c0 += BATCH) {
+        const size_t nb = (size_t)(first + count - c0 < BATCH ? first + count - c0 : BATCH);
+        double *pl = pd + 24 * S * nb;
+        float *pl32 = pd32 + 16 * S * nb, *ph32 = pl32 + 768 * S * nb;
+        for (size_t k = 0; k < nb; k++)
+            iirm_run16_rows(f->h_c5 + 5 * S * ((size_t)c0 + k), S, pd + 24 * S * k, pl + 768 * S * k, pd32 + 16 * S * k,
+                            pl32 + 768 * S * k, ph32 + 24 * S * k);
+        const size_t at = (size_t)c0 * S;
+        rc = llzs_h2d((double *)f->d_coef + 5 * at, f->h_c5 + 5 * at, sizeof(double) * 5 * S * nb, f->stream);
+        if (rc == LLZ_OK) rc = llzs_h2d((double *)d->pd + 24 * at, pd, sizeof(double) * 24 * S * nb, f->stream);
+        if (rc == LLZ_OK) rc = llzs_h2d((double *)d->pl + 768 * at, pl, sizeof(double) * 768 * S * nb, f->stream);
+        if (rc == LLZ_OK && with32) rc = llzs_h2d((float *)d32->pd + 16 * at, pd32, sizeof(float) * 16 * S * nb, f->stream);
+        if (rc == LLZ_OK && with32) rc = llzs_h2d((float *)d32->pl + 768 * at, pl32, sizeof(float) * 768 * S * nb, f->stream);
+        if (rc == LLZ_OK && with32) rc = llzs_h2d((float *)d32->cf + 24 * at, ph32, sizeof(float) * 24 * S * nb, f->stream);
+    }
+    free(pd); free(pd32);
+    return rc;
+}
+
+/* the float tables exist once a float32 handle needs them; a handle in double keeps the double tables only */
+static int iirb_alloc32(iirm_t *f)
+{
+    llzs_iir_wave_tables *d32 = &f->wave[LLZS_IIR_BANK16_F32];
+    if (d32->pl) return LLZ_OK;
+    const size_t rows = (size_t)f->channels * (size_t)f->stages;
+    void *pd = llzs_malloc(sizeof(float) * 16 * rows), *pl = llzs_malloc(sizeof(float) * 768 * rows);
+    void *cf = llzs_malloc(sizeof(float) * 24 * rows);
+    if (!pd || !pl || !cf) {
+        llzs_free(pd); llzs_free(pl); llzs_free(cf);
+        return LLZ_ERR_NOMEM;
+    }
+    f->d_tab[f->ntab++] = pd; f->d_tab[f->ntab++] = pl; f->d_tab[f->ntab++] = cf;
+    d32->pd = pd; d32->pl = pl; d32->cf = cf;
+    return LLZ_OK;
+}
+
+/* after the verdicts of [first, first + count) changed: the rows given, or every row when the float tables have to be
+ * (re)built because the handle is in float32 and they do not hold every channel's current set */
+static int iirb_refresh(iirm_t *f, int first, int count)
+{
+    int rc = LLZ_OK;
+    iirb_handle_verdicts(f);
+    if (f->float32_ok && !f->f32_rows) {
+        rc = iirb_alloc32(f);
+        if (rc == LLZ_OK) rc = iirb_upload_rows(f, 0, f->channels, 1);
+        f->f32_rows = rc == LLZ_OK;
+    } else {
+        rc = iirb_upload_rows(f, first, count, f->float32_ok);
+        if (!f->float32_ok) f->f32_rows = 0;
+    }
+    return rc;
+}
+
+static void iirb_rows_from_coef(iirm_t *f, int first, int count, const double *coef)
+{
+    const size_t rows = (size_t)count * (size_t)f->stages;
+    double *c5 = f->h_c5 + 5 * (size_t)first * (size_t)f->stages;
+    for (size_t r = 0; r < rows; r++) {                    /* {b0,b1,b2,a0,a1,a2} -> {b0,b1,b2,a1,a2}; a0 taken as 1 */
+        c5[5 * r + 0] = coef[6 * r + 0]; c5[5 * r + 1] = coef[6 * r + 1]; c5[5 * r + 2] = coef[6 * r + 2];
+        c5[5 * r + 3] = coef[6 * r + 4]; c5[5 * r + 4] = coef[6 * r + 5];
+    }
+}
+
+unsigned long llz_iir_bank_mc_init(int channels, int stages, const double *coef)
+{
+    if (channels < 1 || stages < 1 || stages > 16 || !coef) {
+        llzs_set_error("llz_iir_bank_mc_init: channels %d (at least 1), stages %d (1..16) or NULL coef", channels, stages);
+        return LLZ_BAD_HANDLE;
+    }
+    iirm_t *f = (iirm_t *)calloc(1, sizeof(*f));
+    if (!f) return LLZ_BAD_HANDLE;
+    f->tag = LLZ_TAG_IIRB;
+    f->device = llzs_device_get();
+    f->channels = channels; f->stages = stages;
+    const size_t rows = (size_t)channels * (size_t)stages, st_bytes = sizeof(double) * 4 * rows;
+    llzs_iir_wave_tables *d = &f->wave[LLZS_IIR_WAVE16_F64];
+    f->h_c5 = (double *)malloc(sizeof(double) * 5 * rows);
+    f->h_f32ok = (unsigned char *)malloc((size_t)channels);
+    f->h_warm = (int *)malloc(sizeof(int) * (size_t)channels);
+    int rc = (f->h_c5 && f->h_f32ok && f->h_warm) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {                                    /* the device first: without one, fail before the probes run */
+        f->d_tab[f->ntab++] = llzs_malloc(sizeof(double) * 5 * rows);
+        f->d_tab[f->ntab++] = llzs_malloc(sizeof(double) * 24 * rows);
+        f->d_tab[f->ntab++] = llzs_malloc(sizeof(double) * 768 * rows);
+        f->d_coef = (const double *)f->d_tab[0];
+        d->cf = f->d_coef; d->pd = f->d_tab[1]; d->pl = f->d_tab[2];
+        f->d_state = (double *)llzs_malloc(st_bytes);
+        f->d_state_alt = (double *)llzs_malloc(st_bytes);
+        if (!d->cf || !d->pd || !d->pl || !f->d_state || !f->d_state_alt) rc = LLZ_ERR_NOMEM;
+    }
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_state, 0, st_bytes, NULL);
+    if (rc == LLZ_OK) {
+        iirb_rows_from_coef(f, 0, channels, coef);
+        rc = iirb_verdicts(f, 0, channels);
+    }
+    if (rc == LLZ_OK) rc = iirb_refresh(f, 0, channels);
+    if (rc == LLZ_OK) rc = llzs_sync(NULL);
+    if (rc != LLZ_OK) {
+        iirm_destroy(f);
+        return LLZ_BAD_HANDLE;
+    }
+    return (unsigned long)f;
+}
+
+void llz_iir_bank_mc_uninit(unsigned long handle)
+{
+    if (LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRB)) {
+        const int prev = llzs_device_enter(((iirm_t *)handle)->device);
+        llzs_sync(((iirm_t *)handle)->stream);
+        iirm_destroy((iirm_t *)handle);
+        llzs_device_leave(prev);
+    }
+}
+
+int llz_iir_bank_mc(unsigned long handle, const float *x, float *y, int frame_len)
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRB) || !x || !y || frame_len < 1) {
+        llzs_set_error("llz_iir_bank_mc: bad handle, buffer or frame_len");
+        return LLZ_ERR_ARG;
+    }
+    iirm_t *f = (iirm_t *)handle;
+    const int prev = llzs_device_enter(f->device);
+    const int rc = iirm_process(f, "llz_iir_bank_mc", x, y, frame_len);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_iir_bank_mc_set_coef(unsigned long handle, int first, int count, const double *coef)
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRB) || !coef) {
+        llzs_set_error("llz_iir_bank_mc_set_coef: bad handle or NULL coef");
+        return LLZ_ERR_ARG;
+    }
+    iirm_t *f = (iirm_t *)handle;
+    if (first < 0 || count < 1 || count > f->channels || first > f->channels - count) {
+        llzs_set_error("llz_iir_bank_mc_set_coef: channels %d .. %d of a bank of %d", first, first + count - 1, f->channels);
+        return LLZ_ERR_ARG;
+    }
+    /* the rows' host copies and verdicts as they were: a call that fails part-way puts them back, so that the handle's
+     * precision and warm-up still describe sets it has run with (the device rows given may then hold either version) */
+    const size_t row = sizeof(double) * 5 * (size_t)f->stages;
+    double *was = (double *)malloc(row * (size_t)count + (sizeof(int) + 1) * (size_t)count);
+    if (!was) {
+        llzs_set_error("llz_iir_bank_mc_set_coef: out of host memory");
+        return LLZ_ERR_NOMEM;
+    }
+    int *was_warm = (int *)((char *)was + row * (size_t)count);
+    unsigned char *was_ok = (unsigned char *)(was_warm + count);
+    memcpy(was, f->h_c5 + 5 * (size_t)f->stages * (size_t)first, row * (size_t)count);
+    memcpy(was_warm, f->h_warm + first, sizeof(int) * (size_t)count);
+    memcpy(was_ok, f->h_f32ok + first, (size_t)count);
+    const int prev = llzs_device_enter(f->device);
+    iirb_rows_from_coef(f, first, count, coef);
+    int rc = iirb_verdicts(f, first, count);
+    if (rc == LLZ_OK) rc = iirb_refresh(f, first, count);
+    if (rc != LLZ_OK) {
+        memcpy(f->h_c5 + 5 * (size_t)f->stages * (size_t)first, was, row * (size_t)count);
+        memcpy(f->h_warm + first, was_warm, sizeof(int) * (size_t)count);
+        memcpy(f->h_f32ok + first, was_ok, (size_t)count);
+        iirb_handle_verdicts(f);
+        f->f32_rows = 0;                                    /* the next successful call rebuilds every float row */
+    }
+    llzs_device_leave(prev);
+    free(was);
+    return rc;
+}
+
+int llz_iir_bank_mc_set_stream(unsigned long handle, void *stream)
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRB)) {
+        llzs_set_error("llz_iir_bank_mc_set_stream: bad handle");
+        return LLZ_ERR_ARG;
+    }
+    ((iirm_t *)handle)->stream = stream;
+    return LLZ_OK;
+}
+
+int llz_iir_bank_mc_precision(unsigned long handle)
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRB)) {
+        llzs_set_error("llz_iir_bank_mc_precision: bad handle");
+        return LLZ_ERR_ARG;
+    }
+    return ((iirm_t *)handle)->float32_ok ? 32 : 64;
+}
+
+int llz_iir_bank_mc_plan(unsigned long handle, int frame_len, int out[5])
+{
+    if (!LLZ_HANDLE_OK(handle, iirm_t, LLZ_TAG_IIRB) || !out || frame_len < 1) {
+        llzs_set_error("llz_iir_bank_mc_plan: bad handle, NULL out or frame_len");
+        return LLZ_ERR_ARG;
+    }
+    return iirm_plan((const iirm_t *)handle, frame_len, out);
 }
 
 

@@ -61,7 +61,9 @@ k_iir_df1_f64_exact(const double *__restrict__ in, double *__restrict__ out, con
 constexpr int CAS_TILE = 64;            // samples per staged tile (and channels per wave)
 constexpr int CAS_PITCH = CAS_TILE + 1; // LDS row pitch: lane-per-row column walks are conflict-free
 
-template <int S>
+// BANK: a coefficient set per channel, coef = [channels][stages][5] (llz_iir_bank_mc): the coefficients are per-lane
+// registers either way, a lane reads its own channel's
+template <int S, bool BANK = false>
 __global__ void __launch_bounds__(64)
 k_iir_cascade_f32(const float *__restrict__ in, float *__restrict__ out, const double *__restrict__ coef,
                   double *__restrict__ state, int channels, int n, long in_pitch, long out_pitch, int stages)
@@ -72,6 +74,7 @@ k_iir_cascade_f32(const float *__restrict__ in, float *__restrict__ out, const d
     const int c0 = blockIdx.x * CAS_TILE;
     const int c = c0 + lane;
     const bool live = c < channels;
+    if (BANK) coef += (size_t)(live ? c : 0) * 5 * stages;
 
     double b0[S], b1[S], b2[S], a1[S], a2[S], x1[S], x2[S], y1[S], y2[S];
 #pragma unroll
@@ -195,7 +198,9 @@ __device__ __forceinline__ float lane63_(float v) { return __int_as_float(__buil
 // R = double: the general form.  R = float: taken only when the host has checked every section of the cascade for a low
 // rounding-noise gain (see llz_iir_cascade_mc_init): same algorithm, float32 arithmetic and 4 KB hand-over slots.
 // RR samples per lane and chunk (16 in both shipped instantiations)
-template <typename R, int RR>
+// BANK: a coefficient set per channel (llz_iir_bank_mc): the three tables are [channels][...], and the workgroup, which owns
+// one channel already, reads its channel's
+template <typename R, int RR, bool BANK = false>
 __global__ void __launch_bounds__(1024)
 k_iir_cascade_pipe(const float *__restrict__ in, float *__restrict__ out, const double *__restrict__ coef,
                        const double *__restrict__ pd /* [S][6][4] */, const double *__restrict__ pl /* [S][64][12] */,
@@ -214,6 +219,7 @@ k_iir_cascade_pipe(const float *__restrict__ in, float *__restrict__ out, const 
     const int skip = seg > 0 ? warm : 0;                                   // leading chunks computed but not written
     const int chunk0 = seg * seg_chunks - skip;
     const int nchunks = min(nchunks_total, (seg + 1) * seg_chunks) - chunk0;
+    if (BANK) { coef += (size_t)c * 5 * stages; pd += (size_t)c * 24 * stages; pl += (size_t)c * 768 * stages; }
     const R b0 = (R)coef[5 * s + 0], b1 = (R)coef[5 * s + 1], b2 = (R)coef[5 * s + 2];
     const R a1 = (R)coef[5 * s + 3], a2 = (R)coef[5 * s + 4];
     R P[4][4];                                                       // P^1, P^2, P^4, P^8 (wave-uniform)
@@ -426,25 +432,44 @@ __device__ __forceinline__ void pk_section(f2 (&U)[8], const f16v H, const f8v c
 
 // S = the number of sections exactly
 // (forcing four waves per SIMD with amdgpu_waves_per_eu spills 6 registers inside the loop: 2.54 against 2.34 ms)
-template <int S>
-__global__ void __launch_bounds__(256)
+// BANK (llz_iir_bank_mc): a coefficient set per channel, the three tables [channels][...].  The workgroup is ONE wave with its
+// one item, so the LDS image is its own channel's: staged in the compact form of k_iir_cascade_wave_pk32 below (P^lane for 64
+// lanes, P^(i+1) i < 16, P^(i+1) i < 32: 448 of the table's 768 values per section, the same numbers), which at 8 sections is
+// 14.8 KB per wave and leaves the registers, not LDS, to bound the waves a CU holds.  The channel is wave-uniform (it comes
+// from blockIdx), so the written-out scalar loads only take a per-wave base.
+template <int S, bool BANK = false>
+__global__ void __launch_bounds__(BANK ? 64 : 256)
 k_iir_cascade_wave_pk(const float *__restrict__ in, float *__restrict__ out,
                       const float *__restrict__ pd32 /* [S][16], P^(2^d) d < 4, row major 2x2 each */,
                       const float *__restrict__ pl32 /* [S][64][12] */, const float *__restrict__ ph32 /* [S][24] */,
                       const double *__restrict__ state_in, double *__restrict__ state, int nchunks_total, long in_pitch,
                       long out_pitch, int segs, int seg_chunks, int warm, long items)
 {
-    __shared__ __attribute__((aligned(16))) float s_pl[S * 64 * 12];
+    __shared__ __attribute__((aligned(16))) float s_pl[BANK ? S * 448 : S * 64 * 12];
     __shared__ __attribute__((aligned(16))) float s_pd[S * 16];
-    // (m00, m01, m10, m11) -> (m00, m10, m01, m11): columns become aligned pairs
-    for (int e = threadIdx.x; e < S * 768; e += 256) s_pl[e] = pl32[(e & ~3) | ((e & 1) << 1) | ((e >> 1) & 1)];
-    if (threadIdx.x < S * 16) {
-        const int e = threadIdx.x;
-        s_pd[e] = pd32[(e & ~3) | ((e & 1) << 1) | ((e >> 1) & 1)];
+    if constexpr (BANK) {
+        const size_t cb = (size_t)(blockIdx.x / segs) * S;
+        pd32 += cb * 16; pl32 += cb * 768; ph32 += cb * 24;
+        for (int e = threadIdx.x; e < S * 448; e += 64) {         // the staging loop of k_iir_cascade_wave_pk32, 64 threads
+            const int sec = e / 448, r = e - sec * 448;
+            const int lane_src = r < 256 ? r >> 2 : (r < 320 ? (r - 256) >> 2 : (r - 320) >> 2);
+            const int part = r < 256 ? 0 : (r < 320 ? 4 : 8);
+            const int el = r & 3, el_t = ((el & 1) << 1) | ((el >> 1) & 1);
+            s_pl[e] = pl32[(sec * 64 + lane_src) * 12 + part + el_t];
+        }
+        for (int e = threadIdx.x; e < S * 16; e += 64) s_pd[e] = pd32[(e & ~3) | ((e & 1) << 1) | ((e >> 1) & 1)];
+    } else {
+        // (m00, m01, m10, m11) -> (m00, m10, m01, m11): columns become aligned pairs
+        for (int e = threadIdx.x; e < S * 768; e += 256) s_pl[e] = pl32[(e & ~3) | ((e & 1) << 1) | ((e >> 1) & 1)];
+        if (threadIdx.x < S * 16) {
+            const int e = threadIdx.x;
+            s_pd[e] = pd32[(e & ~3) | ((e & 1) << 1) | ((e >> 1) & 1)];
+        }
     }
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const long item = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+    const long item = BANK ? (long)blockIdx.x
+                           : (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
     if (item >= items) return;
     const int c = (int)(item / segs), seg = (int)(item - (long)c * segs);
     const int skip = seg > 0 ? warm : 0;
@@ -477,9 +502,16 @@ k_iir_cascade_wave_pk(const float *__restrict__ in, float *__restrict__ out,
 #define LLZ_PK_TIE asm volatile("" : "+v"(U[0]), "+v"(U[7]))
 #define LLZ_PK_FETCH(SEC, HX, CX, TX)                                                                                \
     {                                                                                                                \
-        const lds_cv_f4v *tl = (const lds_cv_f4v *)(s_pl + ((SEC) * 64 + lane) * 12);                                \
         const lds_cv_f4v *tp = (const lds_cv_f4v *)(s_pd + (SEC) * 16);                                              \
-        TX.l0 = tl[0]; TX.l1 = tl[1]; TX.l2 = tl[2];                                                                 \
+        if constexpr (BANK) {                                                                                        \
+            const float *ts = s_pl + (SEC) * 448;                                                                    \
+            TX.l0 = *(const lds_cv_f4v *)(ts + 4 * lane);                                                            \
+            TX.l1 = *(const lds_cv_f4v *)(ts + 256 + 4 * (lane & 15));                                               \
+            TX.l2 = *(const lds_cv_f4v *)(ts + 320 + 4 * (lane & 31));                                               \
+        } else {                                                                                                     \
+            const lds_cv_f4v *tl = (const lds_cv_f4v *)(s_pl + ((SEC) * 64 + lane) * 12);                            \
+            TX.l0 = tl[0]; TX.l1 = tl[1]; TX.l2 = tl[2];                                                             \
+        }                                                                                                            \
         TX.p0 = tp[0]; TX.p1 = tp[1]; TX.p2 = tp[2]; TX.p3 = tp[3];                                                  \
         asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %4"                                        \
                      : "=&s"(HX), "=&s"(CX) : "s"(ph32), "n"((SEC) * 96), "n"((SEC) * 96 + 64) : "memory");           \
@@ -806,6 +838,8 @@ __device__ __forceinline__ void pf_section(double (&u)[16], const d4v c4, const 
     sy1 = lane63_(y1); sy2 = lane63_(y2);
 }
 
+// (No bank instance: one item per workgroup with its channel's 28.7 KB image leaves 4 waves per CU, and the bank pipeline
+//  measured faster on every timed shape: DESIGN.md K2c.)
 template <int S>
 __global__ void __launch_bounds__(256)
 k_iir_cascade_wave_pf64(const float *__restrict__ in, float *__restrict__ out,
@@ -1118,7 +1152,8 @@ extern "C" int llzs_iir_df1_f64(const double *in, double *out, const double *a, 
     return LLZ_OK;
 }
 
-extern "C" int llzs_iir_cascade_f32(const float *in, float *out, const double *coef, double *state, int channels,
+// bank: coef = [channels][stages][5], a set per channel (k_iir_cascade_f32<S, true>), else one set
+static int iir_cascade_lanes_launch(bool bank, const float *in, float *out, const double *coef, double *state, int channels,
                                     int n, long in_pitch, long out_pitch, int stages, void *stream)
 {
     if (!in || !out || !coef || !state || channels <= 0 || n <= 0 || stages < 1 || stages > 16 ||
@@ -1129,16 +1164,28 @@ extern "C" int llzs_iir_cascade_f32(const float *in, float *out, const double *c
     }
     dim3 grid((unsigned)((channels + CAS_TILE - 1) / CAS_TILE));
 #define LLZ_CAS_LAUNCH(S)                                                                                       \
-    hipLaunchKernelGGL(k_iir_cascade_f32<S>, grid, dim3(64), 0, as_stream(stream), in, out, coef, state,       \
-                       channels, n, in_pitch, out_pitch, stages)
+    hipLaunchKernelGGL((bank ? k_iir_cascade_f32<S, true> : k_iir_cascade_f32<S>), grid, dim3(64), 0, as_stream(stream), in, \
+                       out, coef, state, channels, n, in_pitch, out_pitch, stages)
     if (stages <= 1) LLZ_CAS_LAUNCH(1);
     else if (stages <= 2) LLZ_CAS_LAUNCH(2);
     else if (stages <= 4) LLZ_CAS_LAUNCH(4);
     else if (stages <= 8) LLZ_CAS_LAUNCH(8);
     else LLZ_CAS_LAUNCH(16);
 #undef LLZ_CAS_LAUNCH
-    LLZ_LAUNCH_CHECK("k_iir_cascade_f32");
+    LLZ_LAUNCH_CHECK(bank ? "k_iir_cascade_f32<bank>" : "k_iir_cascade_f32");
     return LLZ_OK;
+}
+
+extern "C" int llzs_iir_cascade_f32(const float *in, float *out, const double *coef, double *state, int channels,
+                                    int n, long in_pitch, long out_pitch, int stages, void *stream)
+{
+    return iir_cascade_lanes_launch(false, in, out, coef, state, channels, n, in_pitch, out_pitch, stages, stream);
+}
+
+extern "C" int llzs_iir_bank_f32(const float *in, float *out, const double *coef, double *state, int channels,
+                                 int n, long in_pitch, long out_pitch, int stages, void *stream)
+{
+    return iir_cascade_lanes_launch(true, in, out, coef, state, channels, n, in_pitch, out_pitch, stages, stream);
 }
 
 // ---- time segments: one plan for the stage pipeline and every wave form ----
@@ -1196,10 +1243,25 @@ static iir_plan iir_pipe_plan(int channels, int nchunks, int warm_chunks)
 
 // pd: [stages][6][4] = P^(2^d) row major, P = A^16; pl: [stages][64][12] = P^lane, P^(lane%16+1), P^(lane%32+1).  n must be a multiple of 1024 and
 // the rows 16-byte aligned (pitches % 4 == 0); the caller runs the remainder through llzs_iir_cascade_f32.
-extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const double *coef, const double *pd,
-                                         const double *pl, const double *state_in, double *state, int channels, int n,
-                                         long in_pitch, long out_pitch, int stages, int warm_chunks, int float32,
-                                         void *stream)
+// one typed launch per instance: R the working precision, BANK the tables per channel
+template <typename R, bool BANK>
+static int iir_pipe_launch_as(const float *in, float *out, const double *coef, const double *pd, const double *pl,
+                              const double *state_in, double *state, int channels, int nchunks, long in_pitch, long out_pitch,
+                              int stages, const iir_plan &p, size_t lds, void *stream)
+{
+    if (lds > 64 * 1024)
+        LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_iir_cascade_pipe<R, 16, BANK>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_iir_cascade_pipe<R, 16, BANK>), dim3((unsigned)((long)channels * p.segs)), dim3(64 * stages), lds,
+                       as_stream(stream), in, out, coef, pd, pl, state_in, state, nchunks, in_pitch, out_pitch, stages, p.segs,
+                       p.seg_chunks, p.warm);
+    LLZ_LAUNCH_CHECK(BANK ? "k_iir_cascade_pipe<bank>" : "k_iir_cascade_pipe");
+    return LLZ_OK;
+}
+
+static int iir_pipe_launch(bool bank, const float *in, float *out, const double *coef, const double *pd,
+                           const double *pl, const double *state_in, double *state, int channels, int n,
+                           long in_pitch, long out_pitch, int stages, int warm_chunks, int float32, void *stream)
 {
     // 16 samples per lane in both precisions: 32 in float32 measured slower (4.27 vs 3.62 ms: 128 VGPRs with spills under
     // the 1024-thread bound, and twice as long dependent recurrences per lane)
@@ -1212,34 +1274,40 @@ extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const doub
         return LLZ_ERR_ARG;
     }
     const size_t lds = (size_t)(stages > 1 ? stages - 1 : 1) * chunk * (float32 ? sizeof(float) : sizeof(double));
-    if (lds > 64 * 1024) {
-        if (float32)
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_iir_cascade_pipe<float, 16>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        else
-            LLZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_iir_cascade_pipe<double, 16>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
     const int nchunks = n / chunk;
     const iir_plan p = iir_pipe_plan(channels, nchunks, warm_chunks);
-    const int segs = p.segs, seg_chunks = p.seg_chunks, warm = p.warm;
-    if (float32)
-        hipLaunchKernelGGL((k_iir_cascade_pipe<float, 16>), dim3((unsigned)((long)channels * segs)), dim3(64 * stages), lds,
-                           as_stream(stream), in, out, coef, pd, pl, state_in, state, nchunks, in_pitch, out_pitch, stages, segs,
-                           seg_chunks, warm);
-    else
-        hipLaunchKernelGGL((k_iir_cascade_pipe<double, 16>), dim3((unsigned)((long)channels * segs)), dim3(64 * stages), lds,
-                           as_stream(stream), in, out, coef, pd, pl, state_in, state, nchunks, in_pitch, out_pitch, stages, segs,
-                           seg_chunks, warm);
-    LLZ_LAUNCH_CHECK("k_iir_cascade_pipe");
-    return LLZ_OK;
+#define LLZ_PIPE_AS(R, B) iir_pipe_launch_as<R, B>(in, out, coef, pd, pl, state_in, state, channels, nchunks, in_pitch, out_pitch, \
+                                                   stages, p, lds, stream)
+    if (bank) return float32 ? LLZ_PIPE_AS(float, true) : LLZ_PIPE_AS(double, true);
+    return float32 ? LLZ_PIPE_AS(float, false) : LLZ_PIPE_AS(double, false);
+#undef LLZ_PIPE_AS
+}
+
+extern "C" int llzs_iir_cascade_pipe_f32(const float *in, float *out, const double *coef, const double *pd,
+                                         const double *pl, const double *state_in, double *state, int channels, int n,
+                                         long in_pitch, long out_pitch, int stages, int warm_chunks, int float32,
+                                         void *stream)
+{
+    return iir_pipe_launch(false, in, out, coef, pd, pl, state_in, state, channels, n, in_pitch, out_pitch, stages, warm_chunks,
+                           float32, stream);
+}
+
+extern "C" int llzs_iir_bank_pipe_f32(const float *in, float *out, const double *coef, const double *pd,
+                                      const double *pl, const double *state_in, double *state, int channels, int n,
+                                      long in_pitch, long out_pitch, int stages, int warm_chunks, int float32,
+                                      void *stream)
+{
+    return iir_pipe_launch(true, in, out, coef, pd, pl, state_in, state, channels, n, in_pitch, out_pitch, stages, warm_chunks,
+                           float32, stream);
 }
 
 // ---- the wave-autonomous forms: one row each, one argument check, one slot query, one launch ----
 
-#define IIR_WAVE_INSTANCES(K)                                                                                          \
-    {(const void *)K<1>, (const void *)K<2>, (const void *)K<3>, (const void *)K<4>, (const void *)K<5>,              \
-     (const void *)K<6>, (const void *)K<7>, (const void *)K<8>}
+#define IIR_WAVE_INSTANCES(K, ...)                                                                                     \
+    {(const void *)K<1 __VA_ARGS__>, (const void *)K<2 __VA_ARGS__>, (const void *)K<3 __VA_ARGS__>,                  \
+     (const void *)K<4 __VA_ARGS__>, (const void *)K<5 __VA_ARGS__>, (const void *)K<6 __VA_ARGS__>,                  \
+     (const void *)K<7 __VA_ARGS__>, (const void *)K<8 __VA_ARGS__>}
+#define IIR_BANK , true
 
 // One wave kernel: a wave owns a (channel, time segment) item and runs all of its 1..8 sections in registers (16 would
 // spill), four items per workgroup.  Parameters: in, out, three tables, state_in, state, nchunks, the pitches, the plan,
@@ -1251,14 +1319,17 @@ struct iir_wave_row {
     unsigned lds;               // dynamic LDS bytes
     bool cf_first;              // the tables' parameter order: (cf, pd, pl), else (pd, pl, cf)
     int gain_bytes;             // the input gain is the last parameter, as a float (4) or a double (8); 0: none
+    int block;                  // threads per workgroup: 256 = four items, 64 = one (the bank forms: tables per channel)
 };
-static const iir_wave_row IIR_WAVE_ROWS[LLZS_IIR_WAVE_FORMS] = {        // by LLZS_IIR_WAVE16_F32 .. LLZS_IIR_WAVE32_F64
-    {"k_iir_cascade_wave_pk", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk), 16, 0, false, 0},
-    {"k_iir_cascade_wave_pf64", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pf64), 16, 4 * 1280 * sizeof(float), true, 0},
-    {"k_iir_cascade_wave_pk32", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk32), 32, 0, false, 4},
-    {"k_iir_cascade_wave_pf64w", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pf64w), 32, 0, true, 8},
+static const iir_wave_row IIR_WAVE_ROWS[LLZS_IIR_WAVE_FORMS] = {        // by LLZS_IIR_WAVE16_F32 .. LLZS_IIR_BANK16_F32
+    {"k_iir_cascade_wave_pk", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk), 16, 0, false, 0, 256},
+    {"k_iir_cascade_wave_pf64", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pf64), 16, 4 * 1280 * sizeof(float), true, 0, 256},
+    {"k_iir_cascade_wave_pk32", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk32), 32, 0, false, 4, 256},
+    {"k_iir_cascade_wave_pf64w", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pf64w), 32, 0, true, 8, 256},
+    {"k_iir_cascade_wave_pk<bank>", IIR_WAVE_INSTANCES(k_iir_cascade_wave_pk, IIR_BANK), 16, 0, false, 0, 64},
 };
 #undef IIR_WAVE_INSTANCES
+#undef IIR_BANK
 
 // waves of a kernel the chip holds (queried once per kernel and process: same answer on every device of a node)
 static long iir_wave_slots(int form, int stages)
@@ -1269,17 +1340,20 @@ static long iir_wave_slots(int form, int stages)
     long &slots = seen[form][stages - 1];
     if (!slots) {
         int blocks_per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, IIR_WAVE_ROWS[form].kernel[stages - 1], 256, 0) !=
+        const iir_wave_row &row = IIR_WAVE_ROWS[form];
+        // (the four-item forms have always been asked about without their dynamic LDS, and their plans stay as they are)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, row.kernel[stages - 1], row.block,
+                                                         row.block == 256 ? 0 : row.lds) !=
                 hipSuccess || blocks_per_cu < 1) {
             (void)hipGetLastError();
-            blocks_per_cu = 2;
+            blocks_per_cu = 512 / row.block;
         }
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
             (void)hipGetLastError();
             cus = 256;
         }
-        slots = 4L * blocks_per_cu * cus;
+        slots = (long)(IIR_WAVE_ROWS[form].block / 64) * blocks_per_cu * cus;
     }
     return slots;
 }
@@ -1350,7 +1424,8 @@ extern "C" int llzs_iir_cascade_wave(int form, const llzs_iir_wave_tables *t, co
     void *args[15] = {&in, &out, &t0, &t1, &t2, &state_in, &state, &nchunks, &in_pitch, &out_pitch, &p.segs, &p.seg_chunks,
                       &p.warm, &items, row.gain_bytes == 4 ? (void *)&gain32 : (void *)&gain64};
     if (row.lds) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)row.lds);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), args, row.lds, as_stream(stream));
+    const int per_wg = row.block / 64;
+    (void)hipLaunchKernel(kernel, dim3((unsigned)((items + per_wg - 1) / per_wg)), dim3(row.block), args, row.lds, as_stream(stream));
     LLZ_LAUNCH_CHECK(row.name);
     return LLZ_OK;
 }

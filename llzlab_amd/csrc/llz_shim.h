@@ -170,9 +170,15 @@ int llzs_iir_cascade_pipe_f32(const float *in, float *out, const double *coef, c
  *   WAVE32_F32  k_iir_cascade_wave_pk32  floats: cf [S][40] = (h1[k], h2[k]) k < 16, then 1 b1' b2' a1 a2 xfac yfac pad; pd, pl
  *                                        as for WAVE16_F32
  *   WAVE32_F64  k_iir_cascade_wave_pf64w doubles: cf [S][8] = b1', b2', a1, a2, xfac, yfac, 0, 0; pd [S][16]; pl [S][448] =
- *                                        P^lane for 64 lanes, P^(i+1) i < 16, P^(i+1) i < 32 */
-enum { LLZS_IIR_WAVE16_F32, LLZS_IIR_WAVE16_F64, LLZS_IIR_WAVE32_F32, LLZS_IIR_WAVE32_F64, LLZS_IIR_WAVE_FORMS };
-#define LLZS_IIR_WAVE_CHUNK(form) ((form) >= LLZS_IIR_WAVE32_F32 ? 2048 : 1024)
+ *                                        P^lane for 64 lanes, P^(i+1) i < 16, P^(i+1) i < 32
+ *   BANK16_F32  k_iir_cascade_wave_pk<S, true>    the tables of WAVE16_F32 per channel: cf [C][S][24], pd [C][S][16],
+ *                                        pl [C][S][64][12]
+ * The bank form (llz_iir_bank_mc: a coefficient set per channel) runs one item per 64-thread workgroup; a bank in double has
+ * no wave form (the bank pipeline measured faster). */
+enum { LLZS_IIR_WAVE16_F32, LLZS_IIR_WAVE16_F64, LLZS_IIR_WAVE32_F32, LLZS_IIR_WAVE32_F64, LLZS_IIR_BANK16_F32,
+       LLZS_IIR_WAVE_FORMS };
+#define LLZS_IIR_WAVE_IS32(form) ((form) == LLZS_IIR_WAVE32_F32 || (form) == LLZS_IIR_WAVE32_F64)
+#define LLZS_IIR_WAVE_CHUNK(form) (LLZS_IIR_WAVE_IS32(form) ? 2048 : 1024)
 typedef struct {
     const void *cf, *pd, *pl;
     double in_gain;             /* the 32-sample forms scale the input once */
@@ -180,6 +186,13 @@ typedef struct {
 int llzs_iir_cascade_wave(int form, const llzs_iir_wave_tables *t, const float *in, float *out, const double *state_in,
                           double *state_out, int channels, int n, long in_pitch, long out_pitch, int stages, int warm_chunks,
                           void *stream);
+/* the tail and the stage pipeline with a coefficient set per channel (llz_iir_bank_mc): the same arguments, with coef
+ * [channels][stages][5], pd [channels][stages][6][4], pl [channels][stages][64][12] */
+int llzs_iir_bank_f32(const float *in, float *out, const double *coef, double *state,
+                      int channels, int n, long in_pitch, long out_pitch, int stages, void *stream);
+int llzs_iir_bank_pipe_f32(const float *in, float *out, const double *coef, const double *pd, const double *pl,
+                           const double *state_in, double *state_out, int channels, int n, long in_pitch, long out_pitch,
+                           int stages, int warm_chunks, int float32, void *stream);
 /* the plan such a launch of n samples would run with, nothing launched: form < 0 the stage pipeline, else a wave form;
  * out = {segments per channel, chunks per segment, warm-up chunks} in chunks of the form's own size */
 int llzs_iir_cascade_plan(int form, int channels, int n, int stages, int warm_chunks, int out[3]);

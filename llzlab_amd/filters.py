@@ -289,6 +289,57 @@ class IirCascadeMC:
     __del__ = close
 
 
+class IirBankMC:
+    """channels x n float32 through a cascade of biquads PER CHANNEL: llz_iir_bank_mc_*.  coef: [channels, stages, 6], rows
+    {b0,b1,b2,a0,a1,a2}; a channel with fewer sections pads with identity sections {1,0,0,1,0,0}."""
+
+    def __init__(self, channels, coef, stream=None):
+        self._L = capi.lib()
+        coef = _f64(coef)
+        if coef.ndim != 3 or coef.shape[0] != channels or coef.shape[1] < 1 or coef.shape[2] != 6:
+            raise LlzError(f"IirBankMC: coef must be [channels = {channels}, stages, 6], got {coef.shape} "
+                           "(one coefficient set for every channel is IirCascadeMC)")
+        self.channels, self.stages = channels, coef.shape[1]
+        self.handle = check_handle(self._L.llz_iir_bank_mc_init(channels, self.stages, coef.ctypes.data),
+                                   "llz_iir_bank_mc_init")
+        if stream is not None:
+            check(self._L.llz_iir_bank_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_iir_bank_mc_set_stream")
+
+    @property
+    def precision(self):
+        """32 or 64: the arithmetic of the fast kernels, the handle's verdict over every channel's set (set_coef may change it)"""
+        return check(self._L.llz_iir_bank_mc_precision(self.handle), "llz_iir_bank_mc_precision")
+
+    def set_coef(self, first, coef):
+        """replace the sets of channels first .. first + len(coef) - 1, state kept; coef: [count, stages, 6]"""
+        coef = _f64(coef)
+        if coef.ndim != 3 or coef.shape[1:] != (self.stages, 6):
+            raise LlzError(f"IirBankMC.set_coef: coef must be [count, stages = {self.stages}, 6], got {coef.shape}")
+        check(self._L.llz_iir_bank_mc_set_coef(self.handle, int(first), coef.shape[0], coef.ctypes.data),
+              "llz_iir_bank_mc_set_coef")
+
+    def filter(self, x, out):
+        n = x.shape[-1]
+        check(self._L.llz_iir_bank_mc(self.handle, _typed(x, "float32", self.channels * n, "IirBankMC.filter x"),
+                                      _typed(out, "float32", self.channels * n, "IirBankMC.filter out"), n),
+              "llz_iir_bank_mc")
+        return out
+
+    def plan(self, n):
+        """as IirCascadeMC.plan (llz_iir_bank_mc_plan; nothing is launched); the bank has no "wave32" form"""
+        out = (C.c_int * 5)()
+        check(self._L.llz_iir_bank_mc_plan(self.handle, int(n), out), "llz_iir_bank_mc_plan")
+        return {"form": IIR_FORMS[out[0]], "chunk": 2048 if out[0] == 2 else 1024, "precision": out[1], "segs": out[2],
+                "seg_chunks": out[3], "warm": out[4]}
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_iir_bank_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ resample
 class IirMC:
     """llz_iir_mc_* (include/llz_iir.h part 3): the general direct-form-I filter for many channels, float32 in / out."""
