@@ -64,13 +64,17 @@ double llz_conv(const double *x, const double *h, int h_len);
 enum {
     LLZ_FIR_ALGO_AUTO = 0,       /* time domain up to 32 taps, overlap-save for 33..257 (1024-point), 258..513
                                   * (2048-point), 514..1025 (4096-point) and 1026..6145 (8192-point), matrix-core time
-                                  * domain beyond */
+                                  * domain beyond (never LLZ_FIR_ALGO_PARTITIONED) */
     LLZ_FIR_ALGO_TIME = 1,       /* direct form, taps broadcast, input window staged in LDS */
     LLZ_FIR_ALGO_OVERLAP_SAVE = 2, /* 1024-point in-LDS FFT overlap-save, flt_len <= 257 */
     LLZ_FIR_ALGO_TIME_MFMA = 3,   /* direct form as a banded Toeplitz product on the fp32 matrix cores */
     LLZ_FIR_ALGO_OVERLAP_SAVE_2048 = 4, /* 2048-point register-transform overlap-save, 2 <= flt_len <= 1025 */
     LLZ_FIR_ALGO_OVERLAP_SAVE_4096 = 5, /* 4096-point register-transform overlap-save, 2 <= flt_len <= 3073 */
-    LLZ_FIR_ALGO_OVERLAP_SAVE_8192 = 6  /* 8192-point register-transform overlap-save on pairs of waves, 2 <= flt_len <= 6145 */
+    LLZ_FIR_ALGO_OVERLAP_SAVE_8192 = 6, /* 8192-point register-transform overlap-save on pairs of waves, 2 <= flt_len <= 6145 */
+    LLZ_FIR_ALGO_PARTITIONED = 7        /* uniformly partitioned overlap-save with the block spectra in device memory,
+                                         * 1 <= flt_len <= 131073: the form for long filters, whose cost per sample grows with
+                                         * flt_len / block instead of flt_len.  Never chosen by AUTO: name it.  (The other algos
+                                         * end at 25248 taps, the time-domain kernel's LDS tile.) */
 };
 
 /* channels independent filters sharing one tap set. taps: HOST pointer, flt_len floats (double variant
@@ -93,6 +97,13 @@ int llz_fir_filter_mc(unsigned long handle, const float *in, float *out, int fra
 int llz_fir_filter_mc_flush(unsigned long handle, float *out);
 int llz_fir_filter_mc_flt_len(unsigned long handle);
 int llz_fir_filter_mc_algo(unsigned long handle);
+/* LLZ_FIR_ALGO_PARTITIONED keeps the contract above.  Each call filters concat(history, frame) from scratch -- nothing spectral
+ * is carried from call to call -- so a call costs about frame_len + flt_len samples of work: a frame much shorter than the
+ * filter is legal but wasteful.  The flush runs through the same kernels.  The block spectra live in scratch allocated at init
+ * from frame_len (at most 1 GiB; the channels go in passes of as many as fit; init fails when not one does).
+ * out = {transform points N, partitions P = ceil(flt_len / (N / 2)), channels per pass, passes} for a call of n samples under
+ * the tunes set now; nothing is launched.  LLZ_ERR_ARG for a handle of another algo. */
+int llz_fir_filter_mc_partition_plan(unsigned long handle, int n, int out[4]);
 /* stream: a hipStream_t passed as void* (NULL = default stream) */
 int llz_fir_filter_mc_set_stream(unsigned long handle, void *stream);
 

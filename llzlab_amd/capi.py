@@ -19,6 +19,7 @@ HAMMING, BLACKMAN, KAISER = 0, 1, 2
 FIR_ALGO_AUTO, FIR_ALGO_TIME, FIR_ALGO_OVERLAP_SAVE, FIR_ALGO_TIME_MFMA, FIR_ALGO_OVERLAP_SAVE_2048 = 0, 1, 2, 3, 4
 FIR_ALGO_OVERLAP_SAVE_4096 = 5
 FIR_ALGO_OVERLAP_SAVE_8192 = 6
+FIR_ALGO_PARTITIONED = 7
 OVERLAP_HIGH, OVERLAP_LOW = 0, 1      # llz_asmodel.h: 3/4 and 1/2 overlap
 MDCT_ORIGIN, MDCT_FFT, MDCT_FFT4 = 0, 1, 2
 MDCT_SINE, MDCT_KBD = 0, 1
@@ -135,6 +136,7 @@ def lib():
     sig("llz_fir_filter_mc_flush", i, ul, vp)
     sig("llz_fir_filter_mc_flt_len", i, ul)
     sig("llz_fir_filter_mc_algo", i, ul)
+    sig("llz_fir_filter_mc_partition_plan", i, ul, i, C.POINTER(C.c_int))
     sig("llz_fir_filter_mc_set_stream", i, ul, vp)
     # llz_fir.h part 3
     sig("llz_fir_bank_mc_init", ul, i, i, vp, i, i)

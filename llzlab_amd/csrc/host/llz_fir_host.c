@@ -153,6 +153,10 @@ typedef struct {
     float *d_hist[2];           /* [channels][flt_len-1], ping-pong */
     int cur;
     float *d_zero;              /* [channels][flt_len-1] zeros: flush input */
+    int part_n;                 /* LLZ_FIR_ALGO_PARTITIONED: transform points, fixed at init (0 for every other algo) */
+    float *d_hpart, *d_ptw;     /* ... [P][part_n] partition spectra and [part_n / 2] twiddles (llzs_fir_part_f32) */
+    float *d_scratch;           /* ... block spectra of one pass of channels */
+    size_t scratch_bytes;
     void *stream;
     llz_stage_t st_in, st_out;  /* only for callers passing host memory */
 } firm_t;
@@ -162,6 +166,7 @@ static void firm_destroy(firm_t *f)
     if (!f) return;
     llzs_free(f->d_taps); llzs_free(f->d_hbank); llzs_free(f->ols.hfreq); llzs_free(f->ols.twid); llzs_free(f->ols.tw2k); llzs_free(f->ols.tw4k);
     llzs_free(f->d_hist[0]); llzs_free(f->d_hist[1]); llzs_free(f->d_zero);
+    llzs_free(f->d_hpart); llzs_free(f->d_ptw); llzs_free(f->d_scratch);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     f->tag = 0;
     free(f);
@@ -252,14 +257,115 @@ static int firm_build_ols_tables(firm_t *f, const float *taps, int N)
     return rc;
 }
 
+/* ---- LLZ_FIR_ALGO_PARTITIONED: uniformly partitioned overlap-save (fir_part.hip) ---- */
+
+/* transform points by tap count: the smallest size that keeps the filter within 4 partitions, 8192 beyond.  The product kernel
+ * reads (16 + P - 1) / 16 spectra per output block, so few partitions keep its scratch traffic near one read per block, and a
+ * smaller transform wastes less of a short call; from 16385 taps on only more partitions remain. */
+static int firm_part_nfft(int flt_len)
+{
+    const int forced = llzs_tune(LLZS_TUNE_PART_NFFT);
+    if (forced == 1024 || forced == 2048 || forced == 4096 || forced == 8192) return forced;
+    int n = 1024;
+    while (n < 8192 && flt_len > 4 * (n / 2)) n *= 2;
+    return n;
+}
+
+/* the scratch cap in bytes: 1 GiB, or what the part_scratch_mb tune says (1 .. 1024 MiB) */
+static size_t firm_part_cap(void)
+{
+    const int mb = llzs_tune(LLZS_TUNE_PART_SCRATCH_MB);
+    return (size_t)((mb >= 1 && mb <= 1024) ? mb : 1024) << 20;
+}
+
+/* the partition spectra, the twiddles and the scratch of an algo-7 handle.  H_p = DFT_N(taps[p B .. p B + B), zero-padded) / N
+ * by a radix-2 decimation-in-frequency transform in double (twiddles from a quadrant-exact table), rounded to float once and
+ * left in that transform's output order (entry i = bin bitrev(i)): the device's forward transform leaves its bins in the same
+ * order, and the product is bin-wise.  33 x 8192 points at 131073 taps: milliseconds, where the direct DFT of
+ * firm_build_ols_tables would sum 10^9 terms. */
+static int firm_build_part(firm_t *f, const float *taps)
+{
+    const int N = firm_part_nfft(f->flt_len), B = N / 2, keep = f->flt_len - 1;
+    const int P = (f->flt_len + B - 1) / B;
+    const size_t cap = firm_part_cap();
+    size_t need = 0, need_flush = 0;            /* per channel: a frame, and the flush's flt_len - 1 zeros */
+    if (llzs_fir_part_need(N, f->flt_len, f->frame_len, &need) != LLZ_OK) return LLZ_ERR_ARG;
+    if (keep > 0 && llzs_fir_part_need(N, f->flt_len, keep, &need_flush) != LLZ_OK) return LLZ_ERR_ARG;
+    if (need_flush > need) need = need_flush;
+    if (need > cap) {
+        llzs_set_error("llz_fir_filter_mc_init: one channel of %d samples at %d taps (%d-point partitions) needs %zu B of scratch, "
+                       "the cap is %zu B", f->frame_len > keep ? f->frame_len : keep, f->flt_len, N, need, cap);
+        return LLZ_ERR_NOMEM;
+    }
+    f->part_n = N;
+    f->scratch_bytes = need * (size_t)f->channels < cap ? need * (size_t)f->channels : cap;
+    const size_t hcount = 2 * (size_t)P * (size_t)N;
+    float *hp = (float *)malloc(sizeof(float) * hcount);
+    float *tw = (float *)malloc(sizeof(float) * (size_t)N);
+    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    int rc = (hp && tw && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {
+        for (int i = 0; i < N; i++) {
+            const double ang = 2.0 * M_PI * (double)i / (double)N;
+            cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
+            cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
+        }
+        for (int m = 0; m < N / 2; m++) firm_w(&tw[2 * m], cs, m);
+        for (int p = 0; p < P; p++) {
+            for (int i = 0; i < N; i++) {
+                const long t = (long)p * B + i;
+                z[2 * i] = (i < B && t < f->flt_len) ? (double)taps[t] : 0.0;
+                z[2 * i + 1] = 0.0;
+            }
+            for (int span = N; span >= 2; span /= 2) {
+                const int half = span / 2, step = N / span;
+                for (int base = 0; base < N; base += span)
+                    for (int j = 0; j < half; j++) {
+                        double *a = z + 2 * (base + j), *b = a + 2 * half;
+                        const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
+                        const double dr = a[0] - b[0], di = a[1] - b[1];
+                        a[0] += b[0]; a[1] += b[1];
+                        b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
+                    }
+            }
+            float *row = hp + 2 * (size_t)p * (size_t)N;
+            for (int i = 0; i < 2 * N; i++) row[i] = (float)(z[i] / N);
+        }
+        f->d_hpart = (float *)llzs_malloc(sizeof(float) * hcount);
+        f->d_ptw = (float *)llzs_malloc(sizeof(float) * (size_t)N);
+        f->d_scratch = (float *)llzs_malloc(f->scratch_bytes);
+        if (!f->d_hpart || !f->d_ptw || !f->d_scratch) rc = LLZ_ERR_NOMEM;
+    }
+    /* tables through llzs_h2d_table, in a fixed order: a sharded init records and broadcasts them */
+    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_hpart, hp, sizeof(float) * hcount);
+    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_ptw, tw, sizeof(float) * (size_t)N);
+    free(hp); free(tw); free(cs); free(z);
+    return rc;
+}
+
+/* what a call of n samples may use of the scratch now: the allocation, or less under the part_scratch_mb tune */
+static size_t firm_part_avail(const firm_t *f)
+{
+    const size_t cap = firm_part_cap();
+    return cap < f->scratch_bytes ? cap : f->scratch_bytes;
+}
+
 unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *taps, int flt_len, int algo)
 {
     if (channels < 1 || channels > 65535 || frame_len < 1 || !taps || flt_len < 1) {
         llzs_set_error("llz_fir_filter_mc_init: channels %d frame_len %d flt_len %d", channels, frame_len, flt_len);
         return LLZ_BAD_HANDLE;
     }
-    if (!llzs_fir_td_f32_fits(flt_len)) {
-        /* every handle flushes through the time-domain kernel (and AUTO falls back to it): refuse here, not at the first call */
+    if (algo == LLZ_FIR_ALGO_PARTITIONED) {
+        if (flt_len > LLZS_FIR_PART_MAX_TAPS) {
+            llzs_set_error("llz_fir_filter_mc_init: the partitioned overlap-save takes 1..%d taps, not %d", LLZS_FIR_PART_MAX_TAPS,
+                           flt_len);
+            return LLZ_BAD_HANDLE;
+        }
+    } else if (!llzs_fir_td_f32_fits(flt_len)) {
+        /* every such handle flushes through the time-domain kernel (and AUTO falls back to it): refuse here, not at the first
+         * call.  The partitioned form flushes through itself. */
         llzs_set_error("llz_fir_filter_mc_init: %d taps exceed the time-domain kernel's LDS tile", flt_len);
         return LLZ_BAD_HANDLE;
     }
@@ -280,7 +386,7 @@ unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *t
         llzs_set_error("llz_fir_filter_mc_init: %d taps do not fit the matrix-core kernel's LDS tile", flt_len);
         return LLZ_BAD_HANDLE;
     }
-    if (!ols && algo != LLZ_FIR_ALGO_TIME && algo != LLZ_FIR_ALGO_TIME_MFMA) {
+    if (!ols && algo != LLZ_FIR_ALGO_TIME && algo != LLZ_FIR_ALGO_TIME_MFMA && algo != LLZ_FIR_ALGO_PARTITIONED) {
         llzs_set_error("llz_fir_filter_mc_init: unknown algo %d", algo);
         return LLZ_BAD_HANDLE;
     }
@@ -308,6 +414,7 @@ unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *t
     if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[1], 0, hist_bytes, NULL);
     if (rc == LLZ_OK) rc = llzs_memset(f->d_zero, 0, hist_bytes, NULL);
     if (rc == LLZ_OK && ols) rc = firm_build_ols_tables(f, taps, ols->nfft);
+    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_PARTITIONED) rc = firm_build_part(f, taps);
     if (rc == LLZ_OK) rc = llzs_sync(NULL);
     free(padded);
     if (rc != LLZ_OK) {
@@ -388,6 +495,16 @@ int llz_fir_filter_mc_algo(unsigned long handle)
     return LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM) ? ((firm_t *)handle)->algo : LLZ_ERR_ARG;
 }
 
+int llz_fir_filter_mc_partition_plan(unsigned long handle, int n, int out[4])
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM) || ((firm_t *)handle)->algo != LLZ_FIR_ALGO_PARTITIONED || n < 1 || !out) {
+        llzs_set_error("llz_fir_filter_mc_partition_plan: not a handle of LLZ_FIR_ALGO_PARTITIONED, n %d < 1 or no out", n);
+        return LLZ_ERR_ARG;
+    }
+    const firm_t *f = (const firm_t *)handle;
+    return llzs_fir_part_plan(f->part_n, f->flt_len, n, f->channels, firm_part_avail(f), out);
+}
+
 int llz_fir_filter_mc_set_stream(unsigned long handle, void *stream)
 {
     if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM)) return LLZ_ERR_ARG;
@@ -409,6 +526,9 @@ static int firm_launch(firm_t *f, const float *d_in, float *d_out, int n, long p
     else if (ols)
         rc = llzs_fir_ols_f32(ols->nfft, &f->ols, d_in, d_out, hist, f->channels, n, pitch_in, pitch_out, f->flt_len,
                               f->stream);
+    else if (algo == LLZ_FIR_ALGO_PARTITIONED)
+        rc = llzs_fir_part_f32(f->part_n, f->d_hpart, f->d_ptw, f->d_scratch, firm_part_avail(f), d_in, d_out, hist, f->channels, n,
+                               pitch_in, pitch_out, f->flt_len, f->stream);
     else if (algo == LLZ_FIR_ALGO_TIME_MFMA)
         rc = llzs_fir_mfma_f32(d_in, d_out, hist, f->d_taps, f->channels, n, n, pitch_in, pitch_out, f->flt_len, 1,
                                1.0f, f->stream);
@@ -495,8 +615,10 @@ static int firm_flush(firm_t *f, float *out)
         d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
         if (!d_out) return LLZ_ERR_NOMEM;
     }
-    /* flt_len-1 zeros per channel through the time-domain kernel (tiny; same arithmetic as the frames) */
-    int rc = firm_launch(f, f->d_zero, d_out, keep, keep, keep, LLZ_FIR_ALGO_TIME);
+    /* flt_len-1 zeros per channel through the time-domain kernel (tiny; same arithmetic as the frames); a partitioned handle
+     * through the partitioned launcher at every length: above 25248 taps the time-domain kernel cannot hold the filter */
+    int rc = firm_launch(f, f->d_zero, d_out, keep, keep, keep,
+                         f->algo == LLZ_FIR_ALGO_PARTITIONED ? LLZ_FIR_ALGO_PARTITIONED : LLZ_FIR_ALGO_TIME);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? keep : rc;
 }

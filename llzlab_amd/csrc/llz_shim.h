@@ -58,6 +58,8 @@ enum {
     LLZS_TUNE_LPC_SPLIT,            /* 1: batch LPC with p <= 32 as two launches (correlation, then recursion) like p > 32 */
     LLZS_TUNE_BANK_GLOBAL_H,        /* 1: filter-bank overlap-save reads each spectrum bin from global memory per job (the form
                                      * measured against and dropped: fir_bank.hip) instead of a half-wave's own LDS image */
+    LLZS_TUNE_PART_NFFT,            /* partitioned overlap-save: transform points (1024, 2048, 4096, 8192), read at init */
+    LLZS_TUNE_PART_SCRATCH_MB,      /* ... cap of the spectra scratch in MiB (1 .. 1024; the library's own: 1024), read at init and per call */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -138,6 +140,18 @@ int llzs_fir_mfma_i16x(const short *in, short *out, const short *hist, const sig
                        long long bias, double gain, double eps, void *stream);
 int llzs_fir_mfma_i16x_fits(int T, int M);
 #define LLZS_MX_PLANES 5
+/* uniformly partitioned overlap-save (fir_part.hip), 1..LLZS_FIR_PART_MAX_TAPS taps, nfft = 1024, 2048, 4096 or 8192, block
+ * B = nfft / 2, P = ceil(flt_len / B) partitions.  hpart = [P][nfft] complex floats, row p = DFT_nfft(taps[p B .. p B + B),
+ * zero-padded) / nfft in the ORDER OF A DECIMATION-IN-FREQUENCY TRANSFORM'S OUTPUT (entry i = bin bitrev(i)); tw = [nfft / 2]
+ * complex W_nfft^m.  scratch: device memory of scratch_bytes for the block spectra; the channels go in passes of as many as
+ * it holds (llzs_fir_part_need bytes each), LLZ_ERR_NOMEM when not one does.  llzs_fir_part_plan launches nothing:
+ * plan = {nfft, P, channels per pass, passes}. */
+#define LLZS_FIR_PART_MAX_TAPS 131073
+int llzs_fir_part_need(int nfft, int flt_len, int n, size_t *bytes);      /* scratch bytes of one channel */
+int llzs_fir_part_plan(int nfft, int flt_len, int n, int channels, size_t scratch_bytes, int plan[4]);
+int llzs_fir_part_f32(int nfft, const float *hpart, const float *tw, float *scratch, size_t scratch_bytes, const float *in,
+                      float *out, const float *hist, int channels, int n, long in_pitch, long out_pitch, int flt_len,
+                      void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (BAD_HANDLE, BLACKMAN, FIR_ALGO_AUTO, FIR_ALGO_OVERLAP_SAVE, FIR_ALGO_OVERLAP_SAVE_2048, FIR_ALGO_OVERLAP_SAVE_4096, FIR_ALGO_OVERLAP_SAVE_8192, FIR_ALGO_TIME,  # noqa: F401
+from .capi import (BAD_HANDLE, BLACKMAN, FIR_ALGO_AUTO, FIR_ALGO_OVERLAP_SAVE, FIR_ALGO_OVERLAP_SAVE_2048, FIR_ALGO_OVERLAP_SAVE_4096, FIR_ALGO_OVERLAP_SAVE_8192, FIR_ALGO_PARTITIONED, FIR_ALGO_TIME,  # noqa: F401
                    FIR_ALGO_TIME_MFMA, HAMMING, KAISER,
                    PCM_F32, PCM_I16, PCM_I16_FAST, LlzError, check, check_handle)
 
@@ -142,6 +142,13 @@ class FirFilterMC:
 
     def set_stream(self, stream):
         check(self._L.llz_fir_filter_mc_set_stream(self.handle, _stream_ptr(stream)), "set_stream")
+
+    def partition_plan(self, n):
+        """FIR_ALGO_PARTITIONED only: (transform points, partitions, channels per pass, passes) of a call of n samples under
+        the tunes set now (llz_fir_filter_mc_partition_plan; nothing is launched)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_fir_filter_mc_partition_plan(self.handle, int(n), out), "llz_fir_filter_mc_partition_plan")
+        return tuple(out)
 
     def filter(self, x, out):
         """x, out: [channels, frame_len] float32 (torch device tensors or numpy). Returns out."""
