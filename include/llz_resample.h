@@ -52,6 +52,14 @@ unsigned long llz_resample_mc_init(int channels, int L, int M, double gain, win_
 void          llz_resample_mc_uninit(unsigned long handle);
 int  llz_resample_mc_sub_len(unsigned long handle);                 /* Q */
 long llz_resample_mc_out_len(unsigned long handle, long n_in);      /* n_in*L/M; n_in*L must divide by M, else -1 */
+/* L and M are taken as given, not reduced by their gcd g.  With g > 1 a valid call (n_in a multiple of M/g) may end, and the
+ * next one start, inside a period of L outputs.  Such ragged calls give the same samples as whole-period calls; the
+ * matrix-core entries (resample_mfma_f32, resample_i16x) store whole periods, so a call that does not start on a period
+ * boundary (inputs so far % M == 0) or whose n_in*L/M is no multiple of L runs on the handle's fallback entry
+ * (resample_f32, resample_i16), at that entry's speed.  With coprime L and M every valid call is a whole number of periods. */
+/* the shim entry that produced the last successful call, by its name in the table of llz_resample_host.c ("resample_mfma_f32",
+ * "resample_f32", "resample_i16x", "resample_i16", "fir_mfma_f32", ...); "" before the first call, NULL for a bad handle */
+const char *llz_resample_mc_last_entry(unsigned long handle);
 /* in: planar [channels][n_in]; out: planar [channels][n_in*L/M]; device or host pointers of the handle's
  * sample format. History (Q-1 samples per channel) carries across calls. out may not overlap in (device memory):
  * refused with LLZ_ERR_ARG. Returns outputs per channel or <0. */

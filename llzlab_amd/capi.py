@@ -181,6 +181,7 @@ def lib():
     sig("llz_resample_mc_uninit", None, ul)
     sig("llz_resample_mc_sub_len", i, ul)
     sig("llz_resample_mc_out_len", lng, ul, lng)
+    sig("llz_resample_mc_last_entry", C.c_char_p, ul)
     sig("llz_resample_mc", lng, ul, vp, lng, vp)
     sig("llz_resample_mc_set_stream", i, ul, vp)
     sig("llz_resample_mc_get_matrix", i, ul, vp, i)

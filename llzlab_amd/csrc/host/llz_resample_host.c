@@ -264,8 +264,11 @@ int llz_resample(unsigned long handle, unsigned char *sample_in, int sample_in_s
  *   I16_FAST  fir_mfma_i16x        the screen takes the taps, rs_i16_path != 1              fir_mfma_i16
  *   I16_FAST  fir_mfma_i16         otherwise                                                -
  * A primary declines a call when rsm_path_ok refuses it or the entry returns LLZ_ERR_RANGE (a frame too short for a screened
- * kernel); the fallback then runs, and the primary's message stays in llz_hip_last_error().  RSM_TABLES lists the tables
- * each entry reads: a handle uploads those of its primary and its fallback, in the order of the TAB_ values. */
+ * kernel); the fallback then runs, and the primary's message stays in llz_hip_last_error().  resample_mfma_f32 and
+ * resample_i16x take whole periods only: the call starts on a period boundary (in_count % M == 0, out_count % L == 0) and
+ * n_out % L == 0.  With gcd(L, M) > 1 a call may end or start inside a period; the fallback takes those.  RSM_TABLES lists
+ * the tables each entry reads: a handle uploads those of its primary and its fallback, in the order of the TAB_ values;
+ * RSM_NAMES the names of this table, as llz_resample_mc_last_entry reports them. */
 typedef enum {
     RSM_NONE, RSM_FIR_MFMA_F32, RSM_DEC_F32, RSM_MFMA_F32, RSM_F32, RSM_FIR_MFMA_I16X, RSM_I16X, RSM_I16, RSM_FIR_MFMA_I16
 } rsm_path;
@@ -274,6 +277,11 @@ static const int RSM_TABLES[] = {
     [RSM_NONE] = 0, [RSM_FIR_MFMA_F32] = TAB_M32, [RSM_DEC_F32] = TAB_PHASE, [RSM_MFMA_F32] = TAB_BAND, [RSM_F32] = TAB_M32,
     [RSM_FIR_MFMA_I16X] = TAB_M64 | TAB_SCREEN, [RSM_I16X] = TAB_M64 | TAB_SCREEN, [RSM_I16] = TAB_M64, [RSM_FIR_MFMA_I16] = TAB_M32,
 };
+static const char *const RSM_NAMES[] = {
+    [RSM_NONE] = "", [RSM_FIR_MFMA_F32] = "fir_mfma_f32", [RSM_DEC_F32] = "resample_dec_f32", [RSM_MFMA_F32] = "resample_mfma_f32",
+    [RSM_F32] = "resample_f32", [RSM_FIR_MFMA_I16X] = "fir_mfma_i16x", [RSM_I16X] = "resample_i16x", [RSM_I16] = "resample_i16",
+    [RSM_FIR_MFMA_I16] = "fir_mfma_i16",
+};
 
 typedef struct {
     int tag;
@@ -281,6 +289,7 @@ typedef struct {
     double gain;
     tapmat_t taps;
     rsm_path primary, fallback;
+    rsm_path last;              /* the entry that produced the last successful call (RSM_NONE before the first) */
     void *d_m32;                /* TAB_M32: the L x Q taps as floats */
     void *d_m64;                /* TAB_M64: the L x Q taps as doubles (the all-double kernel, the screen's second looks) */
     void *d_band, *d_band_c0;   /* TAB_BAND: the banded tap matrix in matrix-core operand order (resample_mfma.hip) */
@@ -303,10 +312,11 @@ typedef struct {
     llz_stage_t st_in, st_out;
 } rsm_t;
 
-/* a path's call-time precondition: the period-tile kernels need the call to start on a period boundary */
-static int rsm_path_ok(const rsm_t *r, rsm_path p)
+/* a path's call-time precondition: the period-tile kernels store whole periods, so the call must start on a period boundary
+ * and hold a whole number of periods (with gcd(L, M) > 1 the public contract admits calls that do neither) */
+static int rsm_path_ok(const rsm_t *r, rsm_path p, long n_out)
 {
-    return (p != RSM_MFMA_F32 && p != RSM_I16X) || (r->in_count % r->M == 0 && r->out_count % r->L == 0);
+    return (p != RSM_MFMA_F32 && p != RSM_I16X) || (r->in_count % r->M == 0 && r->out_count % r->L == 0 && n_out % r->L == 0);
 }
 
 static size_t rsm_sample_bytes(const rsm_t *r) { return r->fmt == LLZ_PCM_F32 ? sizeof(float) : sizeof(short); }
@@ -620,6 +630,11 @@ long llz_resample_mc_out_len(unsigned long handle, long n_in)
     return (n_in * r->L) / r->M;
 }
 
+const char *llz_resample_mc_last_entry(unsigned long handle)
+{
+    return LLZ_HANDLE_OK(handle, rsm_t, LLZ_TAG_RSM) ? RSM_NAMES[((const rsm_t *)handle)->last] : NULL;
+}
+
 int llz_resample_mc_set_stream(unsigned long handle, void *stream)
 {
     if (!LLZ_HANDLE_OK(handle, rsm_t, LLZ_TAG_RSM)) return LLZ_ERR_ARG;
@@ -714,9 +729,13 @@ static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_i
         if (!d_out) return LLZ_ERR_NOMEM;
     }
     const void *hist = r->Q > 1 ? r->d_hist[r->cur] : NULL;
+    rsm_path ran = r->primary;
     if (rc == LLZ_OK) {
-        rc = rsm_path_ok(r, r->primary) ? rsm_run(r, r->primary, d_in, d_out, hist, n_in, n_out) : LLZ_ERR_RANGE;
-        if (rc == LLZ_ERR_RANGE && r->fallback != RSM_NONE) rc = rsm_run(r, r->fallback, d_in, d_out, hist, n_in, n_out);
+        rc = rsm_path_ok(r, r->primary, n_out) ? rsm_run(r, r->primary, d_in, d_out, hist, n_in, n_out) : LLZ_ERR_RANGE;
+        if (rc == LLZ_ERR_RANGE && r->fallback != RSM_NONE) {
+            ran = r->fallback;
+            rc = rsm_run(r, ran, d_in, d_out, hist, n_in, n_out);
+        }
     }
     if (rc == LLZ_OK && r->Q > 1) {
         if (r->fmt != LLZ_PCM_F32)
@@ -731,6 +750,7 @@ static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_i
     if (rc != LLZ_OK) return rc;
     r->in_count += n_in;
     r->out_count += n_out;
+    r->last = ran;
     return n_out;
 }
 

@@ -532,7 +532,8 @@ extern "C" int llzs_resample_i16x_fits(int L, int M, int Q)
 // with flag = 1 when the phase's outputs are exact integers the screen itself reproduces (a single tap 1.0 at gain 1.0: no
 // second look); g: the L x Q double taps; shift as
 // in llzs_fir_mfma_i16x; eps = the largest per-phase bound (checked only).  The call must
-// start on a period boundary (input index % M == 0, output index % L == 0).
+// start on a period boundary (input index % M == 0, output index % L == 0) and hold whole periods: k_resample_i8d bounds its
+// stores by periods, so n_out % L != 0 is declined (LLZ_ERR_RANGE: the caller takes the all-double kernel).
 extern "C" int llzs_resample_i16x(const short *in, short *out, const short *hist, const signed char *atab, const int *aoff,
                                   const int *bqtab, const double *g, int channels, long n_in, long n_out, long in_pitch,
                                   long out_pitch, int L, int M, int Q, int shift, double gain, double eps, int any_exact, void *stream)
@@ -545,6 +546,10 @@ extern "C" int llzs_resample_i16x(const short *in, short *out, const short *hist
         !llzs_resample_i16x_fits(L, M, Q)) {
         llzs_set_error("resample_i16x: bad arguments (channels=%d L=%d M=%d Q=%d shift=%d eps=%g)", channels, L, M, Q, shift, eps);
         return LLZ_ERR_ARG;
+    }
+    if (n_out % L != 0) {
+        llzs_set_error("resample_i16x: %ld outputs are not whole periods of %d", n_out, L);
+        return LLZ_ERR_RANGE;
     }
     // the kernel's sample requests are unconditional: one that has no span reads the head of the row instead, so a frame must be
     // at least one span's image long (shorter: the caller takes the all-double kernel)

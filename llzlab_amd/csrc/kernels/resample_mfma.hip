@@ -414,7 +414,9 @@ extern "C" int llzs_resample_mfma_f32_fits(int L, int M, int Q)
 }
 
 // atab: [ceil(L/16)][steps][64] floats (steps = llzs_resample_mfma_f32_table_steps), gain folded in; c0tab: [ceil(L/16)]
-// ints = floor(16 t M / L).  The call must start on a period boundary.
+// ints = floor(16 t M / L).  The call must start on a period boundary.  The phase-tile form (k_resample_mfma_pt_f32) stores whole
+// periods: it declines a call with n_out % L != 0 (LLZ_ERR_RANGE: the caller takes resample_f32); the period-tile form bounds
+// every store by n_out.
 extern "C" int llzs_resample_mfma_f32(const float *in, float *out, const float *hist, const float *atab, const int *c0tab,
                                       int channels, long n_in, long n_out, long in_pitch, long out_pitch, int L, int M, int Q,
                                       void *stream)
@@ -448,6 +450,10 @@ extern "C" int llzs_resample_mfma_f32(const float *in, float *out, const float *
             while (waves < 16 && count > 16L * 64 * waves) waves++;
             ok = lds <= 128 * 1024 && count <= 16L * 64 * waves && n_in >= 16L * 64 * waves;
             if (ok) break;
+        }
+        if (ok && n_out % L != 0) {
+            llzs_set_error("resample_mfma_f32: %ld outputs are not whole periods of %d", n_out, L);
+            return LLZ_ERR_RANGE;
         }
         if (ok) {
             rp.pt = pt;

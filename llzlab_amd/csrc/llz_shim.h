@@ -233,7 +233,8 @@ int llzs_resample_f32(const float *in, float *out, const float *hist, const floa
                       int L, int M, int Q, float gain, long long i0, long long in0, void *stream);
 /* general L/M float32 on the fp32 matrix cores (resample_mfma.hip): atab [ceil(L/16)][steps][64] = the banded tap matrix in
  * MFMA operand order with the gain folded in (steps = llzs_resample_mfma_f32_table_steps), c0tab [ceil(L/16)] =
- * floor(16 t M / L).  The call must start on a period boundary (input index % M == 0, output index % L == 0). */
+ * floor(16 t M / L).  The call must start on a period boundary (input index % M == 0, output index % L == 0); the phase-tile
+ * form declines n_out % L != 0 with LLZ_ERR_RANGE (it stores whole periods), the period-tile form bounds its stores by n_out. */
 int llzs_resample_mfma_f32(const float *in, float *out, const float *hist, const float *atab, const int *c0tab,
                            int channels, long n_in, long n_out, long in_pitch, long out_pitch, int L, int M, int Q,
                            void *stream);
@@ -253,7 +254,8 @@ int llzs_resample_i16(const short *in, short *out, const short *hist, const doub
  * [steps][5][64][16] tap digits in operand order (steps = llzs_resample_i16x_ksteps), aoff [ceil(L/16)] band starts, bqtab
  * [16 ceil(L/16)][4] = floor(128 sum_k G_f[k] / 256) as (lo, hi), the phase's own e32, first | last << 8 non-zero tap | exact
  * << 16; g the L x Q double taps, eps the largest per-phase bound, any_exact: some phase carries the exact flag.
- * The call must start on a period boundary (input index % M == 0, output index % L == 0). */
+ * The call must start on a period boundary (input index % M == 0, output index % L == 0) and hold whole periods: n_out % L != 0
+ * is declined with LLZ_ERR_RANGE (the kernel stores whole periods). */
 int llzs_resample_i16x(const short *in, short *out, const short *hist, const signed char *atab, const int *aoff,
                        const int *bqtab, const double *g, int channels, long n_in, long n_out, long in_pitch, long out_pitch,
                        int L, int M, int Q, int shift, double gain, double eps, int any_exact, void *stream);

@@ -445,6 +445,13 @@ class ResampleMC:
     def out_len(self, n_in):
         return check(self._L.llz_resample_mc_out_len(self.handle, n_in), "llz_resample_mc_out_len")
 
+    def last_entry(self):
+        """name of the shim entry that ran the last successful call ("" before the first)"""
+        name = self._L.llz_resample_mc_last_entry(self.handle)
+        if name is None:
+            raise LlzError("llz_resample_mc_last_entry: bad handle")
+        return name.decode()
+
     def matrix(self):
         m = np.zeros(self.L * self.Q)
         check(self._L.llz_resample_mc_get_matrix(self.handle, m.ctypes.data, m.size), "get_matrix")

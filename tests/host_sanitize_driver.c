@@ -152,6 +152,26 @@ int main(void)
         free(m);
         llz_resample_mc_uninit(h);
     }
+    /* ratios with a common factor: only whole-period calls from a period boundary reach the matrix-core entry, a call that
+     * ends or starts inside a period of L outputs runs on the fallback (llz_resample_mc_last_entry names the entry) */
+    const int rg[][3] = {{294, 320, LLZ_PCM_F32}, {4, 6, LLZ_PCM_I16}};
+    const char *rg_entry[][2] = {{"resample_mfma_f32", "resample_f32"}, {"resample_i16x", "resample_i16"}};
+    for (int i = 0; i < 2; i++) {
+        const int L = rg[i][0], M = rg[i][1], step = M / 2;
+        h = llz_resample_mc_init(3, L, M, 1.0, BLACKMAN, rg[i][2]);
+        CHECK(h != BAD && strcmp(llz_resample_mc_last_entry(h), "") == 0);
+        const void *in = rg[i][2] == LLZ_PCM_F32 ? (const void *)fx : (const void *)sx;
+        void *out = rg[i][2] == LLZ_PCM_F32 ? (void *)fy : (void *)sy;
+        const long calls[] = {8L * M, 3L * step, step, M, 2L * step + step, 4};     /* whole, ragged, back, whole, ragged, refused */
+        const int want[] = {0, 1, 1, 0, 1, 1};
+        for (int k = 0; k < 6; k++) {
+            const long n_out = llz_resample_mc(h, in, calls[k], out);
+            CHECK(k == 5 ? n_out < 0 : n_out == calls[k] * L / M);
+            CHECK(strcmp(llz_resample_mc_last_entry(h), rg_entry[i][want[k]]) == 0);
+        }
+        llz_resample_mc_uninit(h);
+    }
+    CHECK(llz_resample_mc_last_entry(BAD) == NULL && llz_resample_mc_last_entry(0) == NULL);
     /* transforms */
     h = llz_fft_init(1024); CHECK(h != BAD); llz_fft(h, dx); llz_ifft(h, dx); llz_fft_uninit(h);
     CHECK(llz_fft_init(48) == BAD);

@@ -26,6 +26,7 @@ torch = pytest.importorskip("torch")
 from llzlab_amd import capi, filters  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
 from tests import buffer_checks as bc  # noqa: E402
+from tests import rs_ragged_checks as rr  # noqa: E402
 from tests.edge_checks import TOL, rms_check  # noqa: E402
 from tests.test_lpc_host import levinson_py  # noqa: E402
 
@@ -201,7 +202,8 @@ def run_resample(dev, oracle, io, fmt, tune, L, M, win, channels, lens, gate="eq
     def make():
         n = sum(lens)
         x = oracle.synth_f32(channels, n, seed=L + 2 * M) if f32 else oracle.synth_i16(channels, n, seed=L * 31 + M)
-        return x, (oracle.rs_batch_f32 if f32 else oracle.rs_batch_i16)(x, L, M, 1.0, win)
+        # (ref_i16: the reference's frame loop; a length that is no whole number of its frames is zero-padded and cut)
+        return x, (rr.ref_f32 if f32 else rr.ref_i16)(oracle, x, L, M, 1.0, win)
     x, ref = cached(("rs", f32, L, M, win, channels, tuple(lens)), make)
     with capi.tuned(**tune):
         r = filters.ResampleMC(channels, L, M, 1.0, win, fmt)
@@ -510,6 +512,12 @@ add("rs-i16-double", run_resample, OFF16, dict(fmt=RS[1], tune={"rs_i16_path": 1
     dict(fmt=RS[1], tune={"rs_i16_path": 1}, L=2, M=3, win=po.HAMMING, channels=5, lens=[3 * 201, 3 * 311]))
 add("rs-i16-fast", run_resample, OFF16, dict(fmt=RS[2], tune={"rs_i16_path": 1}, L=1, M=3, win=po.BLACKMAN, channels=7, lens=[1536 * 2, 1536], gate="lsb"),
     dict(fmt=RS[2], tune={"rs_i16_path": 1}, L=1, M=3, win=po.BLACKMAN, channels=7, lens=[3 * 201, 3 * 311], gate="lsb"))
+# ratios with a common factor, the first call ending and the second starting inside a period of L outputs (the matrix-core
+# entries store whole periods: the handle runs such calls on its fallback entry, tests/test_resample_ragged_gpu.py)
+CASES.append(("rs-f32-resample_mfma_f32-294:320-ragged", run_resample, dict(fmt=RS[0], tune={}, L=294, M=320, win=po.BLACKMAN, channels=3,
+                                                                           lens=[160 * 129, 160 * 131]), OFF32))
+CASES.append(("rs-i16-screened-L:M-ragged", run_resample, dict(fmt=RS[1], tune={}, L=4, M=6, win=po.BLACKMAN, channels=5,
+                                                              lens=[3 * 1001, 3 * 999]), OFF16))
 # float32 transforms in place: 256 / E transforms per workgroup of the register kernels (E lanes each), 8 at 1024 points
 for n, per in ((64, 32), (256, 16), (128, 32), (512, 16), (2048, 8), (1024, 8)):
     add(f"fft-batch-{n}", run_fft_batch, OFF_INPLACE, dict(n=n, count=per, tune={}), dict(n=n, count=per + 1, tune={}))

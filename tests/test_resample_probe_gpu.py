@@ -14,13 +14,14 @@ from oracle import pyoracle as po  # noqa: E402
 from tests import edge_checks as ec  # noqa: E402
 
 # path of rsm_choose (llz_resample_host.c) -> the override that reaches it, and its shapes; the first shape also runs at
-# gains 2.5 and 0.37 and under white noise at gain 2.5
+# gains 2.5 and 0.37 and under white noise at gain 2.5; the ratios with a common factor (repeated and empty phases in the phase
+# maps floor(f M / L)) run whole periods here and ragged calls in test_resample_ragged_gpu.py
 PATHS = {
     "fir_mfma_f32": ({}, [(1, 3), (1, 2), (1, 5)]),
     "resample_dec_f32": ({"rs_dec_valu": 1}, [(1, 3), (1, 2), (1, 5)]),
-    "resample_mfma_f32 phase-tile waves": ({"rs_mfma_form": -1}, [(147, 160), (160, 147), (441, 320), (320, 441), (20, 147)]),
-    "resample_mfma_f32 period-tile waves": ({"rs_mfma_form": 1}, [(147, 160), (160, 147), (441, 320), (320, 441), (20, 147)]),
-    "resample_f32": ({}, [(2, 3), (3, 2), (5, 3), (8, 7)]),
+    "resample_mfma_f32 phase-tile waves": ({"rs_mfma_form": -1}, [(147, 160), (160, 147), (441, 320), (320, 441), (20, 147), (294, 320), (150, 160)]),
+    "resample_mfma_f32 period-tile waves": ({"rs_mfma_form": 1}, [(147, 160), (160, 147), (441, 320), (320, 441), (20, 147), (294, 320), (150, 160)]),
+    "resample_f32": ({}, [(2, 3), (3, 2), (5, 3), (8, 7), (4, 6), (6, 4), (40, 64)]),
     "resample_f32 rs_generic=1": ({"rs_generic": 1}, [(147, 160)]),
     "resample_f32 rs_generic=2": ({"rs_generic": 2}, [(147, 160)]),
 }
