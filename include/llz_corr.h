@@ -3,7 +3,7 @@
  * of llz_fft + llz_ifft back to back with a pointwise step in between, the same shape as the overlap-save FIR).
  * Part 1: the reference's symbols (reference libllzfilter/llz_corr.h, llz_corr.c:38-177), host `double` buffers, computed
  *         on the GPU in the reference's operation order: bit-identical results.
- * Part 2: many frames at once, float32, planar [frames][n] -> [frames][p+1].
+ * Part 2: many frames at once, float32, planar [frames][n] -> [frames][p+1] (cross-correlation: or [frames][2p+1]).
  */
 #ifndef LLZ_CORR_H
 #define LLZ_CORR_H
@@ -35,6 +35,27 @@ unsigned long llz_autocorr_fast_mc_init(int frames, int n);
 void          llz_autocorr_fast_mc_uninit(unsigned long handle);
 int           llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p);
 int           llz_autocorr_fast_mc_set_stream(unsigned long handle, void *stream);
+
+/* r[f][k] = sum_i x[f][i] * y[f][i+k]  (llz_corr.c:49-58, the reference's definition), float32, planar.
+ * two_sided = 0: r is [frames][p+1], lags 0..p.
+ * two_sided = 1: r is [frames][2p+1], lag k in -p..p at index p+k, with r[-k] = sum_i y[f][i] * x[f][i+k].
+ * x, y: [frames][n]; device or host pointers, each on its own; 0 <= p < n, p <= 255.
+ * x == y is allowed and gives the autocorrelation (the bits of llz_autocorr_mc). r overlapping x or y in device memory is
+ * refused with LLZ_ERR_ARG. Returns 0 or < 0. */
+int llz_crosscorr_mc(const float *x, const float *y, float *r, int frames, int n, int p, int two_sided, void *stream);
+
+/* c[f] = <a,b> / sqrt(<a,a><b,b>)  (llz_corr.c:61-78) for `frames` pairs of n samples; c: [frames]; float32 sums, the quotient in
+ * double. A frame in which a or b is silent gives NaN (0/0), as the reference does, and touches no other frame. c overlapping
+ * a or b in device memory is refused with LLZ_ERR_ARG. */
+int llz_corr_cof_mc(const float *a, const float *b, float *c, int frames, int n, void *stream);
+
+/* FFT form for wide lag ranges: the true linear cross-correlation through fft_len = 2^ceil(log2(2n)) (no wrap for |k| <= n-1;
+ * NOT the first-n-bins quirk of llz_autocorr_fast, which has no cross counterpart in the reference). 4 <= n <= 2048,
+ * 0 <= p <= n-1; x, y, r laid out as for llz_crosscorr_mc, device or host pointers; r may not overlap x or y (device memory). */
+unsigned long llz_crosscorr_fast_mc_init(int frames, int n);
+void          llz_crosscorr_fast_mc_uninit(unsigned long handle);
+int           llz_crosscorr_fast_mc(unsigned long handle, const float *x, const float *y, float *r, int p, int two_sided);
+int           llz_crosscorr_fast_mc_set_stream(unsigned long handle, void *stream);
 
 #ifdef __cplusplus
 }

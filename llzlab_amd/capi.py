@@ -215,6 +215,12 @@ def lib():
     sig("llz_autocorr_fast_mc_uninit", None, ul)
     sig("llz_autocorr_fast_mc", i, ul, vp, vp, i)
     sig("llz_autocorr_fast_mc_set_stream", i, ul, vp)
+    sig("llz_crosscorr_mc", i, vp, vp, vp, i, i, i, i, vp)
+    sig("llz_corr_cof_mc", i, vp, vp, vp, i, i, vp)
+    sig("llz_crosscorr_fast_mc_init", ul, i, i)
+    sig("llz_crosscorr_fast_mc_uninit", None, ul)
+    sig("llz_crosscorr_fast_mc", i, ul, vp, vp, vp, i, i)
+    sig("llz_crosscorr_fast_mc_set_stream", i, ul, vp)
     sig("llz_levinson", None, dp, i, dp, dp, dp)
     sig("llz_levinson1", None, dp, i, dp, dp, dp)
     sig("llz_atlvs", i, dp, i, dp, dp, dp, dp)

@@ -53,6 +53,7 @@ typedef struct {
 
 #define LLZ_TAG_ACF1 0x4c5a4131
 #define LLZ_TAG_ACFM 0x4c5a414d
+#define LLZ_TAG_XCFM 0x4c5a584d
 
 static int acf_fft_len(int n)
 {
@@ -139,6 +140,80 @@ int llz_autocorr_mc(const float *x, float *r, int frames, int n, int p, void *st
     if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, stream);
     if (!x_dev) { llzs_sync(stream); llzs_free(d_x); }
     if (!r_dev) llzs_free(d_r);
+    return rc;
+}
+
+/* a caller's float buffer for a kernel: device memory is used where it lies, host memory goes through a device copy (inputs
+ * are uploaded); *d is the pointer to launch with.  corr_unstage frees what corr_stage allocated. */
+static int corr_stage(const float *user, size_t bytes, int dev, int upload, float **d, void *stream)
+{
+    *d = (float *)user;
+    if (dev) return LLZ_OK;
+    *d = (float *)llzs_malloc(bytes);
+    if (!*d) return LLZ_ERR_NOMEM;
+    return upload ? llzs_h2d(*d, user, bytes, stream) : LLZ_OK;
+}
+
+static void corr_unstage(const float *user, float *d)
+{
+    if (d && d != user) llzs_free(d);
+}
+
+int llz_crosscorr_mc(const float *x, const float *y, float *r, int frames, int n, int p, int two_sided, void *stream)
+{
+    if (!x || !y || !r || frames < 1 || n < 1 || p < 0 || p >= n || p > 255 || (two_sided != 0 && two_sided != 1)) {
+        llzs_set_error("llz_crosscorr_mc: x %p y %p r %p frames %d n %d p %d two_sided %d (p < n, p <= 255, two_sided 0 or 1)",
+                       (const void *)x, (const void *)y, (void *)r, frames, n, p, two_sided);
+        return LLZ_ERR_ARG;
+    }
+    const size_t xb = sizeof(float) * (size_t)frames * n;
+    const size_t rb = sizeof(float) * (size_t)frames * (two_sided ? 2 * (size_t)p + 1 : (size_t)p + 1);
+    const int x_dev = llzs_is_device_ptr(x), y_dev = llzs_is_device_ptr(y), r_dev = llzs_is_device_ptr(r);
+    if (x_dev < 0 || y_dev < 0 || r_dev < 0) return LLZ_ERR_ARG;  /* device memory of a GPU that is not current */
+    if (llz_refuse_device_overlap("llz_crosscorr_mc", "x", x, xb, x_dev, "r", r, rb, r_dev) ||
+        llz_refuse_device_overlap("llz_crosscorr_mc", "y", y, xb, y_dev, "r", r, rb, r_dev))
+        return LLZ_ERR_ARG;
+    float *d_x = NULL, *d_y = NULL, *d_r = NULL;
+    int rc = corr_stage(x, xb, x_dev, 1, &d_x, stream);
+    if (rc == LLZ_OK) {
+        if (y == x) d_y = d_x;                                      /* one row: one copy, and the one-row kernels */
+        else rc = corr_stage(y, xb, y_dev, 1, &d_y, stream);
+    }
+    if (rc == LLZ_OK) rc = corr_stage(r, rb, r_dev, 0, &d_r, stream);
+    if (rc == LLZ_OK) rc = llzs_crosscorr_mc_f32(d_x, d_y, d_r, frames, n, p, two_sided, stream);
+    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, stream);
+    if (!x_dev || !y_dev) llzs_sync(stream);                       /* the kernels are done with the copies */
+    if (y != x) corr_unstage(y, d_y);
+    corr_unstage(x, d_x);
+    corr_unstage(r, d_r);
+    return rc;
+}
+
+int llz_corr_cof_mc(const float *a, const float *b, float *c, int frames, int n, void *stream)
+{
+    if (!a || !b || !c || frames < 1 || n < 1) {
+        llzs_set_error("llz_corr_cof_mc: a %p b %p c %p frames %d n %d", (const void *)a, (const void *)b, (void *)c, frames, n);
+        return LLZ_ERR_ARG;
+    }
+    const size_t ab = sizeof(float) * (size_t)frames * n, cb = sizeof(float) * (size_t)frames;
+    const int a_dev = llzs_is_device_ptr(a), b_dev = llzs_is_device_ptr(b), c_dev = llzs_is_device_ptr(c);
+    if (a_dev < 0 || b_dev < 0 || c_dev < 0) return LLZ_ERR_ARG;
+    if (llz_refuse_device_overlap("llz_corr_cof_mc", "a", a, ab, a_dev, "c", c, cb, c_dev) ||
+        llz_refuse_device_overlap("llz_corr_cof_mc", "b", b, ab, b_dev, "c", c, cb, c_dev))
+        return LLZ_ERR_ARG;
+    float *d_a = NULL, *d_b = NULL, *d_c = NULL;
+    int rc = corr_stage(a, ab, a_dev, 1, &d_a, stream);
+    if (rc == LLZ_OK) {
+        if (b == a) d_b = d_a;
+        else rc = corr_stage(b, ab, b_dev, 1, &d_b, stream);
+    }
+    if (rc == LLZ_OK) rc = corr_stage(c, cb, c_dev, 0, &d_c, stream);
+    if (rc == LLZ_OK) rc = llzs_corr_cof_mc_f32(d_a, d_b, d_c, frames, n, stream);
+    if (rc == LLZ_OK && !c_dev) rc = llzs_d2h(c, d_c, cb, stream);
+    if (!a_dev || !b_dev) llzs_sync(stream);
+    if (b != a) corr_unstage(b, d_b);
+    corr_unstage(a, d_a);
+    corr_unstage(c, d_c);
     return rc;
 }
 
@@ -232,6 +307,133 @@ int llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p)
     }
     /* pack -> FFT -> |X|^2 (first n bins) -> IFFT -> 2 Re, fused in LDS */
     if (rc == LLZ_OK) rc = llzs_acf_fused_f32(d_x, d_r, f->frames, f->n, p, f->fft_len, f->d_cs, f->stream);
+    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->stream);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+/* ---- FFT cross-correlation: z = x + i y through ONE forward transform per frame pair, conj(X) Y, one inverse ---- */
+
+#define XCF_SCRATCH_BYTES ((size_t)256 << 20)      /* spectra scratch: at most this much, walked in slabs of frames */
+
+typedef struct {
+    int tag, device, frames, n, fft_len, slab;      /* slab: frames per walk of the scratch */
+    float *d_cs;            /* fft_len cos then fft_len sin */
+    float *d_z;             /* slab x fft_len complex */
+    void *stream;
+    llz_stage_t st_x, st_y, st_out;
+} xcfm_t;
+
+static void xcfm_destroy(xcfm_t *f)
+{
+    if (!f) return;
+    llzs_free(f->d_cs);
+    llzs_free(f->d_z);
+    llz_stage_release(&f->st_x); llz_stage_release(&f->st_y); llz_stage_release(&f->st_out);
+    f->tag = 0;
+    free(f);
+}
+
+unsigned long llz_crosscorr_fast_mc_init(int frames, int n)
+{
+    if (frames < 1 || n < 4 || n > 2048) {
+        llzs_set_error("llz_crosscorr_fast_mc_init: frames %d n %d (frames >= 1, n in 4..2048)", frames, n);
+        return LLZ_BAD_HANDLE;
+    }
+    xcfm_t *f = (xcfm_t *)calloc(1, sizeof(*f));
+    if (!f) return LLZ_BAD_HANDLE;
+    f->tag = LLZ_TAG_XCFM; f->device = llzs_device_get(); f->frames = frames; f->n = n; f->fft_len = acf_fft_len(n);
+    const int F = f->fft_len;
+    const size_t per_frame = sizeof(float) * 2 * (size_t)F;
+    f->slab = (size_t)frames * per_frame <= XCF_SCRATCH_BYTES ? frames : (int)(XCF_SCRATCH_BYTES / per_frame);
+    float *cs = (float *)malloc(sizeof(float) * 2 * (size_t)F);
+    int rc = cs ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {
+        for (int i = 0; i < F; i++) {
+            const double ang = (double)(2 * M_PI * i) / F;
+            cs[i] = (float)cos(ang);
+            cs[F + i] = (float)sin(ang);
+        }
+        f->d_cs = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)F);
+        rc = f->d_cs ? llzs_h2d(f->d_cs, cs, sizeof(float) * 2 * (size_t)F, NULL) : LLZ_ERR_NOMEM;
+    }
+    free(cs);
+    if (rc == LLZ_OK) {
+        f->d_z = (float *)llzs_malloc((size_t)f->slab * per_frame);
+        if (!f->d_z) rc = LLZ_ERR_NOMEM;
+    }
+    if (rc != LLZ_OK) {
+        xcfm_destroy(f);
+        return LLZ_BAD_HANDLE;
+    }
+    return (unsigned long)f;
+}
+
+void llz_crosscorr_fast_mc_uninit(unsigned long handle)
+{
+    if (LLZ_HANDLE_OK(handle, xcfm_t, LLZ_TAG_XCFM)) {
+        const int prev = llzs_device_enter(((xcfm_t *)handle)->device);
+        llzs_sync(((xcfm_t *)handle)->stream);
+        xcfm_destroy((xcfm_t *)handle);
+        llzs_device_leave(prev);
+    }
+}
+
+int llz_crosscorr_fast_mc_set_stream(unsigned long handle, void *stream)
+{
+    if (!LLZ_HANDLE_OK(handle, xcfm_t, LLZ_TAG_XCFM)) {
+        llzs_set_error("llz_crosscorr_fast_mc_set_stream: not a llz_crosscorr_fast_mc_init handle");
+        return LLZ_ERR_ARG;
+    }
+    ((xcfm_t *)handle)->stream = stream;
+    return LLZ_OK;
+}
+
+int llz_crosscorr_fast_mc(unsigned long handle, const float *x, const float *y, float *r, int p, int two_sided)
+{
+    if (!LLZ_HANDLE_OK(handle, xcfm_t, LLZ_TAG_XCFM)) {
+        llzs_set_error("llz_crosscorr_fast_mc: not a llz_crosscorr_fast_mc_init handle");
+        return LLZ_ERR_ARG;
+    }
+    xcfm_t *f = (xcfm_t *)handle;
+    if (!x || !y || !r || p < 0 || p >= f->n || (two_sided != 0 && two_sided != 1)) {
+        llzs_set_error("llz_crosscorr_fast_mc: x %p y %p r %p p %d two_sided %d (0 <= p < n = %d, two_sided 0 or 1)",
+                       (const void *)x, (const void *)y, (void *)r, p, two_sided, f->n);
+        return LLZ_ERR_ARG;
+    }
+    const int width = two_sided ? 2 * p + 1 : p + 1, F = f->fft_len;
+    const size_t xb = sizeof(float) * (size_t)f->frames * f->n, rb = sizeof(float) * (size_t)f->frames * width;
+    const int prev = llzs_device_enter(f->device);
+    const int x_dev = llzs_is_device_ptr(x), y_dev = llzs_is_device_ptr(y), r_dev = llzs_is_device_ptr(r);
+    const float *d_x = x, *d_y = y;
+    float *d_r = r;
+    int rc = (x_dev < 0 || y_dev < 0 || r_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;   /* a buffer of another GPU: refused, message set */
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_crosscorr_fast_mc", "x", x, xb, x_dev, "r", r, rb, r_dev);
+    if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_crosscorr_fast_mc", "y", y, xb, y_dev, "r", r, rb, r_dev);
+    if (rc == LLZ_OK && !x_dev) {
+        d_x = (const float *)llz_stage_reserve(&f->st_x, xb);
+        rc = d_x ? llzs_h2d((void *)d_x, x, xb, f->stream) : LLZ_ERR_NOMEM;
+    }
+    if (rc == LLZ_OK && !y_dev) {
+        if (y == x) d_y = d_x;
+        else {
+            d_y = (const float *)llz_stage_reserve(&f->st_y, xb);
+            rc = d_y ? llzs_h2d((void *)d_y, y, xb, f->stream) : LLZ_ERR_NOMEM;
+        }
+    }
+    if (rc == LLZ_OK && !r_dev) {
+        d_r = (float *)llz_stage_reserve(&f->st_out, rb);
+        if (!d_r) rc = LLZ_ERR_NOMEM;
+    }
+    /* per slab of frames: pack -> FFT -> conj(X) Y -> IFFT -> lags; the launches of a slab follow the previous slab's on the stream */
+    for (int f0 = 0; rc == LLZ_OK && f0 < f->frames; f0 += f->slab) {
+        const int cnt = f->frames - f0 < f->slab ? f->frames - f0 : f->slab;
+        rc = llzs_xcf_pack(d_x + (size_t)f0 * f->n, d_y + (size_t)f0 * f->n, f->d_z, cnt, f->n, F, f->stream);
+        if (rc == LLZ_OK) rc = llzs_fft_f32(f->d_z, cnt, F, f->d_cs, 0, f->stream);
+        if (rc == LLZ_OK) rc = llzs_xcf_product(f->d_z, cnt, F, f->stream);
+        if (rc == LLZ_OK) rc = llzs_fft_f32(f->d_z, cnt, F, f->d_cs, 1, f->stream);
+        if (rc == LLZ_OK) rc = llzs_xcf_extract(f->d_z, d_r + (size_t)f0 * width, cnt, p, two_sided, F, f->stream);
+    }
     if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->stream);
     llzs_device_leave(prev);
     return rc;

@@ -295,6 +295,16 @@ int llzs_fft_large_passes(int size, int f32);
 int llzs_corr_exact_f64(const double *x, const double *y, int n, int p, double *r, void *stream);
 /* frames x n float32 -> frames x (p+1), direct form */
 int llzs_autocorr_mc_f32(const float *x, float *r, int frames, int n, int p, void *stream);
+/* r[f][k] = sum_i x[f][i]*y[f][i+k] on the same kernels (x == y: the same bits as llzs_autocorr_mc_f32); two_sided = 0:
+ * frames x (p+1); 1: frames x (2p+1), lag k at index p+k (the negative lags: the rows swapped, lags 1..p) */
+int llzs_crosscorr_mc_f32(const float *x, const float *y, float *r, int frames, int n, int p, int two_sided, void *stream);
+/* c[f] = <a,b> / sqrt(<a,a><b,b>): float32 sums, the quotient in double */
+int llzs_corr_cof_mc_f32(const float *a, const float *b, float *c, int frames, int n, void *stream);
+/* pointwise steps of the FFT cross-correlation around llzs_fft_f32 (F points, z: frames x F complex): z = x + i y zero-padded;
+ * conj(X) Y separated from Z[k] and conj(Z[F-k]), in place; lags 0..p or -p..p (lag -k at bin F-k) of the inverse transform */
+int llzs_xcf_pack(const float *x, const float *y, float *z, int frames, int n, int F, void *stream);
+int llzs_xcf_product(float *z, int frames, int F, void *stream);
+int llzs_xcf_extract(const float *z, float *r, int frames, int p, int two_sided, int F, void *stream);
 /* pointwise steps of the FFT form around llzs_fft_f32: real -> zero-padded complex; |X|^2 of the first n bins; 2*Re */
 int llzs_acf_pack(const float *x, float *z, int frames, int n, int F, void *stream);
 int llzs_acf_power(float *z, int frames, int n, int F, void *stream);

@@ -627,6 +627,53 @@ class AutocorrFastMC:
     __del__ = close
 
 
+def _lags(p, two_sided):
+    return 2 * p + 1 if two_sided else p + 1
+
+
+def crosscorr_mc(x, y, r, p, two_sided=False, stream=None):
+    """x, y: [frames, n] float32; r: [frames, p+1] float32 (lags 0..p) or, two_sided, [frames, 2p+1] with lag k at index p+k
+    (device tensors or numpy, each on its own).  r[f][k] = sum_i x[f][i] * y[f][i+k]."""
+    frames, n = x.shape
+    check(capi.lib().llz_crosscorr_mc(_typed(x, "float32", frames * n, "x"), _typed(y, "float32", frames * n, "y"),
+                                      _typed(r, "float32", frames * _lags(p, two_sided), "r"), frames, n, p,
+                                      1 if two_sided else 0, _stream_ptr(stream)), "llz_crosscorr_mc")
+    return r
+
+
+def corr_cof_mc(a, b, c, stream=None):
+    """a, b: [frames, n] float32; c: [frames] float32 = <a,b> / sqrt(<a,a><b,b>) per frame (NaN where a or b is silent)."""
+    frames, n = a.shape
+    check(capi.lib().llz_corr_cof_mc(_typed(a, "float32", frames * n, "a"), _typed(b, "float32", frames * n, "b"),
+                                     _typed(c, "float32", frames, "c"), frames, n, _stream_ptr(stream)), "llz_corr_cof_mc")
+    return c
+
+
+class CrosscorrFastMC:
+    """llz_crosscorr_fast_mc: the linear cross-correlation of frames x n float32 through the FFT, 4 <= n <= 2048, p <= n - 1."""
+
+    def __init__(self, frames, n, stream=None):
+        self._L = capi.lib()
+        self.frames, self.n = frames, n
+        self.handle = check_handle(self._L.llz_crosscorr_fast_mc_init(frames, n), "llz_crosscorr_fast_mc_init")
+        if stream is not None:
+            check(self._L.llz_crosscorr_fast_mc_set_stream(self.handle, _stream_ptr(stream)), "set_stream")
+
+    def run(self, x, y, r, p, two_sided=False):
+        size = self.frames * self.n
+        check(self._L.llz_crosscorr_fast_mc(self.handle, _typed(x, "float32", size, "x"), _typed(y, "float32", size, "y"),
+                                            _typed(r, "float32", self.frames * _lags(max(p, 0), two_sided), "r"), p,
+                                            1 if two_sided else 0), "llz_crosscorr_fast_mc")
+        return r
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_crosscorr_fast_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ linear prediction
 LEVINSON_ORDER_MAX = 64
 

@@ -152,6 +152,39 @@ if "corr" in which:
             f.close()
         del x, r
 
+    # the cross-correlation next to the autocorrelation at the same shapes: 8 B per sample pair read plus the lags written
+    def corr_line(name, frames, n, lags, ms, in_bytes=8.0):
+        gb = (in_bytes * frames * n + 4.0 * frames * lags) / ms / 1e6
+        print(f"{name} {frames} x {n}: {ms:.3f} ms  {frames * n / ms / 1e3:.0f} Mpairs/s  {gb:.0f} GB/s ({gb / 80:.1f} %)")
+
+    for (frames, n, p, sides) in ((1 << 18, 1024, 16, (False, True)), (1 << 17, 2048, 255, (True,))):
+        x = torch.rand(frames, n, dtype=torch.float32, device=dev) * 2 - 1
+        y = torch.rand(frames, n, dtype=torch.float32, device=dev) * 2 - 1
+        r = torch.empty(frames, p + 1, dtype=torch.float32, device=dev)
+        ms = timeit(lambda: filters.autocorr_mc(x, r, p, stream=stream), 3)
+        corr_line(f"autocorr direct, p={p}            ", frames, n, p + 1, ms, in_bytes=4.0)
+        for two in sides:
+            lags = 2 * p + 1 if two else p + 1
+            r2 = torch.empty(frames, lags, dtype=torch.float32, device=dev)
+            ms = timeit(lambda: filters.crosscorr_mc(x, y, r2, p, two_sided=two, stream=stream), 3)
+            corr_line(f"crosscorr direct, p={p}, {'two' if two else 'one'}-sided", frames, n, lags, ms)
+            del r2
+        if p == 16:
+            c = torch.empty(frames, dtype=torch.float32, device=dev)
+            ms = timeit(lambda: filters.corr_cof_mc(x, y, c, stream=stream), 3)
+            corr_line("corr_cof                         ", frames, n, 1, ms)
+            del c
+        del x, y, r
+    frames, n, p = 1 << 17, 2048, 2047
+    x = torch.rand(frames, n, dtype=torch.float32, device=dev) * 2 - 1
+    y = torch.rand(frames, n, dtype=torch.float32, device=dev) * 2 - 1
+    r = torch.empty(frames, 2 * p + 1, dtype=torch.float32, device=dev)
+    f = filters.CrosscorrFastMC(frames, n, stream=stream)
+    ms = timeit(lambda: f.run(x, y, r, p, two_sided=True), 3)
+    corr_line(f"crosscorr fft, p={p}, two-sided ", frames, n, 2 * p + 1, ms)
+    f.close()
+    del x, y, r
+
 if "pcm" in which:
     for ch in (2, 64, 4096):
         n = (1 << 31) // ch // 2                                          # 2 GiB of int16 in, 4 GiB of float32 out
