@@ -7,7 +7,8 @@
  * reference CPU path for identical taps).
  * Part 2 is the multi-channel float32 batch extension of the same init / process / flush / uninit shape
  *  -- the path the MI355X kernels are built for.
- * Part 3 is the same batch with a tap set per channel: the filter bank.
+ * Part 3 is the same batch with a tap set per channel: the filter bank (time domain, and overlap-save up to 257 taps).
+ * Part 4 is the bank for long filters: the partitioned overlap-save of part 2 with a tap set per channel, 1..131073 taps.
  */
 #ifndef LLZ_FIR_H
 #define LLZ_FIR_H
@@ -113,7 +114,8 @@ int llz_fir_filter_mc_set_stream(unsigned long handle, void *stream);
  * per-channel fractional delays).  taps: HOST pointer, planar [channels][flt_len] (the double variant rounds to float once).
  * channels 1..65535.  algo: LLZ_FIR_ALGO_TIME (any flt_len the time-domain kernel holds), LLZ_FIR_ALGO_OVERLAP_SAVE
  * (1024-point, 1..257 taps) or LLZ_FIR_ALGO_AUTO (time domain up to 32 taps, overlap-save for 33..257, time domain above);
- * the matrix-core form and the longer transforms are not built for a bank and are refused.
+ * the matrix-core form and the longer transforms are not built for a bank and are refused.  A bank of filters the time
+ * domain does not hold (above 25248 taps), or cannot afford, is part 4's llz_fir_pbank_mc_init.
  * Returns (unsigned long)-1 on failure (llz_hip_last_error() says why). */
 unsigned long llz_fir_bank_mc_init(int channels, int frame_len, const float *taps, int flt_len, int algo);
 unsigned long llz_fir_bank_mc_init_f64taps(int channels, int frame_len, const double *taps, int flt_len, int algo);
@@ -131,6 +133,24 @@ int llz_fir_bank_mc_set_taps(unsigned long handle, int first, int count, const f
 int llz_fir_bank_mc_flt_len(unsigned long handle);
 int llz_fir_bank_mc_algo(unsigned long handle);
 int llz_fir_bank_mc_set_stream(unsigned long handle, void *stream);
+
+/* ---- Part 4: the partitioned bank -- LLZ_FIR_ALGO_PARTITIONED with one tap set PER CHANNEL, 1..131073 taps ---------- */
+
+/* channels (1..65535) independent filters of flt_len (1..131073) taps, one tap set each: room and cabinet responses, BRIR
+ * sets, long per-microphone calibration.  taps: HOST pointer, planar [channels][flt_len] (the double variant rounds to float
+ * once).  The handle IS A BANK HANDLE of part 3 with llz_fir_bank_mc_algo() == LLZ_FIR_ALGO_PARTITIONED: llz_fir_bank_mc,
+ * _flush, _set_taps, _set_stream, _flt_len, _algo and _uninit take it with their contracts unchanged.  What part 2 says of
+ * LLZ_FIR_ALGO_PARTITIONED holds: a call filters concat(history, frame) from scratch through the same three kernels, the flush
+ * too; the transform size follows flt_len; the scratch is sized at init from frame_len (at most 1 GiB, channels in passes).  The
+ * spectra of all tap sets stay in device memory: channels x ceil(flt_len / (N / 2)) x N x 8 bytes (2.1 MB per channel at
+ * 131073 taps); when that allocation fails the message states the bytes asked for.  llz_fir_bank_mc_set_taps rebuilds the
+ * spectra of the named channels.  Never reached through llz_fir_bank_mc_init, whose algo 7 stays refused.
+ * Returns (unsigned long)-1 on failure (llz_hip_last_error() says why). */
+unsigned long llz_fir_pbank_mc_init(int channels, int frame_len, const float *taps, int flt_len);
+unsigned long llz_fir_pbank_mc_init_f64taps(int channels, int frame_len, const double *taps, int flt_len);
+/* out = {N, P, channels per pass, passes} as llz_fir_filter_mc_partition_plan reports them; LLZ_ERR_ARG for every handle that
+ * is not llz_fir_pbank_mc_init's (llz_fir_filter_mc_partition_plan in turn refuses every bank handle) */
+int           llz_fir_pbank_mc_plan(unsigned long handle, int n, int out[4]);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,10 @@ def lib():
     sig("llz_fir_bank_mc_flt_len", i, ul)
     sig("llz_fir_bank_mc_algo", i, ul)
     sig("llz_fir_bank_mc_set_stream", i, ul, vp)
+    # llz_fir.h part 4
+    sig("llz_fir_pbank_mc_init", ul, i, i, vp, i)
+    sig("llz_fir_pbank_mc_init_f64taps", ul, i, i, vp, i)
+    sig("llz_fir_pbank_mc_plan", i, ul, i, C.POINTER(C.c_int))
     # llz_iir.h
     sig("llz_iir_filter_init", ul, i, dp, i, dp)
     sig("llz_iir_filter_uninit", None, ul)

@@ -154,7 +154,8 @@ typedef struct {
     int cur;
     float *d_zero;              /* [channels][flt_len-1] zeros: flush input */
     int part_n;                 /* LLZ_FIR_ALGO_PARTITIONED: transform points, fixed at init (0 for every other algo) */
-    float *d_hpart, *d_ptw;     /* ... [P][part_n] partition spectra and [part_n / 2] twiddles (llzs_fir_part_f32) */
+    float *d_hpart, *d_ptw;     /* ... [P][part_n] partition spectra and [part_n / 2] twiddles (llzs_fir_part_f32); a bank:
+                                 * [channels][P][part_n] (llzs_fir_part_bank_f32) and no d_taps */
     float *d_scratch;           /* ... block spectra of one pass of channels */
     size_t scratch_bytes;
     void *stream;
@@ -278,69 +279,123 @@ static size_t firm_part_cap(void)
     return (size_t)((mb >= 1 && mb <= 1024) ? mb : 1024) << 20;
 }
 
-/* the partition spectra, the twiddles and the scratch of an algo-7 handle.  H_p = DFT_N(taps[p B .. p B + B), zero-padded) / N
- * by a radix-2 decimation-in-frequency transform in double (twiddles from a quadrant-exact table), rounded to float once and
- * left in that transform's output order (entry i = bin bitrev(i)): the device's forward transform leaves its bins in the same
- * order, and the product is bin-wise.  33 x 8192 points at 131073 taps: milliseconds, where the direct DFT of
- * firm_build_ols_tables would sum 10^9 terms. */
-static int firm_build_part(firm_t *f, const float *taps)
+/* cos then sin of 2 pi i / N, i < N, with exact quadrant values */
+static void firm_part_cs_table(double *cs, int N)
 {
-    const int N = firm_part_nfft(f->flt_len), B = N / 2, keep = f->flt_len - 1;
-    const int P = (f->flt_len + B - 1) / B;
+    for (int i = 0; i < N; i++) {
+        const double ang = 2.0 * M_PI * (double)i / (double)N;
+        cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
+        cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
+    }
+}
+
+/* one tap row into its partition spectra: dst = [P][N] complex floats, P = ceil(flt_len / (N / 2)), row p =
+ * DFT_N(taps[p B .. p B + B), zero-padded) / N by a radix-2 decimation-in-frequency transform in double (twiddles from the
+ * quadrant-exact table cs of firm_part_cs_table), rounded to float once and left in that transform's output order (entry i =
+ * bin bitrev(i)): the device's forward transform leaves its bins in the same order, and the product is bin-wise.  33 x 8192
+ * points at 131073 taps: milliseconds, where the direct DFT of firm_build_ols_tables would sum 10^9 terms.  z: 2 N doubles.
+ * The shared-taps handle and the bank both build their spectra here, so equal taps give equal float32 entries. */
+void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, const double *cs, double *z)
+{
+    const int B = N / 2, P = (flt_len + B - 1) / B;
+    for (int p = 0; p < P; p++) {
+        for (int i = 0; i < N; i++) {
+            const long t = (long)p * B + i;
+            z[2 * i] = (i < B && t < flt_len) ? (double)taps[t] : 0.0;
+            z[2 * i + 1] = 0.0;
+        }
+        for (int span = N; span >= 2; span /= 2) {
+            const int half = span / 2, step = N / span;
+            for (int base = 0; base < N; base += span)
+                for (int j = 0; j < half; j++) {
+                    double *a = z + 2 * (base + j), *b = a + 2 * half;
+                    const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
+                    const double dr = a[0] - b[0], di = a[1] - b[1];
+                    a[0] += b[0]; a[1] += b[1];
+                    b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
+                }
+        }
+        float *row = dst + 2 * (size_t)p * (size_t)N;
+        for (int i = 0; i < 2 * N; i++) row[i] = (float)(z[i] / N);
+    }
+}
+
+/* host staging of the spectra: whole tap rows up to this many bytes at a time, one row at least (2.1 MB at 131073 taps) */
+#define FIRM_PART_STAGE_BYTES ((size_t)8 << 20)
+
+/* build the spectra of tap rows [first, first + count) (taps: [count][flt_len]; the shared-taps handle has the one row 0) and
+ * upload them in chunks of rows: at init as tables, from set_taps on the handle's stream behind the calls already issued */
+static int firm_part_load_rows(firm_t *f, int first, int count, const float *taps, int at_init)
+{
+    const int N = f->part_n, P = (f->flt_len + N / 2 - 1) / (N / 2);
+    const size_t row = 2 * (size_t)P * (size_t)N;                  /* floats of one row's spectra */
+    size_t chunk = FIRM_PART_STAGE_BYTES / (sizeof(float) * row);
+    if (chunk < 1) chunk = 1;
+    if (chunk > (size_t)count) chunk = (size_t)count;
+    float *hp = (float *)malloc(sizeof(float) * row * chunk);
+    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    int rc = (hp && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) firm_part_cs_table(cs, N);
+    for (size_t r0 = 0; r0 < (size_t)count && rc == LLZ_OK; r0 += chunk) {
+        const size_t rows = (size_t)count - r0 < chunk ? (size_t)count - r0 : chunk;
+        for (size_t r = 0; r < rows; r++)
+            llz_host_part_spectra(hp + r * row, taps + (r0 + r) * (size_t)f->flt_len, f->flt_len, N, cs, z);
+        float *d_h = f->d_hpart + ((size_t)first + r0) * row;
+        rc = at_init ? llzs_h2d_table(d_h, hp, sizeof(float) * row * rows) : llzs_h2d(d_h, hp, sizeof(float) * row * rows, f->stream);
+    }
+    free(hp); free(cs); free(z);
+    return rc;
+}
+
+/* the transform size and the scratch bytes of an algo-7 handle, from the tunes set now; refuses a shape of which not one
+ * channel fits the cap.  Touches no device.  who: the init's name, for messages. */
+static int firm_part_size(firm_t *f, const char *who)
+{
+    const int N = firm_part_nfft(f->flt_len), keep = f->flt_len - 1;
     const size_t cap = firm_part_cap();
     size_t need = 0, need_flush = 0;            /* per channel: a frame, and the flush's flt_len - 1 zeros */
     if (llzs_fir_part_need(N, f->flt_len, f->frame_len, &need) != LLZ_OK) return LLZ_ERR_ARG;
     if (keep > 0 && llzs_fir_part_need(N, f->flt_len, keep, &need_flush) != LLZ_OK) return LLZ_ERR_ARG;
     if (need_flush > need) need = need_flush;
     if (need > cap) {
-        llzs_set_error("llz_fir_filter_mc_init: one channel of %d samples at %d taps (%d-point partitions) needs %zu B of scratch, "
-                       "the cap is %zu B", f->frame_len > keep ? f->frame_len : keep, f->flt_len, N, need, cap);
+        llzs_set_error("%s: one channel of %d samples at %d taps (%d-point partitions) needs %zu B of scratch, "
+                       "the cap is %zu B", who, f->frame_len > keep ? f->frame_len : keep, f->flt_len, N, need, cap);
         return LLZ_ERR_NOMEM;
     }
     f->part_n = N;
     f->scratch_bytes = need * (size_t)f->channels < cap ? need * (size_t)f->channels : cap;
-    const size_t hcount = 2 * (size_t)P * (size_t)N;
-    float *hp = (float *)malloc(sizeof(float) * hcount);
+    return LLZ_OK;
+}
+
+/* the partition spectra of `rows` tap rows (1: the shared-taps handle; channels: a bank), the twiddles and the scratch of a
+ * handle that firm_part_size has sized */
+static int firm_build_part(firm_t *f, const float *taps, int rows, const char *who)
+{
+    const int N = f->part_n, P = (f->flt_len + N / 2 - 1) / (N / 2);
+    const size_t hbytes = sizeof(float) * 2 * (size_t)rows * (size_t)P * (size_t)N;
     float *tw = (float *)malloc(sizeof(float) * (size_t)N);
     double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = (hp && tw && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
+    int rc = (tw && cs) ? LLZ_OK : LLZ_ERR_NOMEM;
     if (rc == LLZ_OK) {
-        for (int i = 0; i < N; i++) {
-            const double ang = 2.0 * M_PI * (double)i / (double)N;
-            cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-            cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-        }
+        firm_part_cs_table(cs, N);
         for (int m = 0; m < N / 2; m++) firm_w(&tw[2 * m], cs, m);
-        for (int p = 0; p < P; p++) {
-            for (int i = 0; i < N; i++) {
-                const long t = (long)p * B + i;
-                z[2 * i] = (i < B && t < f->flt_len) ? (double)taps[t] : 0.0;
-                z[2 * i + 1] = 0.0;
-            }
-            for (int span = N; span >= 2; span /= 2) {
-                const int half = span / 2, step = N / span;
-                for (int base = 0; base < N; base += span)
-                    for (int j = 0; j < half; j++) {
-                        double *a = z + 2 * (base + j), *b = a + 2 * half;
-                        const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
-                        const double dr = a[0] - b[0], di = a[1] - b[1];
-                        a[0] += b[0]; a[1] += b[1];
-                        b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
-                    }
-            }
-            float *row = hp + 2 * (size_t)p * (size_t)N;
-            for (int i = 0; i < 2 * N; i++) row[i] = (float)(z[i] / N);
+        f->d_hpart = (float *)llzs_malloc(hbytes);
+        if (!f->d_hpart) {
+            llzs_set_error("%s: no device memory for the partition spectra: %zu B asked for (%d rows x %d partitions x %d points)",
+                           who, hbytes, rows, P, N);
+            rc = LLZ_ERR_NOMEM;
         }
-        f->d_hpart = (float *)llzs_malloc(sizeof(float) * hcount);
+    }
+    if (rc == LLZ_OK) {
         f->d_ptw = (float *)llzs_malloc(sizeof(float) * (size_t)N);
         f->d_scratch = (float *)llzs_malloc(f->scratch_bytes);
-        if (!f->d_hpart || !f->d_ptw || !f->d_scratch) rc = LLZ_ERR_NOMEM;
+        if (!f->d_ptw || !f->d_scratch) rc = LLZ_ERR_NOMEM;
     }
     /* tables through llzs_h2d_table, in a fixed order: a sharded init records and broadcasts them */
-    if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_hpart, hp, sizeof(float) * hcount);
+    if (rc == LLZ_OK) rc = firm_part_load_rows(f, 0, rows, taps, 1);
     if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_ptw, tw, sizeof(float) * (size_t)N);
-    free(hp); free(tw); free(cs); free(z);
+    free(tw); free(cs);
     return rc;
 }
 
@@ -414,7 +469,8 @@ unsigned long llz_fir_filter_mc_init(int channels, int frame_len, const float *t
     if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[1], 0, hist_bytes, NULL);
     if (rc == LLZ_OK) rc = llzs_memset(f->d_zero, 0, hist_bytes, NULL);
     if (rc == LLZ_OK && ols) rc = firm_build_ols_tables(f, taps, ols->nfft);
-    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_PARTITIONED) rc = firm_build_part(f, taps);
+    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_PARTITIONED) rc = firm_part_size(f, "llz_fir_filter_mc_init");
+    if (rc == LLZ_OK && algo == LLZ_FIR_ALGO_PARTITIONED) rc = firm_build_part(f, taps, 1, "llz_fir_filter_mc_init");
     if (rc == LLZ_OK) rc = llzs_sync(NULL);
     free(padded);
     if (rc != LLZ_OK) {
@@ -518,7 +574,10 @@ static int firm_launch(firm_t *f, const float *d_in, float *d_out, int n, long p
     const float *hist = f->flt_len > 1 ? f->d_hist[f->cur] : NULL;
     const struct firm_ols_rung *ols = firm_ols_rung(algo);
     int rc;
-    if (f->tag == LLZ_TAG_FIRB)
+    if (f->tag == LLZ_TAG_FIRB && algo == LLZ_FIR_ALGO_PARTITIONED)
+        rc = llzs_fir_part_bank_f32(f->part_n, f->d_hpart, f->d_ptw, f->d_scratch, firm_part_avail(f), d_in, d_out, hist,
+                                    f->channels, n, pitch_in, pitch_out, f->flt_len, f->stream);
+    else if (f->tag == LLZ_TAG_FIRB)
         rc = ols ? llzs_fir_bank_ols_f32(f->d_hbank, f->ols.twid, d_in, d_out, hist, f->channels, n, pitch_in, pitch_out,
                                          f->flt_len, f->stream)
                  : llzs_fir_td_bank_f32(d_in, d_out, hist, f->d_taps, f->channels, n, pitch_in, pitch_out, f->flt_len,
@@ -713,7 +772,8 @@ unsigned long llz_fir_bank_mc_init(int channels, int frame_len, const float *tap
     if (algo == LLZ_FIR_ALGO_AUTO) algo = (flt_len > 32 && flt_len <= 257) ? LLZ_FIR_ALGO_OVERLAP_SAVE : LLZ_FIR_ALGO_TIME;
     if (algo != LLZ_FIR_ALGO_TIME && algo != LLZ_FIR_ALGO_OVERLAP_SAVE) {
         llzs_set_error("llz_fir_bank_mc_init: algo %d is not built for a bank; accepted: LLZ_FIR_ALGO_AUTO (0), LLZ_FIR_ALGO_TIME "
-                       "(1), LLZ_FIR_ALGO_OVERLAP_SAVE (2, 1..257 taps)", algo);
+                       "(1), LLZ_FIR_ALGO_OVERLAP_SAVE (2, 1..257 taps); a partitioned bank (1..%d taps) comes from "
+                       "llz_fir_pbank_mc_init", algo, LLZS_FIR_PART_MAX_TAPS);
         return LLZ_BAD_HANDLE;
     }
     if (algo == LLZ_FIR_ALGO_OVERLAP_SAVE && flt_len > 257) {
@@ -827,7 +887,8 @@ int llz_fir_bank_mc_set_taps(unsigned long handle, int first, int count, const f
         return LLZ_ERR_ARG;
     }
     const int prev = llzs_device_enter(f->device);
-    const int rc = firb_load_rows(f, first, count, taps, 0);
+    const int rc = f->algo == LLZ_FIR_ALGO_PARTITIONED ? firm_part_load_rows(f, first, count, taps, 0)
+                                                       : firb_load_rows(f, first, count, taps, 0);
     llzs_device_leave(prev);
     return rc;
 }
@@ -847,4 +908,77 @@ int llz_fir_bank_mc_set_stream(unsigned long handle, void *stream)
     if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB)) return LLZ_ERR_ARG;
     ((firm_t *)handle)->stream = stream;
     return LLZ_OK;
+}
+
+/* =====================================================================================================
+ * Part 4: the partitioned bank -- a bank handle (LLZ_TAG_FIRB) of LLZ_FIR_ALGO_PARTITIONED: part 2's partitioned form with
+ * the spectra of every channel's own taps ([channels][P][N], k_fir_part_mac<true>).  No time-domain tap table: the flush
+ * runs through the partitioned launcher.  Every other call is part 3's.
+ * ===================================================================================================== */
+
+unsigned long llz_fir_pbank_mc_init(int channels, int frame_len, const float *taps, int flt_len)
+{
+    if (channels < 1 || channels > 65535 || frame_len < 1 || !taps) {
+        llzs_set_error("llz_fir_pbank_mc_init: channels %d (1..65535) frame_len %d%s", channels, frame_len, taps ? "" : ", no taps");
+        return LLZ_BAD_HANDLE;
+    }
+    if (flt_len < 1 || flt_len > LLZS_FIR_PART_MAX_TAPS) {
+        llzs_set_error("llz_fir_pbank_mc_init: the partitioned overlap-save takes 1..%d taps, not %d", LLZS_FIR_PART_MAX_TAPS,
+                       flt_len);
+        return LLZ_BAD_HANDLE;
+    }
+    firm_t *f = (firm_t *)calloc(1, sizeof(*f));
+    if (!f) return LLZ_BAD_HANDLE;
+    f->tag = LLZ_TAG_FIRB;
+    f->who = "llz_fir_bank_mc";
+    f->device = llzs_device_get();
+    f->channels = channels; f->frame_len = frame_len; f->flt_len = flt_len; f->algo = LLZ_FIR_ALGO_PARTITIONED;
+
+    const size_t hist_bytes = sizeof(float) * (size_t)channels * (size_t)(flt_len > 1 ? flt_len - 1 : 1);
+    int rc = firm_part_size(f, "llz_fir_pbank_mc_init");          /* a scratch cap too small is refused before any allocation */
+    if (rc == LLZ_OK) {
+        f->d_hist[0] = (float *)llzs_malloc(hist_bytes);
+        f->d_hist[1] = (float *)llzs_malloc(hist_bytes);
+        f->d_zero = (float *)llzs_malloc(hist_bytes);
+        if (!f->d_hist[0] || !f->d_hist[1] || !f->d_zero) rc = LLZ_ERR_NOMEM;
+    }
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[0], 0, hist_bytes, NULL);
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_hist[1], 0, hist_bytes, NULL);
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_zero, 0, hist_bytes, NULL);
+    if (rc == LLZ_OK) rc = firm_build_part(f, taps, channels, "llz_fir_pbank_mc_init");
+    if (rc == LLZ_OK) rc = llzs_sync(NULL);
+    if (rc != LLZ_OK) {
+        firm_destroy(f);
+        return LLZ_BAD_HANDLE;
+    }
+    return (unsigned long)f;
+}
+
+unsigned long llz_fir_pbank_mc_init_f64taps(int channels, int frame_len, const double *taps, int flt_len)
+{
+    if (!taps || channels < 1 || channels > 65535 || flt_len < 1 || flt_len > LLZS_FIR_PART_MAX_TAPS) {
+        llzs_set_error("llz_fir_pbank_mc_init_f64taps: channels %d (1..65535), flt_len %d (1..%d)%s", channels, flt_len,
+                       LLZS_FIR_PART_MAX_TAPS, taps ? "" : ", no taps");
+        return LLZ_BAD_HANDLE;
+    }
+    const size_t count = (size_t)channels * (size_t)flt_len;
+    float *t = (float *)malloc(sizeof(float) * count);
+    if (!t) {
+        llzs_set_error("llz_fir_pbank_mc_init_f64taps: no host memory for %zu taps", count);
+        return LLZ_BAD_HANDLE;
+    }
+    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
+    unsigned long h = llz_fir_pbank_mc_init(channels, frame_len, t, flt_len);
+    free(t);
+    return h;
+}
+
+int llz_fir_pbank_mc_plan(unsigned long handle, int n, int out[4])
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRB) || ((firm_t *)handle)->algo != LLZ_FIR_ALGO_PARTITIONED || n < 1 || !out) {
+        llzs_set_error("llz_fir_pbank_mc_plan: not a handle of llz_fir_pbank_mc_init, n %d < 1 or no out", n);
+        return LLZ_ERR_ARG;
+    }
+    const firm_t *f = (const firm_t *)handle;
+    return llzs_fir_part_plan(f->part_n, f->flt_len, n, f->channels, firm_part_avail(f), out);
 }

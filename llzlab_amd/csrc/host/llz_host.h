@@ -28,6 +28,11 @@ int llz_host_mdct_on_device(unsigned long handle, const double *d_src, double *d
 /* cos then sin of 2 pi i / size, i < size, as llz_fft_init builds them (llz_fft.c:222-229), uploaded; NULL on failure */
 double *llz_host_fft_table_f64(int size);
 
+/* llz_fir_host.c: one tap row into the [P][N] complex floats of its partition spectra (LLZ_FIR_ALGO_PARTITIONED), in the
+ * order of a decimation-in-frequency transform's output; cs: 2 N doubles, cos then sin of 2 pi i / N with exact quadrant
+ * values; z: 2 N doubles of work space */
+void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, const double *cs, double *z);
+
 /* Caller buffers: llzs_is_device_ptr(p) is 1 for device memory of the CURRENT device (used in place), 0 for host memory
  * (staged through the GPU) and LLZ_ERR_ARG, with a message, for device memory that lives on another device -- a handle
  * binds its device before it looks at the caller's pointers, so a buffer of the wrong GPU is refused instead of faulting. */

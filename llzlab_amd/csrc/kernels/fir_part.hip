@@ -1,5 +1,5 @@
 // fir_part.hip -- K4d: uniformly partitioned overlap-save, the batch FIR for long filters (LLZ_FIR_ALGO_PARTITIONED, 1..131073
-// taps, one tap set for every channel).
+// taps, one tap set for every channel), and K4e: the same three kernels with a tap set per channel (the partitioned bank).
 //
 // The taps are cut into P = ceil(flt_len / B) partitions of B = N / 2 taps, H_p = DFT_N(partition p, zero-padded) / N.  With
 // X_k = DFT_N of samples [(k - 1) B, (k + 1) B) of a channel's frame (negative indices: the history, before it zeros),
@@ -28,6 +28,11 @@
 //     PART_RUN).  Every sum runs over p ascending in one thread: no atomics, the same call gives the same bits.
 //   * Channels go in passes of as many as the scratch holds ((2 Kh + P - 1) x 8 N bytes per channel), in sequence on the
 //     stream.  All index arithmetic over channels x blocks x N is size_t / long.
+//   * The bank (K4e): only the product reads the taps, so only the product kernel has a second instance, BANK = true, which
+//     reads channel c's spectra at H + c P N.  A template parameter, not a pitch argument: the shared instance keeps the
+//     instructions it had.  In passes H advances with in, out and hist.  Measured 2 .. 8 % behind the shared form (H is no
+//     longer one table in L2); reading Z with nontemporal loads to spare H's cache lines was 6 .. 17 % behind and dropped
+//     (DESIGN.md K4e).
 #include "common.hpp"
 
 namespace {
@@ -151,7 +156,9 @@ k_fir_part_fwd(const float *__restrict__ in, const float *__restrict__ hist, con
     for (int i = tid; i < N; i += PART_THREADS) dst[i] = part_lds[i];
 }
 
-// K4d-2: workgroup (run, bin tile, c): Y_q[bin] = sum_{p < P} Z_{q-p}[bin] H_p[bin] for the PART_RUN blocks q0 .. of the run
+// K4d-2: workgroup (run, bin tile, c): Y_q[bin] = sum_{p < P} Z_{q-p}[bin] H_p[bin] for the PART_RUN blocks q0 .. of the run.
+// BANK: H is [channels][P][N], channel c's own spectra
+template <bool BANK>
 __global__ void __launch_bounds__(PART_THREADS)
 k_fir_part_mac(const float2 *__restrict__ Z, const float2 *__restrict__ H, float2 *__restrict__ Y, part_geom G, int tiles)
 {
@@ -161,7 +168,7 @@ k_fir_part_mac(const float2 *__restrict__ Z, const float2 *__restrict__ H, float
     const long q0 = run * PART_RUN;
     const size_t N = (size_t)G.N;
     const float2 *zc = Z + (size_t)c * (size_t)G.S * N + bin;          // spectrum s = q + P - 1 at zc[s * N]
-    const float2 *h = H + bin;
+    const float2 *h = BANK ? H + (size_t)c * (size_t)G.P * N + bin : H + bin;
     float2 acc[PART_RUN], w[PART_RUN];
 #pragma unroll
     for (int r = 0; r < PART_RUN; r++) {
@@ -275,7 +282,7 @@ extern "C" int llzs_fir_part_plan(int nfft, int flt_len, int n, int channels, si
     return LLZ_OK;
 }
 
-template <int LOG2N>
+template <int LOG2N, bool BANK>
 static int part_run_pass(const part_geom &G, const float2 *H, const float2 *tw, float2 *Z, float2 *Y, const float *in, float *out,
                          const float *hist, int count, hipStream_t st)
 {
@@ -285,16 +292,17 @@ static int part_run_pass(const part_geom &G, const float2 *H, const float2 *tw, 
     const long runs = (G.Kh + PART_RUN - 1) / PART_RUN;
     hipLaunchKernelGGL(k_fir_part_fwd<LOG2N>, dim3((unsigned)G.S, (unsigned)count), dim3(PART_THREADS), lds, st, in, hist, tw, Z, G);
     LLZ_LAUNCH_CHECK("k_fir_part_fwd");
-    hipLaunchKernelGGL(k_fir_part_mac, dim3((unsigned)(runs * tiles), (unsigned)count), dim3(PART_THREADS), 0, st, Z, H, Y, G, tiles);
+    hipLaunchKernelGGL(k_fir_part_mac<BANK>, dim3((unsigned)(runs * tiles), (unsigned)count), dim3(PART_THREADS), 0, st, Z, H, Y, G, tiles);
     LLZ_LAUNCH_CHECK("k_fir_part_mac");
     hipLaunchKernelGGL(k_fir_part_inv<LOG2N>, dim3((unsigned)G.Kh, (unsigned)count), dim3(PART_THREADS), lds, st, Y, tw, out, G);
     LLZ_LAUNCH_CHECK("k_fir_part_inv");
     return LLZ_OK;
 }
 
-extern "C" int llzs_fir_part_f32(int nfft, const float *hpart, const float *tw, float *scratch, size_t scratch_bytes,
-                                 const float *in, float *out, const float *hist, int channels, int n, long in_pitch,
-                                 long out_pitch, int flt_len, void *stream)
+// bank: hpart is [channels][P][nfft] complex, a channel's own spectra; else [P][nfft], one tap set shared by all channels
+static int part_launch(int nfft, const float *hpart, bool bank, const float *tw, float *scratch, size_t scratch_bytes,
+                       const float *in, float *out, const float *hist, int channels, int n, long in_pitch, long out_pitch,
+                       int flt_len, void *stream)
 {
     int plan[4];
     if (!hpart || !tw || !scratch || !in || !out || in_pitch < n || out_pitch < n || channels > 65535 || (flt_len > 1 && !hist)) {
@@ -308,21 +316,45 @@ extern "C" int llzs_fir_part_f32(int nfft, const float *hpart, const float *tw, 
         llzs_set_error("fir_part_f32: %d samples per call are more blocks than a grid holds", n);
         return LLZ_ERR_RANGE;
     }
+    const size_t h_pitch = bank ? 2 * (size_t)G.P * (size_t)nfft : 0;     // floats from one channel's spectra to the next
     const int per_pass = plan[2];
     float2 *Z = reinterpret_cast<float2 *>(scratch);
     float2 *Y = Z + (size_t)per_pass * (size_t)G.S * (size_t)nfft;
-    const float2 *H = reinterpret_cast<const float2 *>(hpart), *W = reinterpret_cast<const float2 *>(tw);
+    const float2 *W = reinterpret_cast<const float2 *>(tw);
+    hipStream_t st = as_stream(stream);
     for (int c0 = 0; c0 < channels && rc == LLZ_OK; c0 += per_pass) {
         const int count = channels - c0 < per_pass ? channels - c0 : per_pass;
         const float *pin = in + (size_t)c0 * (size_t)in_pitch;
         float *pout = out + (size_t)c0 * (size_t)out_pitch;
         const float *ph = flt_len > 1 ? hist + (size_t)c0 * (size_t)(flt_len - 1) : nullptr;
+        // a bank's spectra advance with the channels of the pass
+        const float2 *H = reinterpret_cast<const float2 *>(hpart + (size_t)c0 * h_pitch);
         switch (nfft) {
-        case 1024: rc = part_run_pass<10>(G, H, W, Z, Y, pin, pout, ph, count, as_stream(stream)); break;
-        case 2048: rc = part_run_pass<11>(G, H, W, Z, Y, pin, pout, ph, count, as_stream(stream)); break;
-        case 4096: rc = part_run_pass<12>(G, H, W, Z, Y, pin, pout, ph, count, as_stream(stream)); break;
-        default: rc = part_run_pass<13>(G, H, W, Z, Y, pin, pout, ph, count, as_stream(stream)); break;
+        case 1024: rc = bank ? part_run_pass<10, true>(G, H, W, Z, Y, pin, pout, ph, count, st)
+                             : part_run_pass<10, false>(G, H, W, Z, Y, pin, pout, ph, count, st); break;
+        case 2048: rc = bank ? part_run_pass<11, true>(G, H, W, Z, Y, pin, pout, ph, count, st)
+                             : part_run_pass<11, false>(G, H, W, Z, Y, pin, pout, ph, count, st); break;
+        case 4096: rc = bank ? part_run_pass<12, true>(G, H, W, Z, Y, pin, pout, ph, count, st)
+                             : part_run_pass<12, false>(G, H, W, Z, Y, pin, pout, ph, count, st); break;
+        default: rc = bank ? part_run_pass<13, true>(G, H, W, Z, Y, pin, pout, ph, count, st)
+                           : part_run_pass<13, false>(G, H, W, Z, Y, pin, pout, ph, count, st); break;
         }
     }
     return rc;
+}
+
+extern "C" int llzs_fir_part_f32(int nfft, const float *hpart, const float *tw, float *scratch, size_t scratch_bytes,
+                                 const float *in, float *out, const float *hist, int channels, int n, long in_pitch,
+                                 long out_pitch, int flt_len, void *stream)
+{
+    return part_launch(nfft, hpart, false, tw, scratch, scratch_bytes, in, out, hist, channels, n, in_pitch, out_pitch, flt_len, stream);
+}
+
+// the bank: hbank [channels][P][nfft] complex, channel c filtered with its own spectra
+extern "C" int llzs_fir_part_bank_f32(int nfft, const float *hbank, const float *tw, float *scratch, size_t scratch_bytes,
+                                      const float *in, float *out, const float *hist, int channels, int n, long in_pitch,
+                                      long out_pitch, int flt_len, void *stream)
+{
+    return part_launch(nfft, hbank, true, tw, scratch, scratch_bytes, in, out, hist, channels, n, in_pitch, out_pitch,
+                       flt_len, stream);
 }

@@ -152,6 +152,10 @@ int llzs_fir_part_plan(int nfft, int flt_len, int n, int channels, size_t scratc
 int llzs_fir_part_f32(int nfft, const float *hpart, const float *tw, float *scratch, size_t scratch_bytes, const float *in,
                       float *out, const float *hist, int channels, int n, long in_pitch, long out_pitch, int flt_len,
                       void *stream);
+/* the same with a tap set per channel: hbank = [channels][P][nfft] complex floats, channel c's rows as hpart's */
+int llzs_fir_part_bank_f32(int nfft, const float *hbank, const float *tw, float *scratch, size_t scratch_bytes, const float *in,
+                           float *out, const float *hist, int channels, int n, long in_pitch, long out_pitch, int flt_len,
+                           void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

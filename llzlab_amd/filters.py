@@ -172,7 +172,9 @@ class FirFilterMC:
 
 
 class FirBankMC:
-    """channels x frame_len float32, planar, one tap set per channel: llz_fir_bank_mc_*.  taps: [channels, flt_len]."""
+    """channels x frame_len float32, planar, one tap set per channel: llz_fir_bank_mc_*.  taps: [channels, flt_len].
+    algo=FIR_ALGO_PARTITIONED is the partitioned bank (1..131073 taps, llz_fir_pbank_mc_init); every call but the init and
+    partition_plan is the bank's."""
 
     def __init__(self, channels, frame_len, taps, algo=FIR_ALGO_AUTO, stream=None):
         self._L = capi.lib()
@@ -180,9 +182,14 @@ class FirBankMC:
         if taps.ndim != 2 or taps.shape[0] != channels or taps.shape[1] < 1:
             raise LlzError(f"FirBankMC: taps must be [channels = {channels}, flt_len], got {taps.shape} "
                            "(one tap set for every channel is FirFilterMC)")
-        self.handle = check_handle(
-            self._L.llz_fir_bank_mc_init_f64taps(channels, frame_len, taps.ctypes.data, taps.shape[1], algo),
-            "llz_fir_bank_mc_init")
+        if algo == FIR_ALGO_PARTITIONED:
+            self.handle = check_handle(
+                self._L.llz_fir_pbank_mc_init_f64taps(channels, frame_len, taps.ctypes.data, taps.shape[1]),
+                "llz_fir_pbank_mc_init")
+        else:
+            self.handle = check_handle(
+                self._L.llz_fir_bank_mc_init_f64taps(channels, frame_len, taps.ctypes.data, taps.shape[1], algo),
+                "llz_fir_bank_mc_init")
         self.channels, self.frame_len, self.flt_len = channels, frame_len, taps.shape[1]
         self.algo = self._L.llz_fir_bank_mc_algo(self.handle)
         if stream is not None:
@@ -190,6 +197,13 @@ class FirBankMC:
 
     def set_stream(self, stream):
         check(self._L.llz_fir_bank_mc_set_stream(self.handle, _stream_ptr(stream)), "set_stream")
+
+    def partition_plan(self, n):
+        """(transform points, partitions, channels per pass, passes) of a call of n samples on a partitioned bank under the
+        tunes set now (llz_fir_pbank_mc_plan; nothing is launched)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_fir_pbank_mc_plan(self.handle, int(n), out), "llz_fir_pbank_mc_plan")
+        return tuple(out)
 
     def set_taps(self, first, taps):
         """replace the taps of channels first .. first + len(taps) - 1; taps: [count, flt_len]"""
