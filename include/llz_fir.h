@@ -9,6 +9,7 @@
  *  -- the path the MI355X kernels are built for.
  * Part 3 is the same batch with a tap set per channel: the filter bank (time domain, and overlap-save up to 257 taps).
  * Part 4 is the bank for long filters: the partitioned overlap-save of part 2 with a tap set per channel, 1..131073 taps.
+ * Part 5 is the block convolver for short calls against long filters: it keeps the spectra of its input between calls.
  */
 #ifndef LLZ_FIR_H
 #define LLZ_FIR_H
@@ -151,6 +152,50 @@ unsigned long llz_fir_pbank_mc_init_f64taps(int channels, int frame_len, const d
 /* out = {N, P, channels per pass, passes} as llz_fir_filter_mc_partition_plan reports them; LLZ_ERR_ARG for every handle that
  * is not llz_fir_pbank_mc_init's (llz_fir_filter_mc_partition_plan in turn refuses every bank handle) */
 int           llz_fir_pbank_mc_plan(unsigned long handle, int n, int out[4]);
+
+/* ---- Part 5: the stream convolver -- short blocks against long filters, spectra kept between calls ------------------- */
+
+/* Real-time convolution: frames of 64..4096 samples against up to 131073 taps (room and cabinet responses, BRIR sets).  A
+ * uniformly partitioned overlap-save whose block is the CALLER'S: block (a power of two, 64..4096), frame_len = k x block with
+ * k >= 1, P = ceil(flt_len / block) partitions.  The spectra of the last input blocks of every channel stay in device memory
+ * between calls, in a ring of R = P + k - 1 half-spectra of `block` packed bins (a frequency-domain delay line), beside the
+ * last `block` input samples: a call transforms only its k new blocks, sums the ring against the tap spectra and inverts --
+ * one kernel launch, about P x block x 8 bytes of ring read per channel and block (1 MB at 131073 taps, at any block).
+ * Which form when: this one for calls of ONE OR A FEW blocks, where LLZ_FIR_ALGO_PARTITIONED and llz_fir_pbank_mc_init redo
+ * the whole history (about frame_len + flt_len samples of work per call) and cannot go below their 512..4096-sample block;
+ * those two for LONG calls, whose blocks they run in parallel where this form walks a call's blocks in sequence, one
+ * workgroup per channel.
+ * channels 1..65535, flt_len 1..131073.  rows == 1: taps = HOST pointer to flt_len floats, one tap set for all channels;
+ * rows == channels: planar [channels][flt_len], a tap set per channel (the double variant rounds to float once).  A bank of
+ * equal rows gives the bits of the shared handle.  Device memory: rows x P x block x 8 bytes of tap spectra and channels x R x
+ * block x 8 bytes of ring (about 1 MB per channel at 131073 taps); when an allocation fails the message states the bytes
+ * asked for.  Every refusal leaves a message of its own.  Returns (unsigned long)-1 on failure (llz_hip_last_error() says why).
+ * The result is llz_fir_filter_mc's on the concatenated stream (to rounding: the summation order differs). */
+unsigned long llz_fir_stream_mc_init(int channels, int block, int frame_len, const float *taps, int rows, int flt_len);
+unsigned long llz_fir_stream_mc_init_f64taps(int channels, int block, int frame_len, const double *taps, int rows, int flt_len);
+void          llz_fir_stream_mc_uninit(unsigned long handle);
+/* planar [channels][frame_len] float32 in and out, device memory (used in place, asynchronous on the handle's stream) or host
+ * memory (staged, synchronous); frame_len as at init; out may not alias or overlap in (LLZ_ERR_ARG).  Returns frame_len, or a
+ * negative LLZ_ERR_* code.  The ring's head is kept on the host and passed by value with each launch (no device-side
+ * counter), so a call CAPTURED INTO A GRAPH would replay one and the same ring slot: graph capture is not supported.  How
+ * calls group the blocks of a stream does not change a bit of the result. */
+int llz_fir_stream_mc(unsigned long handle, const float *in, float *out, int frame_len);
+/* out: planar [channels][flt_len-1], the response to ceil((flt_len-1) / block) zero blocks through the same kernel; returns
+ * flt_len-1 and leaves the handle as llz_fir_stream_mc_reset does: reused, it gives the bits of a fresh handle.  With one tap
+ * nothing is written, out may be NULL, and the call returns 0 after the same reset */
+int llz_fir_stream_mc_flush(unsigned long handle, float *out);
+/* the delay line (ring and last block) to zeros, ordered on the handle's stream; the taps stay */
+int llz_fir_stream_mc_reset(unsigned long handle);
+/* replace tap rows [first, first+count) between calls; taps: HOST [count][flt_len].  rows == channels: any range inside
+ * [0, channels); rows == 1: only first 0, count 1.  Ordered on the handle's stream behind the calls already issued.  The
+ * delay line is kept, and it holds INPUT spectra: from the next call on the output is the new taps applied to the whole
+ * input so far (no crossfade). */
+int llz_fir_stream_mc_set_taps(unsigned long handle, int first, int count, const float *taps);
+/* out = {N = 2 block, P = ceil(flt_len / block), ring slots R, blocks per call k}; nothing is launched */
+int llz_fir_stream_mc_plan(unsigned long handle, int out[4]);
+int llz_fir_stream_mc_flt_len(unsigned long handle);
+/* stream: a hipStream_t passed as void* (NULL = default stream) */
+int llz_fir_stream_mc_set_stream(unsigned long handle, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,392 @@
+/* llz_fir_stream_host.c -- include/llz_fir.h part 5: llz_fir_stream_mc, the block convolver that keeps the spectra of its input
+ * between calls (kernel K4f, fir_stream.hip).  Its own handle and tag: the history of a firm_t (a ping-pong of flt_len - 1
+ * samples and the tail kernel) does not apply here -- the history lives as a ring of input spectra plus the last input block.
+ * Staging, pointer classification and error conventions are those of llz_fir_host.c. */
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include "llz_host.h"
+
+#define FIRS_MIN_BLOCK 64
+#define FIRS_MAX_BLOCK 4096
+
+typedef struct {
+    int tag;                    /* LLZ_TAG_FIRS */
+    int device;                 /* the device the handle's buffers live on: every call binds it */
+    int channels, block, frame_len, flt_len, rows;
+    int k, P, R;                /* blocks per call, partitions, ring slots = P + k - 1 */
+    int head;                   /* the ring slot the next block writes: kept here, passed by value with each launch */
+    float *d_h;                 /* [rows][P][block] complex: the partition spectra (llz_host_stream_spectra) */
+    float *d_tw;                /* [block / 2] complex W_block^m, then [block] complex W_N^bitrev(i) */
+    float *d_ring;              /* [channels][R][block] complex: spectra of the last R input blocks */
+    float *d_prev;              /* [channels][block]: the last input block */
+    void *stream;
+    llz_stage_t st_in, st_out;  /* only for callers passing host memory */
+} firs_t;
+
+static void firs_destroy(firs_t *f)
+{
+    if (!f) return;
+    llzs_free(f->d_h); llzs_free(f->d_tw); llzs_free(f->d_ring); llzs_free(f->d_prev);
+    llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
+    f->tag = 0;
+    free(f);
+}
+
+/* cos then sin of 2 pi i / N, i < N, with exact quadrant values */
+static void firs_cs_table(double *cs, int N)
+{
+    for (int i = 0; i < N; i++) {
+        const double ang = 2.0 * M_PI * (double)i / (double)N;
+        cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
+        cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
+    }
+}
+
+static int firs_bitrev(int i, int bits)
+{
+    int r = 0;
+    for (int b = 0; b < bits; b++) r |= ((i >> b) & 1) << (bits - 1 - b);
+    return r;
+}
+
+/* Row p: the N-point transform of partition p by radix-2 decimation in frequency in double, whose output entry e is bin
+ * bitrev_N(e).  A bin k < block has a zero top bit, so it sits at the even entry 2 bitrev_block(k): the packed row is the even
+ * entries as they lie, and the Nyquist bin (k = block) is entry 1.  Shared and per-channel handles both build their spectra
+ * here, so equal taps give equal float32 entries. */
+void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int block, const double *cs, double *z)
+{
+    const int N = 2 * block, P = (flt_len + block - 1) / block;
+    const double scale = 1.0 / (2.0 * (double)N);
+    for (int p = 0; p < P; p++) {
+        for (int i = 0; i < N; i++) {
+            const long t = (long)p * block + i;
+            z[2 * i] = (i < block && t < flt_len) ? (double)taps[t] : 0.0;
+            z[2 * i + 1] = 0.0;
+        }
+        for (int span = N; span >= 2; span /= 2) {
+            const int half = span / 2, step = N / span;
+            for (int base = 0; base < N; base += span)
+                for (int j = 0; j < half; j++) {
+                    double *a = z + 2 * (base + j), *b = a + 2 * half;
+                    const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
+                    const double dr = a[0] - b[0], di = a[1] - b[1];
+                    a[0] += b[0]; a[1] += b[1];
+                    b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
+                }
+        }
+        float *row = dst + 2 * (size_t)p * (size_t)block;
+        row[0] = (float)(z[0] * scale);
+        row[1] = (float)(z[2] * scale);
+        for (int i = 1; i < block; i++) {
+            row[2 * i] = (float)(z[4 * i] * scale);
+            row[2 * i + 1] = (float)(z[4 * i + 1] * scale);
+        }
+    }
+}
+
+/* host staging of the spectra: whole tap rows up to this many bytes at a time, one row at least (1 MB at 131073 taps) */
+#define FIRS_STAGE_BYTES ((size_t)8 << 20)
+
+/* build the spectra of tap rows [first, first + count) (taps: [count][flt_len]) and upload them in chunks of rows: at init as
+ * tables, from set_taps on the handle's stream behind the calls already issued */
+static int firs_load_rows(firs_t *f, int first, int count, const float *taps, int at_init)
+{
+    const int N = 2 * f->block;
+    const size_t row = 2 * (size_t)f->P * (size_t)f->block;         /* floats of one row's spectra */
+    size_t chunk = FIRS_STAGE_BYTES / (sizeof(float) * row);
+    if (chunk < 1) chunk = 1;
+    if (chunk > (size_t)count) chunk = (size_t)count;
+    float *hp = (float *)malloc(sizeof(float) * row * chunk);
+    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    int rc = (hp && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) firs_cs_table(cs, N);
+    for (size_t r0 = 0; r0 < (size_t)count && rc == LLZ_OK; r0 += chunk) {
+        const size_t rows = (size_t)count - r0 < chunk ? (size_t)count - r0 : chunk;
+        for (size_t r = 0; r < rows; r++)
+            llz_host_stream_spectra(hp + r * row, taps + (r0 + r) * (size_t)f->flt_len, f->flt_len, f->block, cs, z);
+        float *d_h = f->d_h + ((size_t)first + r0) * row;
+        rc = at_init ? llzs_h2d_table(d_h, hp, sizeof(float) * row * rows) : llzs_h2d(d_h, hp, sizeof(float) * row * rows, f->stream);
+    }
+    free(hp); free(cs); free(z);
+    return rc;
+}
+
+/* the transform's twiddles W_block^m, m < block / 2, then the split twiddles by position: W_N^bitrev(i), i < block */
+static int firs_load_twiddles(firs_t *f)
+{
+    const int B = f->block, N = 2 * B;
+    int bits = 0;
+    while ((1 << bits) < B) bits++;
+    const size_t count = (size_t)B / 2 + (size_t)B;
+    float *tw = (float *)malloc(sizeof(float) * 2 * count);
+    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
+    int rc = (tw && cs) ? LLZ_OK : LLZ_ERR_NOMEM;
+    if (rc == LLZ_OK) {
+        firs_cs_table(cs, N);
+        for (int m = 0; m < B / 2; m++) {
+            tw[2 * m] = (float)cs[2 * (2 * m)];
+            tw[2 * m + 1] = (float)(-cs[2 * (2 * m) + 1]);
+        }
+        for (int i = 0; i < B; i++) {
+            const int k = firs_bitrev(i, bits);
+            tw[2 * (B / 2 + i)] = (float)cs[2 * k];
+            tw[2 * (B / 2 + i) + 1] = (float)(-cs[2 * k + 1]);
+        }
+        rc = llzs_h2d_table(f->d_tw, tw, sizeof(float) * 2 * count);
+    }
+    free(tw); free(cs);
+    return rc;
+}
+
+/* the refusals of both inits, each with a message of its own that names `who` and the range */
+static int firs_refuse(const char *who, int channels, int block, int frame_len, const void *taps, int rows, int flt_len)
+{
+    if (channels < 1 || channels > 65535) {
+        llzs_set_error("%s: channels %d outside 1..65535", who, channels);
+        return 1;
+    }
+    if (block < FIRS_MIN_BLOCK || block > FIRS_MAX_BLOCK || (block & (block - 1))) {
+        llzs_set_error("%s: block %d is not a power of two in %d..%d", who, block, FIRS_MIN_BLOCK, FIRS_MAX_BLOCK);
+        return 1;
+    }
+    if (frame_len < block || frame_len % block) {
+        llzs_set_error("%s: frame_len %d is not k x block with k >= 1 (block %d)", who, frame_len, block);
+        return 1;
+    }
+    if (flt_len < 1 || flt_len > LLZS_FIR_PART_MAX_TAPS) {
+        llzs_set_error("%s: flt_len %d outside 1..%d", who, flt_len, LLZS_FIR_PART_MAX_TAPS);
+        return 1;
+    }
+    if (rows != 1 && rows != channels) {
+        llzs_set_error("%s: rows %d is neither 1 (one tap set for all channels) nor channels (%d)", who, rows, channels);
+        return 1;
+    }
+    if (!taps) {
+        llzs_set_error("%s: no taps", who);
+        return 1;
+    }
+    return 0;
+}
+
+/* zeros in the delay line (ring and last block), ordered on the handle's stream */
+static int firs_clear(firs_t *f)
+{
+    int rc = llzs_memset(f->d_ring, 0, sizeof(float) * 2 * (size_t)f->channels * (size_t)f->R * (size_t)f->block, f->stream);
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_prev, 0, sizeof(float) * (size_t)f->channels * (size_t)f->block, f->stream);
+    f->head = 0;
+    return rc;
+}
+
+unsigned long llz_fir_stream_mc_init(int channels, int block, int frame_len, const float *taps, int rows, int flt_len)
+{
+    const char *who = "llz_fir_stream_mc_init";
+    if (firs_refuse(who, channels, block, frame_len, taps, rows, flt_len)) return LLZ_BAD_HANDLE;
+    firs_t *f = (firs_t *)calloc(1, sizeof(*f));
+    if (!f) return LLZ_BAD_HANDLE;
+    f->tag = LLZ_TAG_FIRS;
+    f->device = llzs_device_get();
+    f->channels = channels; f->block = block; f->frame_len = frame_len; f->flt_len = flt_len; f->rows = rows;
+    f->k = frame_len / block;
+    f->P = (flt_len + block - 1) / block;
+    f->R = f->P + f->k - 1;
+    const size_t hbytes = sizeof(float) * 2 * (size_t)rows * (size_t)f->P * (size_t)block;
+    const size_t rbytes = sizeof(float) * 2 * (size_t)channels * (size_t)f->R * (size_t)block;
+    int rc = LLZ_OK;
+    f->d_h = (float *)llzs_malloc(hbytes);
+    if (!f->d_h) {
+        llzs_set_error("%s: no device memory for the partition spectra: %zu B asked for (%d rows x %d partitions x %d bins)", who,
+                       hbytes, rows, f->P, block);
+        rc = LLZ_ERR_NOMEM;
+    }
+    if (rc == LLZ_OK && !(f->d_ring = (float *)llzs_malloc(rbytes))) {
+        llzs_set_error("%s: no device memory for the delay line: %zu B asked for (%d channels x %d slots x %d bins)", who, rbytes,
+                       channels, f->R, block);
+        rc = LLZ_ERR_NOMEM;
+    }
+    if (rc == LLZ_OK) {
+        f->d_tw = (float *)llzs_malloc(sizeof(float) * 2 * ((size_t)block / 2 + (size_t)block));
+        f->d_prev = (float *)llzs_malloc(sizeof(float) * (size_t)channels * (size_t)block);
+        if (!f->d_tw || !f->d_prev) {
+            llzs_set_error("%s: no device memory for the twiddles and the last input blocks: %zu B and %zu B asked for", who,
+                           sizeof(float) * 2 * ((size_t)block / 2 + (size_t)block), sizeof(float) * (size_t)channels * (size_t)block);
+            rc = LLZ_ERR_NOMEM;
+        }
+    }
+    /* tables through llzs_h2d_table, in a fixed order */
+    if (rc == LLZ_OK) rc = firs_load_rows(f, 0, rows, taps, 1);
+    if (rc == LLZ_OK) rc = firs_load_twiddles(f);
+    if (rc == LLZ_OK) rc = firs_clear(f);
+    if (rc == LLZ_OK) rc = llzs_sync(NULL);
+    if (rc != LLZ_OK) {
+        firs_destroy(f);
+        return LLZ_BAD_HANDLE;
+    }
+    return (unsigned long)f;
+}
+
+unsigned long llz_fir_stream_mc_init_f64taps(int channels, int block, int frame_len, const double *taps, int rows, int flt_len)
+{
+    const char *who = "llz_fir_stream_mc_init_f64taps";
+    if (firs_refuse(who, channels, block, frame_len, taps, rows, flt_len)) return LLZ_BAD_HANDLE;
+    const size_t count = (size_t)rows * (size_t)flt_len;
+    float *t = (float *)malloc(sizeof(float) * count);
+    if (!t) {
+        llzs_set_error("%s: no host memory for %zu taps", who, count);
+        return LLZ_BAD_HANDLE;
+    }
+    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
+    unsigned long h = llz_fir_stream_mc_init(channels, block, frame_len, t, rows, flt_len);
+    free(t);
+    return h;
+}
+
+void llz_fir_stream_mc_uninit(unsigned long handle)
+{
+    if (LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS)) {
+        firs_t *f = (firs_t *)handle;
+        const int prev = llzs_device_enter(f->device);
+        llzs_sync(f->stream);
+        firs_destroy(f);
+        llzs_device_leave(prev);
+    }
+}
+
+static int firs_process(firs_t *f, const float *in, float *out, int frame_len)
+{
+    if (frame_len != f->frame_len) {
+        llzs_set_error("llz_fir_stream_mc: frame_len %d != init frame_len %d", frame_len, f->frame_len);
+        return LLZ_ERR_ARG;
+    }
+    if (in == out) {
+        llzs_set_error("llz_fir_stream_mc: in-place filtering is not supported");
+        return LLZ_ERR_ARG;
+    }
+    const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
+    const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
+    if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
+    if (llz_refuse_device_overlap("llz_fir_stream_mc", "in", in, bytes, in_dev, "out", out, bytes, out_dev)) return LLZ_ERR_ARG;
+    const float *d_in = in;
+    float *d_out = out;
+    int rc = LLZ_OK;
+    if (!in_dev) {
+        d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
+        if (!d_in) return LLZ_ERR_NOMEM;
+        rc = llzs_h2d((void *)d_in, in, bytes, f->stream);
+    }
+    if (rc == LLZ_OK && !out_dev) {
+        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
+        if (!d_out) return LLZ_ERR_NOMEM;
+    }
+    if (rc == LLZ_OK)
+        rc = llzs_fir_stream_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, d_in, d_out, f->channels, f->k, 0,
+                                 frame_len, frame_len, frame_len, f->P, f->R, f->head, f->stream);
+    if (rc == LLZ_OK) f->head = (f->head + f->k) % f->R;
+    if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
+    return rc == LLZ_OK ? frame_len : rc;
+}
+
+int llz_fir_stream_mc(unsigned long handle, const float *in, float *out, int frame_len)
+{
+    if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS) || !in || !out) {
+        llzs_set_error("llz_fir_stream_mc: bad handle or NULL buffer");
+        return LLZ_ERR_ARG;
+    }
+    firs_t *f = (firs_t *)handle;
+    const int prev = llzs_device_enter(f->device);       /* the handle's device, whatever the caller has current */
+    const int rc = firs_process(f, in, out, frame_len);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+static int firs_flush(firs_t *f, float *out)
+{
+    const int keep = f->flt_len - 1;
+    if (keep == 0) {                                              /* nothing to emit; the handle still starts over */
+        const int rc0 = firs_clear(f);
+        return rc0 == LLZ_OK ? 0 : rc0;
+    }
+    const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)keep;
+    const int out_dev = llzs_is_device_ptr(out);
+    if (out_dev < 0) return LLZ_ERR_ARG;
+    float *d_out = out;
+    if (!out_dev) {
+        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
+        if (!d_out) return LLZ_ERR_NOMEM;
+    }
+    /* ceil(keep / block) zero blocks behind the input so far, then the delay line to zeros: the handle starts over */
+    int rc = llzs_fir_stream_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, NULL, d_out, f->channels,
+                                 (keep + f->block - 1) / f->block, 1, keep, 0, keep, f->P, f->R, f->head, f->stream);
+    if (rc == LLZ_OK) rc = firs_clear(f);
+    if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
+    return rc == LLZ_OK ? keep : rc;
+}
+
+int llz_fir_stream_mc_flush(unsigned long handle, float *out)
+{
+    /* one tap: nothing to emit, so out may be NULL (an empty buffer has no address worth naming) */
+    if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS) || (!out && ((firs_t *)handle)->flt_len > 1)) {
+        llzs_set_error("llz_fir_stream_mc_flush: bad handle or NULL buffer");
+        return LLZ_ERR_ARG;
+    }
+    firs_t *f = (firs_t *)handle;
+    const int prev = llzs_device_enter(f->device);
+    const int rc = firs_flush(f, out);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_fir_stream_mc_reset(unsigned long handle)
+{
+    if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS)) {
+        llzs_set_error("llz_fir_stream_mc_reset: bad handle");
+        return LLZ_ERR_ARG;
+    }
+    firs_t *f = (firs_t *)handle;
+    const int prev = llzs_device_enter(f->device);
+    const int rc = firs_clear(f);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_fir_stream_mc_set_taps(unsigned long handle, int first, int count, const float *taps)
+{
+    if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS) || !taps) {
+        llzs_set_error("llz_fir_stream_mc_set_taps: bad handle or NULL taps");
+        return LLZ_ERR_ARG;
+    }
+    firs_t *f = (firs_t *)handle;
+    if (first < 0 || count < 1 || first >= f->rows || count > f->rows - first) {
+        llzs_set_error("llz_fir_stream_mc_set_taps: tap rows [%d, %d + %d) outside the handle's [0, %d)%s", first, first, count,
+                       f->rows, f->rows == 1 && f->channels > 1 ? " (one tap set for all channels: only first 0, count 1)" : "");
+        return LLZ_ERR_ARG;
+    }
+    const int prev = llzs_device_enter(f->device);
+    const int rc = firs_load_rows(f, first, count, taps, 0);
+    llzs_device_leave(prev);
+    return rc;
+}
+
+int llz_fir_stream_mc_plan(unsigned long handle, int out[4])
+{
+    if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS) || !out) {
+        llzs_set_error("llz_fir_stream_mc_plan: bad handle or no out");
+        return LLZ_ERR_ARG;
+    }
+    const firs_t *f = (const firs_t *)handle;
+    out[0] = 2 * f->block; out[1] = f->P; out[2] = f->R; out[3] = f->k;
+    return LLZ_OK;
+}
+
+int llz_fir_stream_mc_flt_len(unsigned long handle)
+{
+    return LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS) ? ((firs_t *)handle)->flt_len : LLZ_ERR_ARG;
+}
+
+int llz_fir_stream_mc_set_stream(unsigned long handle, void *stream)
+{
+    if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS)) return LLZ_ERR_ARG;
+    ((firs_t *)handle)->stream = stream;
+    return LLZ_OK;
+}

@@ -17,7 +17,7 @@ int llz_host_design(int kind, double **out, int n, double fc1, double fc2, win_t
 enum {
     LLZ_TAG_FIR1 = 0x4c5a4631, LLZ_TAG_FIRM = 0x4c5a464d, LLZ_TAG_IIR1 = 0x4c5a4931, LLZ_TAG_IIRM = 0x4c5a494d,
     LLZ_TAG_RS1 = 0x4c5a5231, LLZ_TAG_RSM = 0x4c5a524d, LLZ_TAG_FFT1 = 0x4c5a5431, LLZ_TAG_FFTB = 0x4c5a5442,
-    LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942
+    LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942, LLZ_TAG_FIRS = 0x4c5a4653
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))
@@ -32,6 +32,13 @@ double *llz_host_fft_table_f64(int size);
  * order of a decimation-in-frequency transform's output; cs: 2 N doubles, cos then sin of 2 pi i / N with exact quadrant
  * values; z: 2 N doubles of work space */
 void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, const double *cs, double *z);
+
+/* llz_fir_stream_host.c: one tap row into the [P][block] complex floats of its partition spectra for llz_fir_stream_mc, P =
+ * ceil(flt_len / block): row p holds bins 0 .. block of DFT_N(taps[p block .. (p + 1) block), zero-padded), N = 2 block, scaled by
+ * 1 / (2 N), computed in double and rounded to float once.  Entry i > 0 is bin bitrev(i) (over log2 block bits); entry 0
+ * packs the two real bins: (DC, Nyquist).  cs: 2 N doubles, cos then sin of 2 pi i / N with exact quadrant values; z: 2 N
+ * doubles of work space */
+void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int block, const double *cs, double *z);
 
 /* Caller buffers: llzs_is_device_ptr(p) is 1 for device memory of the CURRENT device (used in place), 0 for host memory
  * (staged through the GPU) and LLZ_ERR_ARG, with a message, for device memory that lives on another device -- a handle

@@ -18,7 +18,7 @@
 //     product is bin-wise, so nothing is ever bit-reversed: the host stores H_p in the forward transform's output order.  The
 //     register transforms of fft32.hpp serve 1024 points per half-wave; composing them to 8192 costs the 8192-point rung its
 //     pairs of waves and fixed overlaps, and the transforms are not where this form spends its time (the product's scratch
-//     traffic is), so one LDS form serves all four sizes.
+//     traffic is), so one LDS form serves all four sizes.  The passes live in part_fft.hpp, shared with fir_stream.hip (K4f).
 //   * Three kernels, not fused: forward (samples -> Z in scratch), product (Z, H -> Y in scratch), inverse (Y -> samples).  A
 //     fused product + inverse would have to hold a run of N-point accumulators per workgroup (64 KB each at 8192 points: a
 //     run of 2), and without a run every output block reads P spectra.  The product kernel's thread owns ONE bin of a run of
@@ -34,6 +34,7 @@
 //     longer one table in L2); reading Z with nontemporal loads to spare H's cache lines was 6 .. 17 % behind and dropped
 //     (DESIGN.md K4e).
 #include "common.hpp"
+#include "part_fft.hpp"
 
 namespace {
 
@@ -46,85 +47,6 @@ struct part_geom {
     int Kh, S;                  // complex output blocks per channel, complex spectra per channel = Kh + P - 1
     long in_pitch, out_pitch;
 };
-
-__device__ __forceinline__ float2 c_add(float2 a, float2 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ float2 c_sub(float2 a, float2 b) { return {a.x - b.x, a.y - b.y}; }
-// a * w (INV = false) or a * conj(w)
-template <bool INV>
-__device__ __forceinline__ float2 c_mul(float2 a, float2 w)
-{
-    if (INV) return {__builtin_fmaf(a.y, w.y, a.x * w.x), __builtin_fmaf(-a.x, w.y, a.y * w.x)};
-    return {__builtin_fmaf(-a.y, w.y, a.x * w.x), __builtin_fmaf(a.x, w.y, a.y * w.x)};
-}
-
-// forward: N-point decimation in frequency in LDS, natural order in, l[i] = X[bitrev(i)] out.  tw[m] = W_N^m, m < N / 2.
-template <int LOG2N>
-__device__ __forceinline__ void part_fft_dif(float2 *l, const float2 *__restrict__ tw, int tid)
-{
-    constexpr int N = 1 << LOG2N;
-    int S = N;
-    for (; S >= 4; S >>= 2) {                   // spans S and S / 2 in one round trip
-        const int Q = S >> 2, tstep = N / S;
-        __syncthreads();
-        for (int b = tid; b < N / 4; b += PART_THREADS) {
-            const int j = b & (Q - 1);
-            const int base = (b - j) * 4 + j;
-            const float2 x0 = l[base], x1 = l[base + Q], x2 = l[base + 2 * Q], x3 = l[base + 3 * Q];
-            const float2 w1 = tw[2 * j * tstep];
-            const float2 a0 = c_add(x0, x2), a1 = c_add(x1, x3);
-            const float2 a2 = c_mul<false>(c_sub(x0, x2), tw[j * tstep]);
-            const float2 a3 = c_mul<false>(c_sub(x1, x3), tw[(j + Q) * tstep]);
-            l[base] = c_add(a0, a1);
-            l[base + Q] = c_mul<false>(c_sub(a0, a1), w1);
-            l[base + 2 * Q] = c_add(a2, a3);
-            l[base + 3 * Q] = c_mul<false>(c_sub(a2, a3), w1);
-        }
-    }
-    if (S == 2) {                               // odd log2 N: the last span alone, twiddle 1
-        __syncthreads();
-        for (int b = tid; b < N / 2; b += PART_THREADS) {
-            const float2 a = l[2 * b], c = l[2 * b + 1];
-            l[2 * b] = c_add(a, c);
-            l[2 * b + 1] = c_sub(a, c);
-        }
-    }
-    __syncthreads();
-}
-
-// inverse (unscaled): decimation in time, l[i] = Y[bitrev(i)] in, natural order out: the forward's stages backwards
-template <int LOG2N>
-__device__ __forceinline__ void part_fft_dit_inv(float2 *l, const float2 *__restrict__ tw, int tid)
-{
-    constexpr int N = 1 << LOG2N;
-    int S = 4;
-    if (LOG2N & 1) {
-        __syncthreads();
-        for (int b = tid; b < N / 2; b += PART_THREADS) {
-            const float2 a = l[2 * b], c = l[2 * b + 1];
-            l[2 * b] = c_add(a, c);
-            l[2 * b + 1] = c_sub(a, c);
-        }
-        S = 8;
-    }
-    for (; S <= N; S <<= 2) {                   // spans S / 2 and S in one round trip
-        const int Q = S >> 2, tstep = N / S;
-        __syncthreads();
-        for (int b = tid; b < N / 4; b += PART_THREADS) {
-            const int j = b & (Q - 1);
-            const int base = (b - j) * 4 + j;
-            const float2 x0 = l[base], x1 = l[base + Q], x2 = l[base + 2 * Q], x3 = l[base + 3 * Q];
-            const float2 w1 = tw[2 * j * tstep];
-            const float2 t1 = c_mul<true>(x1, w1), t3 = c_mul<true>(x3, w1);
-            const float2 a0 = c_add(x0, t1), a1 = c_sub(x0, t1), a2 = c_add(x2, t3), a3 = c_sub(x2, t3);
-            const float2 u2 = c_mul<true>(a2, tw[j * tstep]), u3 = c_mul<true>(a3, tw[(j + Q) * tstep]);
-            l[base] = c_add(a0, u2);
-            l[base + 2 * Q] = c_sub(a0, u2);
-            l[base + Q] = c_add(a1, u3);
-            l[base + 3 * Q] = c_sub(a1, u3);
-        }
-    }
-    __syncthreads();
-}
 
 // sample t of concat(zeros, history, frame, zeros) of one channel; t = 0 is the frame's first sample
 __device__ __forceinline__ float part_sample(const float *__restrict__ row, const float *__restrict__ hrow, long t, int n, int keep)
@@ -151,7 +73,7 @@ k_fir_part_fwd(const float *__restrict__ in, const float *__restrict__ hist, con
     const long t0 = (q - 1) * G.B, t1 = t0 + (long)G.Kh * G.B;
     for (int i = tid; i < N; i += PART_THREADS)
         part_lds[i] = float2{part_sample(row, hrow, t0 + i, G.n, keep), part_sample(row, hrow, t1 + i, G.n, keep)};
-    part_fft_dif<LOG2N>(part_lds, tw, tid);
+    part_fft_dif<LOG2N, PART_THREADS>(part_lds, tw, tid);
     float2 *dst = Z + ((size_t)c * (size_t)G.S + (size_t)s) * N;
     for (int i = tid; i < N; i += PART_THREADS) dst[i] = part_lds[i];
 }
@@ -210,7 +132,7 @@ k_fir_part_inv(const float2 *__restrict__ Y, const float2 *__restrict__ tw, floa
     const long q = blockIdx.x;
     const float2 *src = Y + ((size_t)c * (size_t)G.Kh + (size_t)q) * N;
     for (int i = tid; i < N; i += PART_THREADS) part_lds[i] = src[i];
-    part_fft_dit_inv<LOG2N>(part_lds, tw, tid);
+    part_fft_dit_inv<LOG2N, PART_THREADS>(part_lds, tw, tid);
     float *orow = out + (size_t)c * (size_t)G.out_pitch;
     const long ta = q * B, tb = (q + G.Kh) * B;
     for (int i = tid; i < B; i += PART_THREADS) {

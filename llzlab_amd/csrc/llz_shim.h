@@ -156,6 +156,18 @@ int llzs_fir_part_f32(int nfft, const float *hpart, const float *tw, float *scra
 int llzs_fir_part_bank_f32(int nfft, const float *hbank, const float *tw, float *scratch, size_t scratch_bytes, const float *in,
                            float *out, const float *hist, int channels, int n, long in_pitch, long out_pitch, int flt_len,
                            void *stream);
+/* the block convolver with a frequency-domain delay line (fir_stream.hip), block = 64 .. 4096 (a power of two), N = 2 block,
+ * P = ceil(flt_len / block) partitions.  hspec = [P][block] complex floats (bank != 0: [channels][P][block]) as
+ * llz_host_stream_spectra builds them: the packed half-spectra of the partitions over 2 N, in the order of a decimation-in-
+ * frequency transform's output; tw = [block / 2] complex W_block^m, then [block] complex W_N^bitrev(i); ring =
+ * [channels][R][block] complex, the spectra of the last input blocks, R >= P; prev = [channels][block], the last input block.
+ * flush == 0: the nblk blocks of in ([channels][in_pitch], in_pitch >= nblk block) in order, block j's spectrum into ring slot
+ * (head + j) mod R, prev updated; the caller advances head by nblk.  flush != 0: nblk <= P zero blocks behind the input so far;
+ * in is not read, ring and prev are not written.  Either way the first n_out <= nblk block samples of every channel are stored
+ * to out ([channels][out_pitch]). */
+int llzs_fir_stream_f32(int block, const float *hspec, int bank, const float *tw, float *ring, float *prev, const float *in,
+                        float *out, int channels, int nblk, int flush, long n_out, long in_pitch, long out_pitch, int P, int R,
+                        int head, void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

@@ -234,6 +234,71 @@ class FirBankMC:
     __del__ = close
 
 
+class FirStreamMC:
+    """channels x frame_len float32, planar, frame_len = k x block: llz_fir_stream_mc_*, the block convolver that keeps the
+    spectra of its input between calls (short blocks against long filters).  taps: 1-D (one tap set for all channels) or
+    [channels, flt_len] (a tap set per channel).  frame_len defaults to block."""
+
+    def __init__(self, channels, block, taps, frame_len=None, stream=None):
+        self._L = capi.lib()
+        taps = _f64(taps)
+        if taps.ndim not in (1, 2) or taps.shape[-1] < 1 or (taps.ndim == 2 and taps.shape[0] != channels):
+            raise LlzError(f"FirStreamMC: taps must be [flt_len] or [channels = {channels}, flt_len], got {taps.shape}")
+        frame_len = block if frame_len is None else frame_len
+        self.rows = 1 if taps.ndim == 1 else channels
+        self.handle = check_handle(
+            self._L.llz_fir_stream_mc_init_f64taps(channels, block, frame_len, taps.ctypes.data, self.rows, taps.shape[-1]),
+            "llz_fir_stream_mc_init")
+        self.channels, self.block, self.frame_len, self.flt_len = channels, block, frame_len, taps.shape[-1]
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_fir_stream_mc_set_stream(self.handle, _stream_ptr(stream)), "set_stream")
+
+    def plan(self):
+        """(N = 2 block, partitions P, ring slots R, blocks per call k)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_fir_stream_mc_plan(self.handle, out), "llz_fir_stream_mc_plan")
+        return tuple(out)
+
+    def set_taps(self, first, taps):
+        """replace tap rows first .. first + count - 1; taps: [count, flt_len], or [flt_len] for one row"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps = taps[None, :] if taps.ndim == 1 else taps
+        if taps.ndim != 2 or taps.shape[1] != self.flt_len:
+            raise LlzError(f"FirStreamMC.set_taps: taps must be [count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_fir_stream_mc_set_taps(self.handle, first, taps.shape[0], taps.ctypes.data),
+              "llz_fir_stream_mc_set_taps")
+
+    def filter(self, x, out):
+        """x, out: [channels, frame_len] float32 (torch device tensors or numpy). Returns out."""
+        count = self.channels * self.frame_len
+        check(self._L.llz_fir_stream_mc(self.handle, _typed(x, "float32", count, "FirStreamMC.filter x"),
+                                        _typed(out, "float32", count, "FirStreamMC.filter out"), self.frame_len),
+              "llz_fir_stream_mc")
+        return out
+
+    def flush(self, out):
+        """out: [channels, flt_len - 1]; the handle starts over afterwards.  With one tap there is nothing to emit: out is an
+        empty buffer or None, and the call only resets the handle"""
+        ptr = None
+        if self.flt_len > 1 or out is not None:
+            ptr = _typed(out, "float32", self.channels * (self.flt_len - 1), "FirStreamMC.flush out")
+        check(self._L.llz_fir_stream_mc_flush(self.handle, ptr), "llz_fir_stream_mc_flush")
+        return out
+
+    def reset(self):
+        check(self._L.llz_fir_stream_mc_reset(self.handle), "llz_fir_stream_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_fir_stream_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
