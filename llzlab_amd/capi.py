@@ -243,6 +243,12 @@ def lib():
     sig("llz_lpc_uninit", None, ul)
     sig("llz_lpc", d, ul, dp, i, dp, dp, dp)
     sig("llz_lpc_mc", i, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp)
+    sig("llz_lpc_filter_mc_init", ul, i, i, i)
+    sig("llz_lpc_filter_mc_uninit", None, ul)
+    sig("llz_lpc_filter_mc_set_stream", i, ul, vp)
+    sig("llz_lpc_filter_mc_reset", i, ul)
+    sig("llz_lpc_residual_mc", i, ul, vp, vp, vp, i)
+    sig("llz_lpc_synth_mc", i, ul, vp, vp, vp, i)
     # llz_asmodel.h
     for n in ("llz_analysis_fft_init", "llz_synthesis_fft_init"):
         sig(n, ul, i, i, i)

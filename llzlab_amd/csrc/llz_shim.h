@@ -340,6 +340,18 @@ int llzs_levinson_f32(const float *r, float *acof, float *kcof, float *err, floa
 /* y[f][i] = x[f][i] * win[i] (float32, one rounding) */
 int llzs_window_f32(const float *x, const float *win, float *y, int frames, int n, void *stream);
 
+/* ---- the filters that apply LPC coefficients (lpc_filter.hip; include/llz_lpc.h part 3) ----
+ * x, e, y planar [channels][frames * frame_len]; acof [channels][frames][p + 1], entry 0 of a set is not read; 0 <= p <= 64,
+ * p < frame_len.  Rows and coefficient sets need their element's alignment only.
+ * residual: e[t] = x[t] + sum_k a_f[k] x[t - k] as a float32 fma chain over k = p .. 1.  hist_in / hist_out: [channels][64]
+ * floats, [c][i] = x(-1 - i) in front of / behind the call (i < p), two different buffers */
+int llzs_lpc_residual_f32(const float *x, const float *acof, float *e, const float *hist_in, float *hist_out, int channels,
+                          int frames, int frame_len, int p, void *stream);
+/* synthesis: y[t] = e[t] - sum_k a_f[k] y[t - k] in double over k = p .. 1, rounded multiply then rounded subtract, stored as
+ * float32.  state: [channels][64] doubles, [c][i] = the unrounded y(-1 - i) (i < p), updated in place */
+int llzs_lpc_synth_f32(const float *e, const float *acof, float *y, double *state, int channels, int frames, int frame_len,
+                       int p, void *stream);
+
 /* windowed-FFT frames (llz_asmodel.c:180-310), float32 batch, fft_len 8..4096 in one launch per direction: x planar
  * [C][frames*F] (row pitch x_pitch), spectra [C][frames][size/2+1]; hist / ola: [C][size-F] state carried between calls
  * (ola_old != ola_new); w: size floats; cs: cos then sin of 2*pi*i/size */

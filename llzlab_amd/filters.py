@@ -835,6 +835,50 @@ def lpc_mc(x, acof, kcof=None, err=None, gain=None, r=None, win=None, p=None, st
     return acof
 
 
+class LpcFilterMC:
+    """llz_lpc_filter_mc_*: the filters that apply lpc_mc's coefficients, a set per (channel, frame).  x, e, y:
+    [channels, frames * frame_len] float32, planar; acof: [channels, frames, p + 1] float32 (lpc_mc's output on
+    x.view(channels * frames, frame_len)).  residual and synth keep their own state in the handle, so consecutive calls
+    continue the streams.  Device tensors or numpy arrays."""
+
+    def __init__(self, channels, frame_len, p, stream=None):
+        self._L = capi.lib()
+        self.handle = check_handle(self._L.llz_lpc_filter_mc_init(channels, frame_len, p), "llz_lpc_filter_mc_init")
+        self.channels, self.frame_len, self.p = channels, frame_len, p
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_lpc_filter_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_lpc_filter_mc_set_stream")
+
+    def _run(self, fn, src, acof, dst, frames):
+        if frames is None:
+            frames = (src.numel() if hasattr(src, "numel") else src.size) // (self.channels * self.frame_len)
+        count = self.channels * frames * self.frame_len
+        check(getattr(self._L, fn)(self.handle, _typed(src, "float32", count, fn + " input"),
+                                   _typed(acof, "float32", self.channels * frames * (self.p + 1), fn + " acof"),
+                                   _typed(dst, "float32", count, fn + " output"), frames), fn)
+        return dst
+
+    def residual(self, x, acof, e, frames=None):
+        """e[t] = x[t] + sum_k a_f[k] x[t-k] (float32 fma chain, k = p .. 1).  Returns e."""
+        return self._run("llz_lpc_residual_mc", x, acof, e, frames)
+
+    def synth(self, e, acof, y, frames=None):
+        """y[t] = e[t] - sum_k a_f[k] y[t-k] (double, k = p .. 1, rounded to float32 on store).  Returns y."""
+        return self._run("llz_lpc_synth_mc", e, acof, y, frames)
+
+    def reset(self):
+        check(self._L.llz_lpc_filter_mc_reset(self.handle), "llz_lpc_filter_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_lpc_filter_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ windowed-FFT frames
 class _FftFrames:
     """llz_analysis_fft_* / llz_synthesis_fft_* (llz_asmodel.h:36-42): one frame per call, host float64, exact."""
