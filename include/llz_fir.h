@@ -10,6 +10,7 @@
  * Part 3 is the same batch with a tap set per channel: the filter bank (time domain, and overlap-save up to 257 taps).
  * Part 4 is the bank for long filters: the partitioned overlap-save of part 2 with a tap set per channel, 1..131073 taps.
  * Part 5 is the block convolver for short calls against long filters: it keeps the spectra of its input between calls.
+ * Part 6 is that block convolver with a filter per (output, input) path: many inputs into many outputs, summed in the spectrum.
  */
 #ifndef LLZ_FIR_H
 #define LLZ_FIR_H
@@ -196,6 +197,60 @@ int llz_fir_stream_mc_plan(unsigned long handle, int out[4]);
 int llz_fir_stream_mc_flt_len(unsigned long handle);
 /* stream: a hipStream_t passed as void* (NULL = default stream) */
 int llz_fir_stream_mc_set_stream(unsigned long handle, void *stream);
+
+/* ---- Part 6: the matrix convolver -- many inputs into many outputs, y_o = sum_i x_i * h_{o,i} -------------------------- */
+
+/* N sources rendered to 2 ears (HRTF and BRIR sets), M microphones filtered and summed into B beams, crosstalk cancellers,
+ * wave-field synthesis, multi-way crossovers: part 5's block convolver with a filter per PATH (o, i) and a sum over inputs.
+ * block (a power of two, 64..4096), frame_len = k x block with k in 1..65535, P = ceil(flt_len / block), R = P + k - 1 as in
+ * part 5.  There is one delay line per INPUT -- inputs x R x block x 8 bytes of ring beside the last `block` samples of every
+ * input -- shared by all outputs; the sum over inputs and partitions happens in the spectrum, and one inverse transform runs
+ * per output block: inputs + outputs transforms per block where a part-5 bank of inputs x outputs channels on replicated inputs
+ * runs inputs x outputs forward and as many inverse ones, keeps as many rings, and leaves the sum to the caller.  A call is
+ * three launches ordered by the handle's stream: the forward transforms, the product -- the sum over inputs cut into G groups
+ * of neighbouring inputs, G fixed at init from (inputs, outputs, block) alone, each group's partial spectrum in a scratch --
+ * and the inverse transforms, which add the partials g ascending.  Within a group the inputs go ascending, p ascending within
+ * an input, one fma chain per bin: how calls group the blocks of a stream does not change a bit of the result, a fresh handle
+ * repeats its bits, and with all inputs but one at zero an output is part 5's for that path, value for value.
+ * A path whose flt_len taps are ALL ZERO is not connected: the product skips it -- it costs no memory traffic and passes
+ * nothing on, not even a NaN or an Inf of its input -- so a routing matrix that is mostly zeros costs what its connected paths
+ * cost.  (Its spectra stay allocated.)
+ * Which form when: this one wherever an output sums several inputs or several outputs share an input: by count it reads half
+ * the bytes of the part-5 emulation and runs inputs + outputs transforms for its inputs x outputs (the timing
+ * table against that emulation is not measured yet, so no shape is known at which the emulation wins).  For inputs == outputs
+ * with a diagonal matrix part 5's bank is the direct form: one launch per call and no scratch.
+ * inputs, outputs 1..4096, flt_len 1..131073.  taps: HOST pointer, [outputs][inputs][flt_len] (the double variant rounds to
+ * float once).  Device memory: outputs x inputs x P x block x 8 bytes of tap spectra, the rings, and G x outputs x max(k, blocks
+ * of a flush pass) x block x 8 bytes of partial spectra (a flush's passes are cut so that these stay within 64 MiB); when an
+ * allocation fails the message states the bytes asked for.  Every refusal leaves a message of its own.  Returns
+ * (unsigned long)-1 on failure (llz_hip_last_error() says why). */
+unsigned long llz_fir_matrix_mc_init(int inputs, int outputs, int block, int frame_len, const float *taps, int flt_len);
+unsigned long llz_fir_matrix_mc_init_f64taps(int inputs, int outputs, int block, int frame_len, const double *taps, int flt_len);
+void          llz_fir_matrix_mc_uninit(unsigned long handle);
+/* in: planar [inputs][frame_len], out: planar [outputs][frame_len], float32, device memory (used in place, asynchronous on the
+ * handle's stream) or host memory (staged, synchronous); frame_len as at init; out may not alias or overlap in (LLZ_ERR_ARG).
+ * Returns frame_len, or a negative LLZ_ERR_* code.  The rings' head is kept on the host and passed by value with each launch,
+ * and the two buffers of the last input block are swapped there, so a call CAPTURED INTO A GRAPH would replay one and the same
+ * ring slot: graph capture is not supported. */
+int llz_fir_matrix_mc(unsigned long handle, const float *in, float *out, int frame_len);
+/* out: planar [outputs][flt_len-1], the response to ceil((flt_len-1) / block) zero blocks, run side by side; returns flt_len-1
+ * and leaves the handle as llz_fir_matrix_mc_reset does: reused, it gives the bits of a fresh handle.  With one tap nothing is
+ * written, out may be NULL, and the call returns 0 after the same reset */
+int llz_fir_matrix_mc_flush(unsigned long handle, float *out);
+/* the delay lines (rings and last blocks) to zeros, ordered on the handle's stream; the taps stay */
+int llz_fir_matrix_mc_reset(unsigned long handle);
+/* replace the sub-matrix of paths [out_first, out_first+out_count) x [in_first, in_first+in_count) between calls; taps: HOST
+ * [out_count][in_count][flt_len].  A range outside the matrix is refused.  Ordered on the handle's stream behind the calls
+ * already issued, the connection table too: a path is connected from then on exactly when its new taps are not all zero.  The
+ * delay lines are kept, and they hold INPUT spectra: from the next call on the output is the new taps applied to the whole
+ * input so far (no crossfade). */
+int llz_fir_matrix_mc_set_taps(unsigned long handle, int out_first, int out_count, int in_first, int in_count, const float *taps);
+/* out = {N = 2 block, P = ceil(flt_len / block), ring slots R, blocks per call k, input groups G, connected paths}; nothing is
+ * launched */
+int llz_fir_matrix_mc_plan(unsigned long handle, int out[6]);
+int llz_fir_matrix_mc_flt_len(unsigned long handle);
+/* stream: a hipStream_t passed as void* (NULL = default stream) */
+int llz_fir_matrix_mc_set_stream(unsigned long handle, void *stream);
 
 #ifdef __cplusplus
 }

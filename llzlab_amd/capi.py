@@ -163,6 +163,16 @@ def lib():
     sig("llz_fir_stream_mc_plan", i, ul, C.POINTER(C.c_int))
     sig("llz_fir_stream_mc_flt_len", i, ul)
     sig("llz_fir_stream_mc_set_stream", i, ul, vp)
+    sig("llz_fir_matrix_mc_init", ul, i, i, i, i, vp, i)
+    sig("llz_fir_matrix_mc_init_f64taps", ul, i, i, i, i, vp, i)
+    sig("llz_fir_matrix_mc_uninit", None, ul)
+    sig("llz_fir_matrix_mc", i, ul, vp, vp, i)
+    sig("llz_fir_matrix_mc_flush", i, ul, vp)
+    sig("llz_fir_matrix_mc_reset", i, ul)
+    sig("llz_fir_matrix_mc_set_taps", i, ul, i, i, i, i, vp)
+    sig("llz_fir_matrix_mc_plan", i, ul, C.POINTER(C.c_int))
+    sig("llz_fir_matrix_mc_flt_len", i, ul)
+    sig("llz_fir_matrix_mc_set_stream", i, ul, vp)
     # llz_iir.h
     sig("llz_iir_filter_init", ul, i, dp, i, dp)
     sig("llz_iir_filter_uninit", None, ul)

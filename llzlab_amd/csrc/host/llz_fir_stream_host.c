@@ -34,7 +34,7 @@ static void firs_destroy(firs_t *f)
 }
 
 /* cos then sin of 2 pi i / N, i < N, with exact quadrant values */
-static void firs_cs_table(double *cs, int N)
+void llz_host_stream_cs_table(double *cs, int N)
 {
     for (int i = 0; i < N; i++) {
         const double ang = 2.0 * M_PI * (double)i / (double)N;
@@ -101,7 +101,7 @@ static int firs_load_rows(firs_t *f, int first, int count, const float *taps, in
     double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
     double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
     int rc = (hp && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) firs_cs_table(cs, N);
+    if (rc == LLZ_OK) llz_host_stream_cs_table(cs, N);
     for (size_t r0 = 0; r0 < (size_t)count && rc == LLZ_OK; r0 += chunk) {
         const size_t rows = (size_t)count - r0 < chunk ? (size_t)count - r0 : chunk;
         for (size_t r = 0; r < rows; r++)
@@ -114,9 +114,9 @@ static int firs_load_rows(firs_t *f, int first, int count, const float *taps, in
 }
 
 /* the transform's twiddles W_block^m, m < block / 2, then the split twiddles by position: W_N^bitrev(i), i < block */
-static int firs_load_twiddles(firs_t *f)
+int llz_host_stream_twiddles(float *d_tw, int block)
 {
-    const int B = f->block, N = 2 * B;
+    const int B = block, N = 2 * B;
     int bits = 0;
     while ((1 << bits) < B) bits++;
     const size_t count = (size_t)B / 2 + (size_t)B;
@@ -124,7 +124,7 @@ static int firs_load_twiddles(firs_t *f)
     double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
     int rc = (tw && cs) ? LLZ_OK : LLZ_ERR_NOMEM;
     if (rc == LLZ_OK) {
-        firs_cs_table(cs, N);
+        llz_host_stream_cs_table(cs, N);
         for (int m = 0; m < B / 2; m++) {
             tw[2 * m] = (float)cs[2 * (2 * m)];
             tw[2 * m + 1] = (float)(-cs[2 * (2 * m) + 1]);
@@ -134,7 +134,7 @@ static int firs_load_twiddles(firs_t *f)
             tw[2 * (B / 2 + i)] = (float)cs[2 * k];
             tw[2 * (B / 2 + i) + 1] = (float)(-cs[2 * k + 1]);
         }
-        rc = llzs_h2d_table(f->d_tw, tw, sizeof(float) * 2 * count);
+        rc = llzs_h2d_table(d_tw, tw, sizeof(float) * 2 * count);
     }
     free(tw); free(cs);
     return rc;
@@ -216,7 +216,7 @@ unsigned long llz_fir_stream_mc_init(int channels, int block, int frame_len, con
     }
     /* tables through llzs_h2d_table, in a fixed order */
     if (rc == LLZ_OK) rc = firs_load_rows(f, 0, rows, taps, 1);
-    if (rc == LLZ_OK) rc = firs_load_twiddles(f);
+    if (rc == LLZ_OK) rc = llz_host_stream_twiddles(f->d_tw, f->block);
     if (rc == LLZ_OK) rc = firs_clear(f);
     if (rc == LLZ_OK) rc = llzs_sync(NULL);
     if (rc != LLZ_OK) {

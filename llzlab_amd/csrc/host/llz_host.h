@@ -17,7 +17,8 @@ int llz_host_design(int kind, double **out, int n, double fc1, double fc2, win_t
 enum {
     LLZ_TAG_FIR1 = 0x4c5a4631, LLZ_TAG_FIRM = 0x4c5a464d, LLZ_TAG_IIR1 = 0x4c5a4931, LLZ_TAG_IIRM = 0x4c5a494d,
     LLZ_TAG_RS1 = 0x4c5a5231, LLZ_TAG_RSM = 0x4c5a524d, LLZ_TAG_FFT1 = 0x4c5a5431, LLZ_TAG_FFTB = 0x4c5a5442,
-    LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942, LLZ_TAG_FIRS = 0x4c5a4653
+    LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942, LLZ_TAG_FIRS = 0x4c5a4653,
+    LLZ_TAG_FIRX = 0x4c5a4658
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))
@@ -39,6 +40,10 @@ void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, co
  * packs the two real bins: (DC, Nyquist).  cs: 2 N doubles, cos then sin of 2 pi i / N with exact quadrant values; z: 2 N
  * doubles of work space */
 void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int block, const double *cs, double *z);
+/* the cs table it takes, and the device table of both delay-line forms (llz_fir_stream_mc, llz_fir_matrix_mc) uploaded through
+ * llzs_h2d_table: [block / 2] complex W_block^m, then [block] complex W_N^bitrev(i); d_tw: 2 (block / 2 + block) floats */
+void llz_host_stream_cs_table(double *cs, int N);
+int  llz_host_stream_twiddles(float *d_tw, int block);
 
 /* Caller buffers: llzs_is_device_ptr(p) is 1 for device memory of the CURRENT device (used in place), 0 for host memory
  * (staged through the GPU) and LLZ_ERR_ARG, with a message, for device memory that lives on another device -- a handle

@@ -34,6 +34,7 @@
 //   * All index arithmetic over channels x slots x bins is size_t / long.
 #include "common.hpp"
 #include "part_fft.hpp"
+#include "stream_bins.hpp"
 
 namespace {
 
@@ -44,46 +45,6 @@ struct stream_geom {
     long n_out;                 // samples per channel to store: <= nblk B
     long in_pitch, out_pitch;
 };
-
-constexpr int stream_threads(int log2b) { return (1 << log2b) < 256 ? (1 << log2b) : 256; }
-
-__device__ __forceinline__ float2 c_conj(float2 a) { return {a.x, -a.y}; }
-
-// acc += x h; PACKED0: bin 0 holds DC and Nyquist, two real values: each half by its own
-__device__ __forceinline__ void bin_mac(float2 &acc, float2 x, float2 h, bool packed0)
-{
-    const float xr = packed0 ? 0.f : x.x, xi = packed0 ? 0.f : x.y, hh = packed0 ? h.y : h.x;
-    acc.x = __builtin_fmaf(-xi, h.y, __builtin_fmaf(x.x, h.x, acc.x));
-    acc.y = __builtin_fmaf(x.y, hh, __builtin_fmaf(xr, h.y, acc.y));
-}
-
-// position of bin B - k for the position i > 0 of bin k = bitrev(i) (position 0, the packed bin, has no mirror: itself)
-template <int LOG2B>
-__device__ __forceinline__ int mirror(int i)
-{
-    const unsigned k = __brev((unsigned)i) >> (32 - LOG2B);
-    return i ? (int)(__brev((1u << LOG2B) - k) >> (32 - LOG2B)) : 0;
-}
-
-// V neighbouring bins in one load (V = 2: 16 bytes; every row of ring and H starts on a multiple of 512 bytes)
-template <int V>
-__device__ __forceinline__ void load_bins(const float2 *p, float2 *dst)
-{
-    if (V == 2) {
-        const float4 q = *reinterpret_cast<const float4 *>(p);
-        dst[0] = float2{q.x, q.y};
-        dst[1] = float2{q.z, q.w};
-    } else {
-        dst[0] = *p;
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void store_bins(float2 *p, const float2 *src)
-{
-    if (V == 2) *reinterpret_cast<float4 *>(p) = float4{src[0].x, src[0].y, src[1].x, src[1].y};
-    else *p = src[0];
-}
 
 // K4f: workgroup c (a flush: (c, block)) -> channel c.  tw: [B / 2] W_B^m, then [B] split twiddles W_N^bitrev(i) by position.
 // BANK: H is [channels][P][B], channel c's own spectra

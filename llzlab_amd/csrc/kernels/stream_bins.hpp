@@ -1,0 +1,73 @@
+// stream_bins.hpp -- what the two frequency-domain delay lines share: fir_stream.hip (K4f) and fir_matrix.hip (K4g).  The packed
+// half-spectrum of a real block pair (B bins by position, position i holds bin bitrev(i), position 0 packs DC and Nyquist), its
+// product step, the loads and stores of neighbouring bins, and the two split steps between the B-point complex transform
+// (part_fft.hpp) and that half-spectrum.  The product step, mirror and the loads and stores are used by both files;
+// k_fir_stream keeps its own in-line copy of the two split steps (as functions they changed its register assignment), which
+// split_fwd / split_inv below restate operation for operation, so that one path of the matrix form gives the stream
+// convolver's values.
+#pragma once
+#include "common.hpp"
+#include "part_fft.hpp"
+
+namespace {
+
+constexpr int stream_threads(int log2b) { return (1 << log2b) < 256 ? (1 << log2b) : 256; }
+
+__device__ __forceinline__ float2 c_conj(float2 a) { return {a.x, -a.y}; }
+
+// acc += x h; PACKED0: bin 0 holds DC and Nyquist, two real values: each half by its own
+__device__ __forceinline__ void bin_mac(float2 &acc, float2 x, float2 h, bool packed0)
+{
+    const float xr = packed0 ? 0.f : x.x, xi = packed0 ? 0.f : x.y, hh = packed0 ? h.y : h.x;
+    acc.x = __builtin_fmaf(-xi, h.y, __builtin_fmaf(x.x, h.x, acc.x));
+    acc.y = __builtin_fmaf(x.y, hh, __builtin_fmaf(xr, h.y, acc.y));
+}
+
+// position of bin B - k for the position i > 0 of bin k = bitrev(i) (position 0, the packed bin, has no mirror: itself)
+template <int LOG2B>
+__device__ __forceinline__ int mirror(int i)
+{
+    const unsigned k = __brev((unsigned)i) >> (32 - LOG2B);
+    return i ? (int)(__brev((1u << LOG2B) - k) >> (32 - LOG2B)) : 0;
+}
+
+// V neighbouring bins in one load (V = 2: 16 bytes; every row of ring and H starts on a multiple of 512 bytes)
+template <int V>
+__device__ __forceinline__ void load_bins(const float2 *p, float2 *dst)
+{
+    if (V == 2) {
+        const float4 q = *reinterpret_cast<const float4 *>(p);
+        dst[0] = float2{q.x, q.y};
+        dst[1] = float2{q.z, q.w};
+    } else {
+        dst[0] = *p;
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void store_bins(float2 *p, const float2 *src)
+{
+    if (V == 2) *reinterpret_cast<float4 *>(p) = float4{src[0].x, src[0].y, src[1].x, src[1].y};
+    else *p = src[0];
+}
+
+// forward split: bin k of the real transform (doubled) = (Z_k + conj Z_{B-k}) + W_N^k (-j) (Z_k - conj Z_{B-k}); a = Z_k, zm =
+// Z_{B-k}, w = W_N^k.  The packed bin: (DC, Nyquist) from Z_0 alone
+__device__ __forceinline__ float2 split_fwd(float2 a, float2 zm, float2 w)
+{
+    const float2 b = c_conj(zm);
+    const float2 e = c_add(a, b), d = c_sub(a, b);
+    return c_add(e, c_mul<false>(float2{d.y, -d.x}, w));
+}
+__device__ __forceinline__ float2 split_fwd0(float2 a) { return float2{2.f * (a.x + a.y), 2.f * (a.x - a.y)}; }
+
+// inverse split: Z''_k = (Y_k + conj Y_{B-k}) + j conj(W_N^k) (Y_k - conj Y_{B-k}); a = Y_k, ym = Y_{B-k}
+__device__ __forceinline__ float2 split_inv(float2 a, float2 ym, float2 w)
+{
+    const float2 b = c_conj(ym);
+    const float2 e = c_add(a, b), d = c_sub(a, b);
+    return c_add(e, c_mul<true>(float2{-d.y, d.x}, w));
+}
+__device__ __forceinline__ float2 split_inv0(float2 a) { return float2{a.x + a.y, a.x - a.y}; }
+
+} // namespace

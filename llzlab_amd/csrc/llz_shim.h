@@ -168,6 +168,26 @@ int llzs_fir_part_bank_f32(int nfft, const float *hbank, const float *tw, float 
 int llzs_fir_stream_f32(int block, const float *hspec, int bank, const float *tw, float *ring, float *prev, const float *in,
                         float *out, int channels, int nblk, int flush, long n_out, long in_pitch, long out_pitch, int P, int R,
                         int head, void *stream);
+/* the many-in, many-out stream convolver (fir_matrix.hip): llzs_fir_stream_f32's block, tw and packed spectra, with a delay line
+ * per INPUT and a sum over inputs, as three launches ordered by the stream.  ring = [inputs][R][block] complex; prev_in /
+ * prev_out = [inputs][block], two different buffers (the caller swaps them after a call); hspec = [outputs][inputs][P][block]
+ * complex, a row as llz_host_stream_spectra builds it; conn = [outputs][inputs] bytes, 0 = the path (o, i) is skipped; ypart =
+ * [groups][outputs][nblk][block] complex scratch, group g the inputs [g group_size, (g + 1) group_size) (the last group may be
+ * short).  inputs, outputs 1..4096, nblk 1..65535.
+ * fwd: the spectra of the nblk blocks of in ([inputs][in_pitch]) into ring slots (head + j) mod R, block nblk - 1 into prev_out;
+ *      flush != 0: nblk == 1, the spectrum of (prev_in, zeros) into slot head, in and prev_out untouched.
+ * mac: ypart[g][o][j] = the sum over group g's connected inputs (ascending) and p (ascending) of ring_i[(head + j - p) mod R]
+ *      H[o][i][p]; flush != 0: the launch's block j is block j0 + j of the flush and starts at p = j0 + j, j0 + nblk <= P
+ *      (a long flush goes in passes of as many blocks as ypart holds); flush == 0: j0 == 0.
+ * inv: the partials added g ascending, the inverse transform, the first n_out <= nblk block samples of every output stored to
+ *      out ([outputs][out_pitch]). */
+int llzs_fir_matrix_fwd_f32(int block, const float *tw, float *ring, const float *prev_in, float *prev_out, const float *in,
+                            int inputs, int nblk, int flush, long in_pitch, int R, int head, void *stream);
+int llzs_fir_matrix_mac_f32(int block, const float *hspec, const float *ring, const unsigned char *conn, float *ypart, int inputs,
+                            int outputs, int nblk, int flush, int j0, int P, int R, int head, int groups, int group_size,
+                            void *stream);
+int llzs_fir_matrix_inv_f32(int block, const float *ypart, const float *tw, float *out, int outputs, int nblk, int groups,
+                            long n_out, long out_pitch, void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

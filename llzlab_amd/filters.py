@@ -299,6 +299,70 @@ class FirStreamMC:
     __del__ = close
 
 
+class FirMatrixMC:
+    """[inputs, frame_len] -> [outputs, frame_len] float32, planar, frame_len = k x block: llz_fir_matrix_mc_*, the stream
+    convolver with a filter per path, y_o = sum_i x_i * h[o, i].  taps: [outputs, inputs, flt_len]; a path whose taps are all
+    zero is not connected (it costs nothing and passes nothing on).  frame_len defaults to block."""
+
+    def __init__(self, inputs, outputs, block, taps, frame_len=None, stream=None):
+        self._L = capi.lib()
+        taps = _f64(taps)
+        if taps.ndim != 3 or taps.shape[:2] != (outputs, inputs) or taps.shape[2] < 1:
+            raise LlzError(f"FirMatrixMC: taps must be [outputs = {outputs}, inputs = {inputs}, flt_len], got {taps.shape}")
+        frame_len = block if frame_len is None else frame_len
+        self.handle = check_handle(
+            self._L.llz_fir_matrix_mc_init_f64taps(inputs, outputs, block, frame_len, taps.ctypes.data, taps.shape[2]),
+            "llz_fir_matrix_mc_init")
+        self.inputs, self.outputs, self.block, self.frame_len, self.flt_len = inputs, outputs, block, frame_len, taps.shape[2]
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_fir_matrix_mc_set_stream(self.handle, _stream_ptr(stream)), "set_stream")
+
+    def plan(self):
+        """(N = 2 block, partitions P, ring slots R, blocks per call k, input groups G, connected paths)"""
+        out = (C.c_int * 6)()
+        check(self._L.llz_fir_matrix_mc_plan(self.handle, out), "llz_fir_matrix_mc_plan")
+        return tuple(out)
+
+    def set_taps(self, out_first, in_first, taps):
+        """replace the paths [out_first, +out_count) x [in_first, +in_count); taps: [out_count, in_count, flt_len], or [flt_len]
+        for one path"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps = taps[None, None, :] if taps.ndim == 1 else taps
+        if taps.ndim != 3 or taps.shape[2] != self.flt_len:
+            raise LlzError(f"FirMatrixMC.set_taps: taps must be [out_count, in_count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_fir_matrix_mc_set_taps(self.handle, out_first, taps.shape[0], in_first, taps.shape[1], taps.ctypes.data),
+              "llz_fir_matrix_mc_set_taps")
+
+    def filter(self, x, out):
+        """x: [inputs, frame_len], out: [outputs, frame_len] float32 (torch device tensors or numpy). Returns out."""
+        check(self._L.llz_fir_matrix_mc(self.handle, _typed(x, "float32", self.inputs * self.frame_len, "FirMatrixMC.filter x"),
+                                        _typed(out, "float32", self.outputs * self.frame_len, "FirMatrixMC.filter out"),
+                                        self.frame_len), "llz_fir_matrix_mc")
+        return out
+
+    def flush(self, out):
+        """out: [outputs, flt_len - 1]; the handle starts over afterwards.  With one tap there is nothing to emit: out is an
+        empty buffer or None, and the call only resets the handle"""
+        ptr = None
+        if self.flt_len > 1 or out is not None:
+            ptr = _typed(out, "float32", self.outputs * (self.flt_len - 1), "FirMatrixMC.flush out")
+        check(self._L.llz_fir_matrix_mc_flush(self.handle, ptr), "llz_fir_matrix_mc_flush")
+        return out
+
+    def reset(self):
+        check(self._L.llz_fir_matrix_mc_reset(self.handle), "llz_fir_matrix_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_fir_matrix_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
