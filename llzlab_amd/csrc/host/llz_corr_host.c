@@ -293,18 +293,10 @@ int llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p)
     const size_t xb = sizeof(float) * (size_t)f->frames * f->n, rb = sizeof(float) * (size_t)f->frames * (p + 1);
     const int prev = llzs_device_enter(f->device);
     const int x_dev = llzs_is_device_ptr(x), r_dev = llzs_is_device_ptr(r);
-    const float *d_x = x;
-    float *d_r = r;
     int rc = (x_dev < 0 || r_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;     /* a buffer of another GPU: refused, message set */
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_autocorr_fast_mc", "x", x, xb, x_dev, "r", r, rb, r_dev);
-    if (rc == LLZ_OK && !x_dev) {
-        d_x = (const float *)llz_stage_reserve(&f->st_in, xb);
-        rc = d_x ? llzs_h2d((void *)d_x, x, xb, f->stream) : LLZ_ERR_NOMEM;
-    }
-    if (rc == LLZ_OK && !r_dev) {
-        d_r = (float *)llz_stage_reserve(&f->st_out, rb);
-        if (!d_r) rc = LLZ_ERR_NOMEM;
-    }
+    const float *d_x = llz_stage_in(&f->st_in, x, xb, x_dev, f->stream, &rc);
+    float *d_r = llz_stage_out(&f->st_out, r, rb, r_dev, &rc);
     /* pack -> FFT -> |X|^2 (first n bins) -> IFFT -> 2 Re, fused in LDS */
     if (rc == LLZ_OK) rc = llzs_acf_fused_f32(d_x, d_r, f->frames, f->n, p, f->fft_len, f->d_cs, f->stream);
     if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->stream);
@@ -405,26 +397,13 @@ int llz_crosscorr_fast_mc(unsigned long handle, const float *x, const float *y, 
     const size_t xb = sizeof(float) * (size_t)f->frames * f->n, rb = sizeof(float) * (size_t)f->frames * width;
     const int prev = llzs_device_enter(f->device);
     const int x_dev = llzs_is_device_ptr(x), y_dev = llzs_is_device_ptr(y), r_dev = llzs_is_device_ptr(r);
-    const float *d_x = x, *d_y = y;
-    float *d_r = r;
     int rc = (x_dev < 0 || y_dev < 0 || r_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;   /* a buffer of another GPU: refused, message set */
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_crosscorr_fast_mc", "x", x, xb, x_dev, "r", r, rb, r_dev);
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_crosscorr_fast_mc", "y", y, xb, y_dev, "r", r, rb, r_dev);
-    if (rc == LLZ_OK && !x_dev) {
-        d_x = (const float *)llz_stage_reserve(&f->st_x, xb);
-        rc = d_x ? llzs_h2d((void *)d_x, x, xb, f->stream) : LLZ_ERR_NOMEM;
-    }
-    if (rc == LLZ_OK && !y_dev) {
-        if (y == x) d_y = d_x;
-        else {
-            d_y = (const float *)llz_stage_reserve(&f->st_y, xb);
-            rc = d_y ? llzs_h2d((void *)d_y, y, xb, f->stream) : LLZ_ERR_NOMEM;
-        }
-    }
-    if (rc == LLZ_OK && !r_dev) {
-        d_r = (float *)llz_stage_reserve(&f->st_out, rb);
-        if (!d_r) rc = LLZ_ERR_NOMEM;
-    }
+    const float *d_x = llz_stage_in(&f->st_x, x, xb, x_dev, f->stream, &rc);
+    /* an autocorrelation from host memory (y == x) is staged once */
+    const float *d_y = y == x ? d_x : llz_stage_in(&f->st_y, y, xb, y_dev, f->stream, &rc);
+    float *d_r = llz_stage_out(&f->st_out, r, rb, r_dev, &rc);
     /* per slab of frames: pack -> FFT -> conj(X) Y -> IFFT -> lags; the launches of a slab follow the previous slab's on the stream */
     for (int f0 = 0; rc == LLZ_OK && f0 < f->frames; f0 += f->slab) {
         const int cnt = f->frames - f0 < f->slab ? f->frames - f0 : f->slab;

@@ -3,7 +3,6 @@
  * (reference libllzfilter/llz_fir.c:442-625) and the multi-channel float32 batch extension.  Plain C; the device
  * is reached only through llz_shim.h.
  */
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../../include/llz_fir.h"
@@ -226,12 +225,7 @@ static int firm_build_ols_tables(firm_t *f, const float *taps, int N)
     if (!cs) rc = LLZ_ERR_NOMEM;
     if (rc == LLZ_OK) {
         float *hf = host[0], *tw = host[1], *w2 = host[2], *w4 = host[3];
-        for (int i = 0; i < N; i++) {
-            /* exact quadrant values keep the table symmetric */
-            const double ang = 2.0 * M_PI * (double)i / (double)N;
-            cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-            cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-        }
+        llz_host_cs_table(cs, N);
         for (int k = 0; k < N; k++) {
             double re = 0.0, im = 0.0;
             for (int t = 0; t < f->flt_len; t++) {
@@ -279,73 +273,11 @@ static size_t firm_part_cap(void)
     return (size_t)((mb >= 1 && mb <= 1024) ? mb : 1024) << 20;
 }
 
-/* cos then sin of 2 pi i / N, i < N, with exact quadrant values */
-static void firm_part_cs_table(double *cs, int N)
+/* floats of one tap row's partition spectra: [P][part_n] complex */
+static size_t firm_part_row(const firm_t *f)
 {
-    for (int i = 0; i < N; i++) {
-        const double ang = 2.0 * M_PI * (double)i / (double)N;
-        cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-        cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-    }
-}
-
-/* one tap row into its partition spectra: dst = [P][N] complex floats, P = ceil(flt_len / (N / 2)), row p =
- * DFT_N(taps[p B .. p B + B), zero-padded) / N by a radix-2 decimation-in-frequency transform in double (twiddles from the
- * quadrant-exact table cs of firm_part_cs_table), rounded to float once and left in that transform's output order (entry i =
- * bin bitrev(i)): the device's forward transform leaves its bins in the same order, and the product is bin-wise.  33 x 8192
- * points at 131073 taps: milliseconds, where the direct DFT of firm_build_ols_tables would sum 10^9 terms.  z: 2 N doubles.
- * The shared-taps handle and the bank both build their spectra here, so equal taps give equal float32 entries. */
-void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, const double *cs, double *z)
-{
-    const int B = N / 2, P = (flt_len + B - 1) / B;
-    for (int p = 0; p < P; p++) {
-        for (int i = 0; i < N; i++) {
-            const long t = (long)p * B + i;
-            z[2 * i] = (i < B && t < flt_len) ? (double)taps[t] : 0.0;
-            z[2 * i + 1] = 0.0;
-        }
-        for (int span = N; span >= 2; span /= 2) {
-            const int half = span / 2, step = N / span;
-            for (int base = 0; base < N; base += span)
-                for (int j = 0; j < half; j++) {
-                    double *a = z + 2 * (base + j), *b = a + 2 * half;
-                    const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
-                    const double dr = a[0] - b[0], di = a[1] - b[1];
-                    a[0] += b[0]; a[1] += b[1];
-                    b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
-                }
-        }
-        float *row = dst + 2 * (size_t)p * (size_t)N;
-        for (int i = 0; i < 2 * N; i++) row[i] = (float)(z[i] / N);
-    }
-}
-
-/* host staging of the spectra: whole tap rows up to this many bytes at a time, one row at least (2.1 MB at 131073 taps) */
-#define FIRM_PART_STAGE_BYTES ((size_t)8 << 20)
-
-/* build the spectra of tap rows [first, first + count) (taps: [count][flt_len]; the shared-taps handle has the one row 0) and
- * upload them in chunks of rows: at init as tables, from set_taps on the handle's stream behind the calls already issued */
-static int firm_part_load_rows(firm_t *f, int first, int count, const float *taps, int at_init)
-{
-    const int N = f->part_n, P = (f->flt_len + N / 2 - 1) / (N / 2);
-    const size_t row = 2 * (size_t)P * (size_t)N;                  /* floats of one row's spectra */
-    size_t chunk = FIRM_PART_STAGE_BYTES / (sizeof(float) * row);
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)count) chunk = (size_t)count;
-    float *hp = (float *)malloc(sizeof(float) * row * chunk);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = (hp && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) firm_part_cs_table(cs, N);
-    for (size_t r0 = 0; r0 < (size_t)count && rc == LLZ_OK; r0 += chunk) {
-        const size_t rows = (size_t)count - r0 < chunk ? (size_t)count - r0 : chunk;
-        for (size_t r = 0; r < rows; r++)
-            llz_host_part_spectra(hp + r * row, taps + (r0 + r) * (size_t)f->flt_len, f->flt_len, N, cs, z);
-        float *d_h = f->d_hpart + ((size_t)first + r0) * row;
-        rc = at_init ? llzs_h2d_table(d_h, hp, sizeof(float) * row * rows) : llzs_h2d(d_h, hp, sizeof(float) * row * rows, f->stream);
-    }
-    free(hp); free(cs); free(z);
-    return rc;
+    const int B = f->part_n / 2;
+    return 2 * (size_t)((f->flt_len + B - 1) / B) * (size_t)f->part_n;
 }
 
 /* the transform size and the scratch bytes of an algo-7 handle, from the tunes set now; refuses a shape of which not one
@@ -378,7 +310,7 @@ static int firm_build_part(firm_t *f, const float *taps, int rows, const char *w
     double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
     int rc = (tw && cs) ? LLZ_OK : LLZ_ERR_NOMEM;
     if (rc == LLZ_OK) {
-        firm_part_cs_table(cs, N);
+        llz_host_cs_table(cs, N);
         for (int m = 0; m < N / 2; m++) firm_w(&tw[2 * m], cs, m);
         f->d_hpart = (float *)llzs_malloc(hbytes);
         if (!f->d_hpart) {
@@ -393,7 +325,7 @@ static int firm_build_part(firm_t *f, const float *taps, int rows, const char *w
         if (!f->d_ptw || !f->d_scratch) rc = LLZ_ERR_NOMEM;
     }
     /* tables through llzs_h2d_table, in a fixed order: a sharded init records and broadcasts them */
-    if (rc == LLZ_OK) rc = firm_part_load_rows(f, 0, rows, taps, 1);
+    if (rc == LLZ_OK) rc = llz_host_load_spectra(who, f->d_hpart, firm_part_row(f), rows, taps, f->flt_len, N, 0, 1, NULL);
     if (rc == LLZ_OK) rc = llzs_h2d_table(f->d_ptw, tw, sizeof(float) * (size_t)N);
     free(tw); free(cs);
     return rc;
@@ -486,9 +418,8 @@ unsigned long llz_fir_filter_mc_init_f64taps(int channels, int frame_len, const 
         llzs_set_error("llz_fir_filter_mc_init_f64taps: no taps");
         return LLZ_BAD_HANDLE;
     }
-    float *t = (float *)malloc(sizeof(float) * (size_t)flt_len);
+    float *t = llz_host_taps_f32("llz_fir_filter_mc_init_f64taps", taps, (size_t)flt_len);
     if (!t) return LLZ_BAD_HANDLE;
-    for (int i = 0; i < flt_len; i++) t[i] = (float)taps[i];
     unsigned long h = llz_fir_filter_mc_init(channels, frame_len, t, flt_len, algo);
     free(t);
     return h;
@@ -632,18 +563,9 @@ static int firm_process(firm_t *f, const float *in, float *out, int frame_len)
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
     if (llz_refuse_device_overlap(f->who, "in", in, bytes, in_dev, "out", out, bytes, out_dev)) return LLZ_ERR_ARG;
-    const float *d_in = in;
-    float *d_out = out;
     int rc = LLZ_OK;
-    if (!in_dev) {
-        d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
-        if (!d_in) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_in, in, bytes, f->stream);
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    const float *d_in = llz_stage_in(&f->st_in, in, bytes, in_dev, f->stream, &rc);
+    float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
     if (rc == LLZ_OK) rc = firm_launch(f, d_in, d_out, frame_len, frame_len, frame_len, f->algo);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? frame_len : rc;
@@ -669,15 +591,13 @@ static int firm_flush(firm_t *f, float *out)
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)keep;
     const int out_dev = llzs_is_device_ptr(out);
     if (out_dev < 0) return LLZ_ERR_ARG;
-    float *d_out = out;
-    if (!out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    int rc = LLZ_OK;
+    float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
+    if (rc != LLZ_OK) return rc;
     /* flt_len-1 zeros per channel through the time-domain kernel (tiny; same arithmetic as the frames); a partitioned handle
      * through the partitioned launcher at every length: above 25248 taps the time-domain kernel cannot hold the filter */
-    int rc = firm_launch(f, f->d_zero, d_out, keep, keep, keep,
-                         f->algo == LLZ_FIR_ALGO_PARTITIONED ? LLZ_FIR_ALGO_PARTITIONED : LLZ_FIR_ALGO_TIME);
+    rc = firm_launch(f, f->d_zero, d_out, keep, keep, keep,
+                     f->algo == LLZ_FIR_ALGO_PARTITIONED ? LLZ_FIR_ALGO_PARTITIONED : LLZ_FIR_ALGO_TIME);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? keep : rc;
 }
@@ -688,16 +608,6 @@ static int firm_flush(firm_t *f, float *out)
  * ===================================================================================================== */
 
 enum { FIRB_N = 1024 };
-
-/* cos / sin of 2 pi i / 1024 with exact quadrant values, as firm_build_ols_tables makes them */
-static void firb_cs_table(double *cs)
-{
-    for (int i = 0; i < FIRB_N; i++) {
-        const double ang = 2.0 * M_PI * (double)i / (double)FIRB_N;
-        cs[2 * i] = (i == FIRB_N / 4 || i == 3 * FIRB_N / 4) ? 0.0 : cos(ang);
-        cs[2 * i + 1] = (i == 0 || i == FIRB_N / 2) ? 0.0 : sin(ang);
-    }
-}
 
 /* dst[0 .. 512] = DFT_1024(taps)[k] / 1024 as float pairs: a radix-2 transform in double (decimation in time, twiddles from
  * the table), rounded once.  The direct DFT of firm_build_ols_tables costs 513 x flt_len terms per filter here: 4096 filters
@@ -740,7 +650,7 @@ static int firb_load_rows(firm_t *f, int first, int count, const float *taps, in
     double *work = hbytes ? (double *)malloc(sizeof(double) * 4 * FIRB_N) : NULL;
     int rc = (pt && (!hbytes || (hb && work))) ? LLZ_OK : LLZ_ERR_NOMEM;
     if (rc == LLZ_OK) {
-        if (hbytes) firb_cs_table(work + 2 * FIRB_N);
+        if (hbytes) llz_host_cs_table(work + 2 * FIRB_N, FIRB_N);
         for (int c = 0; c < count; c++) {
             const float *row = taps + (size_t)c * (size_t)f->flt_len;
             memcpy(pt + (size_t)c * (size_t)tpad, row, sizeof(float) * (size_t)f->flt_len);
@@ -803,7 +713,7 @@ unsigned long llz_fir_bank_mc_init(int channels, int frame_len, const float *tap
         float *tw = (float *)malloc(sizeof(float) * 2 * 1024);
         if (!f->d_hbank || !f->ols.twid || !cs || !tw) rc = LLZ_ERR_NOMEM;
         if (rc == LLZ_OK) {
-            firb_cs_table(cs);
+            llz_host_cs_table(cs, FIRB_N);
             for (int a = 0; a < 32; a++)
                 for (int b = 0; b < 32; b++) firm_w(&tw[2 * (a * 32 + b)], cs, (a * b) % FIRB_N);
             rc = llzs_h2d_table(f->ols.twid, tw, sizeof(float) * 2 * 1024);
@@ -828,10 +738,8 @@ unsigned long llz_fir_bank_mc_init_f64taps(int channels, int frame_len, const do
         llzs_set_error("llz_fir_bank_mc_init_f64taps: channels %d flt_len %d%s", channels, flt_len, taps ? "" : ", no taps");
         return LLZ_BAD_HANDLE;
     }
-    const size_t count = (size_t)channels * (size_t)flt_len;
-    float *t = (float *)malloc(sizeof(float) * count);
+    float *t = llz_host_taps_f32("llz_fir_bank_mc_init_f64taps", taps, (size_t)channels * (size_t)flt_len);
     if (!t) return LLZ_BAD_HANDLE;
-    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
     unsigned long h = llz_fir_bank_mc_init(channels, frame_len, t, flt_len, algo);
     free(t);
     return h;
@@ -887,8 +795,11 @@ int llz_fir_bank_mc_set_taps(unsigned long handle, int first, int count, const f
         return LLZ_ERR_ARG;
     }
     const int prev = llzs_device_enter(f->device);
-    const int rc = f->algo == LLZ_FIR_ALGO_PARTITIONED ? firm_part_load_rows(f, first, count, taps, 0)
-                                                       : firb_load_rows(f, first, count, taps, 0);
+    /* on the handle's stream, behind the calls already issued */
+    const int rc = f->algo == LLZ_FIR_ALGO_PARTITIONED
+        ? llz_host_load_spectra("llz_fir_bank_mc_set_taps", f->d_hpart + (size_t)first * firm_part_row(f), firm_part_row(f), count,
+                                taps, f->flt_len, f->part_n, 0, 0, f->stream)
+        : firb_load_rows(f, first, count, taps, 0);
     llzs_device_leave(prev);
     return rc;
 }
@@ -961,13 +872,8 @@ unsigned long llz_fir_pbank_mc_init_f64taps(int channels, int frame_len, const d
                        LLZS_FIR_PART_MAX_TAPS, taps ? "" : ", no taps");
         return LLZ_BAD_HANDLE;
     }
-    const size_t count = (size_t)channels * (size_t)flt_len;
-    float *t = (float *)malloc(sizeof(float) * count);
-    if (!t) {
-        llzs_set_error("llz_fir_pbank_mc_init_f64taps: no host memory for %zu taps", count);
-        return LLZ_BAD_HANDLE;
-    }
-    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
+    float *t = llz_host_taps_f32("llz_fir_pbank_mc_init_f64taps", taps, (size_t)channels * (size_t)flt_len);
+    if (!t) return LLZ_BAD_HANDLE;
     unsigned long h = llz_fir_pbank_mc_init(channels, frame_len, t, flt_len);
     free(t);
     return h;

@@ -1,8 +1,8 @@
 /* llz_fir_matrix_host.c -- include/llz_fir.h part 6: llz_fir_matrix_mc, the many-in, many-out stream convolver y_o = sum_i x_i *
  * h_{o,i} (kernels K4g, fir_matrix.hip).  llz_fir_stream_mc's scheme (llz_fir_stream_host.c) with a delay line per INPUT, tap
  * spectra per path (o, i) and three launches per call: forward transforms, the product summed over inputs in G groups, inverse
- * transforms.  The tap spectra and the twiddles come from the stream convolver's builders, so one path of the matrix is a
- * stream channel.  Staging, pointer classification and error conventions are those of llz_fir_host.c. */
+ * transforms.  The tap spectra and the twiddles come from the builders the stream convolver uses (llz_spectra.c), so one
+ * path of the matrix is a stream channel.  Staging, pointer classification and error conventions are those of llz_fir_host.c. */
 #include <stdlib.h>
 #include <string.h>
 #include "llz_host.h"
@@ -14,7 +14,6 @@
 #define FIRX_WG_TARGET 1024                     /* workgroups of the product asked for before the sum over inputs stays whole */
 #define FIRX_MAX_GROUPS 32
 #define FIRX_SCRATCH_BYTES ((size_t)64 << 20)   /* the partial spectra of a flush beyond this go in several passes */
-#define FIRX_STAGE_BYTES ((size_t)8 << 20)      /* host staging of the spectra: whole tap rows up to this, one at least */
 
 typedef struct {
     int tag;                    /* LLZ_TAG_FIRX */
@@ -67,31 +66,14 @@ static int firx_row_connected(const float *taps, int flt_len)
     return 0;
 }
 
-/* the spectra of the paths (o, in_first .. in_first + in_count) (taps: [in_count][flt_len]) built and uploaded in chunks of
- * rows, and the paths' entries of the connection table: at init as tables, from set_taps on the handle's stream behind the
- * calls already issued */
+/* the spectra of the paths (o, in_first .. in_first + in_count) (taps: [in_count][flt_len]) built and uploaded, and the paths'
+ * entries of the connection table: at init as tables, from set_taps on the handle's stream behind the calls already issued */
 static int firx_load_paths(firx_t *f, int o, int in_first, int in_count, const float *taps, int at_init)
 {
-    const int N = 2 * f->block;
     const size_t row = 2 * (size_t)f->P * (size_t)f->block;         /* floats of one path's spectra */
     const size_t first = (size_t)o * (size_t)f->inputs + (size_t)in_first;
-    size_t chunk = FIRX_STAGE_BYTES / (sizeof(float) * row);
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)in_count) chunk = (size_t)in_count;
-    float *hp = (float *)malloc(sizeof(float) * row * chunk);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = (hp && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc != LLZ_OK) llzs_set_error("llz_fir_matrix_mc: no host memory for %zu B of tap spectra", sizeof(float) * row * chunk);
-    if (rc == LLZ_OK) llz_host_stream_cs_table(cs, N);
-    for (size_t r0 = 0; r0 < (size_t)in_count && rc == LLZ_OK; r0 += chunk) {
-        const size_t rows = (size_t)in_count - r0 < chunk ? (size_t)in_count - r0 : chunk;
-        for (size_t r = 0; r < rows; r++)
-            llz_host_stream_spectra(hp + r * row, taps + (r0 + r) * (size_t)f->flt_len, f->flt_len, f->block, cs, z);
-        float *d_h = f->d_h + (first + r0) * row;
-        rc = at_init ? llzs_h2d_table(d_h, hp, sizeof(float) * row * rows) : llzs_h2d(d_h, hp, sizeof(float) * row * rows, f->stream);
-    }
-    free(hp); free(cs); free(z);
+    const int rc = llz_host_load_spectra("llz_fir_matrix_mc", f->d_h + first * row, row, in_count, taps, f->flt_len, 2 * f->block, 1,
+                                         at_init, f->stream);
     if (rc != LLZ_OK) return rc;
     for (int i = 0; i < in_count; i++) {
         const unsigned char now = (unsigned char)firx_row_connected(taps + (size_t)i * (size_t)f->flt_len, f->flt_len);
@@ -220,13 +202,8 @@ unsigned long llz_fir_matrix_mc_init_f64taps(int inputs, int outputs, int block,
 {
     const char *who = "llz_fir_matrix_mc_init_f64taps";
     if (firx_refuse(who, inputs, outputs, block, frame_len, taps, flt_len)) return LLZ_BAD_HANDLE;
-    const size_t count = (size_t)outputs * (size_t)inputs * (size_t)flt_len;
-    float *t = (float *)malloc(sizeof(float) * count);
-    if (!t) {
-        llzs_set_error("%s: no host memory for %zu taps", who, count);
-        return LLZ_BAD_HANDLE;
-    }
-    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
+    float *t = llz_host_taps_f32(who, taps, (size_t)outputs * (size_t)inputs * (size_t)flt_len);
+    if (!t) return LLZ_BAD_HANDLE;
     unsigned long h = llz_fir_matrix_mc_init(inputs, outputs, block, frame_len, t, flt_len);
     free(t);
     return h;
@@ -258,18 +235,9 @@ static int firx_process(firx_t *f, const float *in, float *out, int frame_len)
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
     if (llz_refuse_device_overlap("llz_fir_matrix_mc", "in", in, ibytes, in_dev, "out", out, obytes, out_dev)) return LLZ_ERR_ARG;
-    const float *d_in = in;
-    float *d_out = out;
     int rc = LLZ_OK;
-    if (!in_dev) {
-        d_in = (const float *)llz_stage_reserve(&f->st_in, ibytes);
-        if (!d_in) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_in, in, ibytes, f->stream);
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, obytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    const float *d_in = llz_stage_in(&f->st_in, in, ibytes, in_dev, f->stream, &rc);
+    float *d_out = llz_stage_out(&f->st_out, out, obytes, out_dev, &rc);
     if (rc == LLZ_OK)
         rc = llzs_fir_matrix_fwd_f32(f->block, f->d_tw, f->d_ring, f->d_prev[f->cur], f->d_prev[f->cur ^ 1], d_in, f->inputs, f->k,
                                      0, frame_len, f->R, f->head, f->stream);
@@ -310,16 +278,13 @@ static int firx_flush(firx_t *f, float *out)
     const size_t bytes = sizeof(float) * (size_t)f->outputs * (size_t)keep;
     const int out_dev = llzs_is_device_ptr(out);
     if (out_dev < 0) return LLZ_ERR_ARG;
-    float *d_out = out;
-    if (!out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    int rc = LLZ_OK;
+    float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
+    if (rc != LLZ_OK) return rc;
     /* behind the input only the spectrum of (last block, zeros) is new: it goes into slot `head`, which the reset below gives
      * up anyway; then the ceil(keep / block) zero blocks side by side, as many at a time as the scratch holds */
     const int nblk = (keep + B - 1) / B;
-    int rc = llzs_fir_matrix_fwd_f32(B, f->d_tw, f->d_ring, f->d_prev[f->cur], NULL, NULL, f->inputs, 1, 1, 0, f->R, f->head,
-                                     f->stream);
+    rc = llzs_fir_matrix_fwd_f32(B, f->d_tw, f->d_ring, f->d_prev[f->cur], NULL, NULL, f->inputs, 1, 1, 0, f->R, f->head, f->stream);
     for (int j0 = 0; j0 < nblk && rc == LLZ_OK; j0 += f->ycap) {
         const int nb = nblk - j0 < f->ycap ? nblk - j0 : f->ycap;
         const long left = (long)keep - (long)j0 * B, n_out = left < (long)nb * B ? left : (long)nb * B;

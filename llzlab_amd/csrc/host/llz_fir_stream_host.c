@@ -2,7 +2,6 @@
  * between calls (kernel K4f, fir_stream.hip).  Its own handle and tag: the history of a firm_t (a ping-pong of flt_len - 1
  * samples and the tail kernel) does not apply here -- the history lives as a ring of input spectra plus the last input block.
  * Staging, pointer classification and error conventions are those of llz_fir_host.c. */
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "llz_host.h"
@@ -31,113 +30,6 @@ static void firs_destroy(firs_t *f)
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     f->tag = 0;
     free(f);
-}
-
-/* cos then sin of 2 pi i / N, i < N, with exact quadrant values */
-void llz_host_stream_cs_table(double *cs, int N)
-{
-    for (int i = 0; i < N; i++) {
-        const double ang = 2.0 * M_PI * (double)i / (double)N;
-        cs[2 * i] = (i == N / 4 || i == 3 * N / 4) ? 0.0 : cos(ang);
-        cs[2 * i + 1] = (i == 0 || i == N / 2) ? 0.0 : sin(ang);
-    }
-}
-
-static int firs_bitrev(int i, int bits)
-{
-    int r = 0;
-    for (int b = 0; b < bits; b++) r |= ((i >> b) & 1) << (bits - 1 - b);
-    return r;
-}
-
-/* Row p: the N-point transform of partition p by radix-2 decimation in frequency in double, whose output entry e is bin
- * bitrev_N(e).  A bin k < block has a zero top bit, so it sits at the even entry 2 bitrev_block(k): the packed row is the even
- * entries as they lie, and the Nyquist bin (k = block) is entry 1.  Shared and per-channel handles both build their spectra
- * here, so equal taps give equal float32 entries. */
-void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int block, const double *cs, double *z)
-{
-    const int N = 2 * block, P = (flt_len + block - 1) / block;
-    const double scale = 1.0 / (2.0 * (double)N);
-    for (int p = 0; p < P; p++) {
-        for (int i = 0; i < N; i++) {
-            const long t = (long)p * block + i;
-            z[2 * i] = (i < block && t < flt_len) ? (double)taps[t] : 0.0;
-            z[2 * i + 1] = 0.0;
-        }
-        for (int span = N; span >= 2; span /= 2) {
-            const int half = span / 2, step = N / span;
-            for (int base = 0; base < N; base += span)
-                for (int j = 0; j < half; j++) {
-                    double *a = z + 2 * (base + j), *b = a + 2 * half;
-                    const double wr = cs[2 * j * step], wi = -cs[2 * j * step + 1];
-                    const double dr = a[0] - b[0], di = a[1] - b[1];
-                    a[0] += b[0]; a[1] += b[1];
-                    b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
-                }
-        }
-        float *row = dst + 2 * (size_t)p * (size_t)block;
-        row[0] = (float)(z[0] * scale);
-        row[1] = (float)(z[2] * scale);
-        for (int i = 1; i < block; i++) {
-            row[2 * i] = (float)(z[4 * i] * scale);
-            row[2 * i + 1] = (float)(z[4 * i + 1] * scale);
-        }
-    }
-}
-
-/* host staging of the spectra: whole tap rows up to this many bytes at a time, one row at least (1 MB at 131073 taps) */
-#define FIRS_STAGE_BYTES ((size_t)8 << 20)
-
-/* build the spectra of tap rows [first, first + count) (taps: [count][flt_len]) and upload them in chunks of rows: at init as
- * tables, from set_taps on the handle's stream behind the calls already issued */
-static int firs_load_rows(firs_t *f, int first, int count, const float *taps, int at_init)
-{
-    const int N = 2 * f->block;
-    const size_t row = 2 * (size_t)f->P * (size_t)f->block;         /* floats of one row's spectra */
-    size_t chunk = FIRS_STAGE_BYTES / (sizeof(float) * row);
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)count) chunk = (size_t)count;
-    float *hp = (float *)malloc(sizeof(float) * row * chunk);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    double *z = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = (hp && cs && z) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) llz_host_stream_cs_table(cs, N);
-    for (size_t r0 = 0; r0 < (size_t)count && rc == LLZ_OK; r0 += chunk) {
-        const size_t rows = (size_t)count - r0 < chunk ? (size_t)count - r0 : chunk;
-        for (size_t r = 0; r < rows; r++)
-            llz_host_stream_spectra(hp + r * row, taps + (r0 + r) * (size_t)f->flt_len, f->flt_len, f->block, cs, z);
-        float *d_h = f->d_h + ((size_t)first + r0) * row;
-        rc = at_init ? llzs_h2d_table(d_h, hp, sizeof(float) * row * rows) : llzs_h2d(d_h, hp, sizeof(float) * row * rows, f->stream);
-    }
-    free(hp); free(cs); free(z);
-    return rc;
-}
-
-/* the transform's twiddles W_block^m, m < block / 2, then the split twiddles by position: W_N^bitrev(i), i < block */
-int llz_host_stream_twiddles(float *d_tw, int block)
-{
-    const int B = block, N = 2 * B;
-    int bits = 0;
-    while ((1 << bits) < B) bits++;
-    const size_t count = (size_t)B / 2 + (size_t)B;
-    float *tw = (float *)malloc(sizeof(float) * 2 * count);
-    double *cs = (double *)malloc(sizeof(double) * 2 * (size_t)N);
-    int rc = (tw && cs) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) {
-        llz_host_stream_cs_table(cs, N);
-        for (int m = 0; m < B / 2; m++) {
-            tw[2 * m] = (float)cs[2 * (2 * m)];
-            tw[2 * m + 1] = (float)(-cs[2 * (2 * m) + 1]);
-        }
-        for (int i = 0; i < B; i++) {
-            const int k = firs_bitrev(i, bits);
-            tw[2 * (B / 2 + i)] = (float)cs[2 * k];
-            tw[2 * (B / 2 + i) + 1] = (float)(-cs[2 * k + 1]);
-        }
-        rc = llzs_h2d_table(d_tw, tw, sizeof(float) * 2 * count);
-    }
-    free(tw); free(cs);
-    return rc;
 }
 
 /* the refusals of both inits, each with a message of its own that names `who` and the range */
@@ -215,7 +107,8 @@ unsigned long llz_fir_stream_mc_init(int channels, int block, int frame_len, con
         }
     }
     /* tables through llzs_h2d_table, in a fixed order */
-    if (rc == LLZ_OK) rc = firs_load_rows(f, 0, rows, taps, 1);
+    if (rc == LLZ_OK)
+        rc = llz_host_load_spectra(who, f->d_h, 2 * (size_t)f->P * (size_t)block, rows, taps, flt_len, 2 * block, 1, 1, NULL);
     if (rc == LLZ_OK) rc = llz_host_stream_twiddles(f->d_tw, f->block);
     if (rc == LLZ_OK) rc = firs_clear(f);
     if (rc == LLZ_OK) rc = llzs_sync(NULL);
@@ -230,13 +123,8 @@ unsigned long llz_fir_stream_mc_init_f64taps(int channels, int block, int frame_
 {
     const char *who = "llz_fir_stream_mc_init_f64taps";
     if (firs_refuse(who, channels, block, frame_len, taps, rows, flt_len)) return LLZ_BAD_HANDLE;
-    const size_t count = (size_t)rows * (size_t)flt_len;
-    float *t = (float *)malloc(sizeof(float) * count);
-    if (!t) {
-        llzs_set_error("%s: no host memory for %zu taps", who, count);
-        return LLZ_BAD_HANDLE;
-    }
-    for (size_t i = 0; i < count; i++) t[i] = (float)taps[i];
+    float *t = llz_host_taps_f32(who, taps, (size_t)rows * (size_t)flt_len);
+    if (!t) return LLZ_BAD_HANDLE;
     unsigned long h = llz_fir_stream_mc_init(channels, block, frame_len, t, rows, flt_len);
     free(t);
     return h;
@@ -267,18 +155,9 @@ static int firs_process(firs_t *f, const float *in, float *out, int frame_len)
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
     if (llz_refuse_device_overlap("llz_fir_stream_mc", "in", in, bytes, in_dev, "out", out, bytes, out_dev)) return LLZ_ERR_ARG;
-    const float *d_in = in;
-    float *d_out = out;
     int rc = LLZ_OK;
-    if (!in_dev) {
-        d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
-        if (!d_in) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_in, in, bytes, f->stream);
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    const float *d_in = llz_stage_in(&f->st_in, in, bytes, in_dev, f->stream, &rc);
+    float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
     if (rc == LLZ_OK)
         rc = llzs_fir_stream_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, d_in, d_out, f->channels, f->k, 0,
                                  frame_len, frame_len, frame_len, f->P, f->R, f->head, f->stream);
@@ -310,14 +189,12 @@ static int firs_flush(firs_t *f, float *out)
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)keep;
     const int out_dev = llzs_is_device_ptr(out);
     if (out_dev < 0) return LLZ_ERR_ARG;
-    float *d_out = out;
-    if (!out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    int rc = LLZ_OK;
+    float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
+    if (rc != LLZ_OK) return rc;
     /* ceil(keep / block) zero blocks behind the input so far, then the delay line to zeros: the handle starts over */
-    int rc = llzs_fir_stream_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, NULL, d_out, f->channels,
-                                 (keep + f->block - 1) / f->block, 1, keep, 0, keep, f->P, f->R, f->head, f->stream);
+    rc = llzs_fir_stream_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, NULL, d_out, f->channels,
+                             (keep + f->block - 1) / f->block, 1, keep, 0, keep, f->P, f->R, f->head, f->stream);
     if (rc == LLZ_OK) rc = firs_clear(f);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? keep : rc;
@@ -363,7 +240,9 @@ int llz_fir_stream_mc_set_taps(unsigned long handle, int first, int count, const
         return LLZ_ERR_ARG;
     }
     const int prev = llzs_device_enter(f->device);
-    const int rc = firs_load_rows(f, first, count, taps, 0);
+    const size_t row = 2 * (size_t)f->P * (size_t)f->block;         /* floats of one row's spectra */
+    const int rc = llz_host_load_spectra("llz_fir_stream_mc_set_taps", f->d_h + (size_t)first * row, row, count, taps, f->flt_len,
+                                         2 * f->block, 1, 0, f->stream);      /* behind the calls already issued */
     llzs_device_leave(prev);
     return rc;
 }

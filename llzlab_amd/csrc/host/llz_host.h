@@ -29,21 +29,36 @@ int llz_host_mdct_on_device(unsigned long handle, const double *d_src, double *d
 /* cos then sin of 2 pi i / size, i < size, as llz_fft_init builds them (llz_fft.c:222-229), uploaded; NULL on failure */
 double *llz_host_fft_table_f64(int size);
 
-/* llz_fir_host.c: one tap row into the [P][N] complex floats of its partition spectra (LLZ_FIR_ALGO_PARTITIONED), in the
- * order of a decimation-in-frequency transform's output; cs: 2 N doubles, cos then sin of 2 pi i / N with exact quadrant
- * values; z: 2 N doubles of work space */
+/* ---- llz_spectra.c: the tables of the frequency-domain FIR forms ---- */
+
+/* cs: 2 N doubles, cos then sin of 2 pi i / N, i < N, with exact quadrant values: the one table every FIR form's spectra and
+ * twiddles come from */
+void llz_host_cs_table(double *cs, int N);
+
+/* one tap row into the [P][N] complex floats of its partition spectra (LLZ_FIR_ALGO_PARTITIONED), P = ceil(flt_len / (N / 2)):
+ * row p = DFT_N(taps[p N / 2 .. (p + 1) N / 2), zero-padded) / N, computed in double and rounded to float once, in the order of a
+ * decimation-in-frequency transform's output (entry i = bin bitrev(i)); cs: llz_host_cs_table(cs, N); z: 2 N doubles of work
+ * space */
 void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, const double *cs, double *z);
 
-/* llz_fir_stream_host.c: one tap row into the [P][block] complex floats of its partition spectra for llz_fir_stream_mc, P =
- * ceil(flt_len / block): row p holds bins 0 .. block of DFT_N(taps[p block .. (p + 1) block), zero-padded), N = 2 block, scaled by
- * 1 / (2 N), computed in double and rounded to float once.  Entry i > 0 is bin bitrev(i) (over log2 block bits); entry 0
- * packs the two real bins: (DC, Nyquist).  cs: 2 N doubles, cos then sin of 2 pi i / N with exact quadrant values; z: 2 N
- * doubles of work space */
+/* one tap row into the [P][block] complex floats of its partition spectra for the delay-line forms (llz_fir_stream_mc,
+ * llz_fir_matrix_mc), P = ceil(flt_len / block): row p holds bins 0 .. block of the same transform, N = 2 block, scaled by
+ * 1 / (2 N).  Entry i > 0 is bin bitrev(i) (over log2 block bits); entry 0 packs the two real bins: (DC, Nyquist).  cs:
+ * llz_host_cs_table(cs, N); z: 2 N doubles of work space */
 void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int block, const double *cs, double *z);
-/* the cs table it takes, and the device table of both delay-line forms (llz_fir_stream_mc, llz_fir_matrix_mc) uploaded through
- * llzs_h2d_table: [block / 2] complex W_block^m, then [block] complex W_N^bitrev(i); d_tw: 2 (block / 2 + block) floats */
-void llz_host_stream_cs_table(double *cs, int N);
+/* the device table of both delay-line forms uploaded through llzs_h2d_table: [block / 2] complex W_block^m, then [block] complex
+ * W_N^bitrev(i); d_tw: 2 (block / 2 + block) floats */
 int  llz_host_stream_twiddles(float *d_tw, int block);
+
+/* The spectra of `count` tap rows (taps: [count][flt_len]) built with N-point transforms -- llz_host_stream_spectra if packed,
+ * else llz_host_part_spectra -- into d_dst = [count][row] floats, in chunks of whole rows of at most 8 MiB of host staging (one
+ * row at least): at init through llzs_h2d_table, one table per chunk in row order, else (set_taps) through llzs_h2d on
+ * `stream`, behind the calls already issued.  Out of host memory: LLZ_ERR_NOMEM and a message naming `who`. */
+int llz_host_load_spectra(const char *who, float *d_dst, size_t row, int count, const float *taps, int flt_len, int N, int packed,
+                          int at_init, void *stream);
+
+/* a malloc'ed float copy of `count` double taps; NULL, with a message naming `who`, when out of host memory */
+float *llz_host_taps_f32(const char *who, const double *taps, size_t count);
 
 /* Caller buffers: llzs_is_device_ptr(p) is 1 for device memory of the CURRENT device (used in place), 0 for host memory
  * (staged through the GPU) and LLZ_ERR_ARG, with a message, for device memory that lives on another device -- a handle
@@ -78,5 +93,14 @@ typedef struct {
 /* grow-only device scratch; returns NULL on failure */
 void *llz_stage_reserve(llz_stage_t *s, size_t bytes);
 void  llz_stage_release(llz_stage_t *s);
+
+/* The staged call of the out-of-place batch entry points, once the caller's pointers are classified (user_dev as
+ * llzs_is_device_ptr() answered, 0 or 1) and overlap is refused: where a kernel reads its input and writes its output.  Device
+ * memory is used where it lies; for host memory llz_stage_in reserves `bytes` of s and copies the input there on `stream`,
+ * llz_stage_out only reserves, and the call ends with llzs_d2h from the stage.  Both chain on *rc: with *rc != LLZ_OK on entry
+ * they do nothing (a failed upload skips the output's reserve), and they set it to LLZ_ERR_NOMEM when the reserve fails or to
+ * the copy's error. */
+const void *llz_stage_in(llz_stage_t *s, const void *user, size_t bytes, int user_dev, void *stream, int *rc);
+void *llz_stage_out(llz_stage_t *s, void *user, size_t bytes, int user_dev, int *rc);
 
 #endif

@@ -546,18 +546,9 @@ static int iirm_process(iirm_t *f, const char *who, const float *x, float *y, in
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
     /* a later time segment reads its warm-up chunks from x while the segment before it writes them to y */
     if (llz_refuse_device_overlap(who, "x", x, bytes, in_dev, "y", y, bytes, out_dev)) return LLZ_ERR_ARG;
-    const float *d_in = x;
-    float *d_out = y;
     int rc = LLZ_OK;
-    if (!in_dev) {
-        d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
-        if (!d_in) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_in, x, bytes, f->stream);
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    const float *d_in = llz_stage_in(&f->st_in, x, bytes, in_dev, f->stream, &rc);
+    float *d_out = llz_stage_out(&f->st_out, y, bytes, out_dev, &rc);
     /* whole 1024-sample chunks go through the path's kernel (needs 16-byte aligned rows): with a 32-sample form the whole
      * 2048-sample chunks, then its 16-sample counterpart what is left; the ragged remainder through the one-lane-per-channel
      * kernel.  All read and write the same per-section state. */
@@ -1026,18 +1017,10 @@ int llz_iir_mc(unsigned long handle, const float *x, float *y, int frame_len)
     const int prev = llzs_device_enter(f->device);
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frame_len;
     const int in_dev = llzs_is_device_ptr(x), out_dev = llzs_is_device_ptr(y);
-    const float *d_in = x;
-    float *d_out = y;
     int rc = (in_dev < 0 || out_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_iir_mc", "x", x, bytes, in_dev, "y", y, bytes, out_dev);
-    if (rc == LLZ_OK && !in_dev) {
-        d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
-        rc = d_in ? llzs_h2d((void *)d_in, x, bytes, f->stream) : LLZ_ERR_NOMEM;
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) rc = LLZ_ERR_NOMEM;
-    }
+    const float *d_in = llz_stage_in(&f->st_in, x, bytes, in_dev, f->stream, &rc);
+    float *d_out = llz_stage_out(&f->st_out, y, bytes, out_dev, &rc);
     if (rc == LLZ_OK) rc = iirg_launch(f, d_in, d_out, frame_len);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(y, d_out, bytes, f->stream);
     llzs_device_leave(prev);
@@ -1056,12 +1039,8 @@ int llz_iir_mc_flush(unsigned long handle, float *y)
     const int prev = llzs_device_enter(f->device);
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)f->N;
     const int out_dev = llzs_is_device_ptr(y);
-    float *d_out = y;
     int rc = out_dev < 0 ? LLZ_ERR_ARG : LLZ_OK;
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) rc = LLZ_ERR_NOMEM;
-    }
+    float *d_out = llz_stage_out(&f->st_out, y, bytes, out_dev, &rc);
     if (rc == LLZ_OK) rc = iirg_launch(f, f->d_zero, d_out, f->N);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(y, d_out, bytes, f->stream);
     llzs_device_leave(prev);

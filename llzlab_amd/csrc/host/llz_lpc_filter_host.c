@@ -134,23 +134,10 @@ static int lpcf_run(lpcf_t *f, const char *who, int synth, const char *in_name, 
     if (llz_refuse_device_overlap(who, in_name, in, bytes, in_dev, out_name, out, bytes, out_dev) ||
         llz_refuse_device_overlap(who, "acof", acof, cbytes, cof_dev, out_name, out, bytes, out_dev))
         return LLZ_ERR_ARG;
-    const float *d_in = in, *d_cof = acof;
-    float *d_out = out;
     int rc = LLZ_OK;
-    if (!in_dev) {
-        d_in = (const float *)llz_stage_reserve(&f->st_in, bytes);
-        if (!d_in) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_in, in, bytes, f->stream);
-    }
-    if (rc == LLZ_OK && !cof_dev) {
-        d_cof = (const float *)llz_stage_reserve(&f->st_cof, cbytes);
-        if (!d_cof) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_cof, acof, cbytes, f->stream);
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = (float *)llz_stage_reserve(&f->st_out, bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    const float *d_in = llz_stage_in(&f->st_in, in, bytes, in_dev, f->stream, &rc);
+    const float *d_cof = llz_stage_in(&f->st_cof, acof, cbytes, cof_dev, f->stream, &rc);
+    float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
     if (rc == LLZ_OK && synth)
         rc = llzs_lpc_synth_f32(d_in, d_cof, d_out, f->d_ys, f->channels, frames, f->frame_len, f->p, f->stream);
     if (rc == LLZ_OK && !synth) {

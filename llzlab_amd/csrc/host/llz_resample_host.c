@@ -716,18 +716,9 @@ static long rsm_process(rsm_t *r, unsigned long handle, const void *in, long n_i
     const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
     if (in_dev < 0 || out_dev < 0) return LLZ_ERR_ARG;            /* a buffer of another GPU: refused, message set */
     if (llz_refuse_device_overlap("llz_resample_mc", "in", in, in_bytes, in_dev, "out", out, out_bytes, out_dev)) return LLZ_ERR_ARG;
-    const void *d_in = in;
-    void *d_out = out;
     int rc = LLZ_OK;
-    if (!in_dev) {
-        d_in = llz_stage_reserve(&r->st_in, in_bytes);
-        if (!d_in) return LLZ_ERR_NOMEM;
-        rc = llzs_h2d((void *)d_in, in, in_bytes, r->stream);
-    }
-    if (rc == LLZ_OK && !out_dev) {
-        d_out = llz_stage_reserve(&r->st_out, out_bytes);
-        if (!d_out) return LLZ_ERR_NOMEM;
-    }
+    const void *d_in = llz_stage_in(&r->st_in, in, in_bytes, in_dev, r->stream, &rc);
+    void *d_out = llz_stage_out(&r->st_out, out, out_bytes, out_dev, &rc);
     const void *hist = r->Q > 1 ? r->d_hist[r->cur] : NULL;
     rsm_path ran = r->primary;
     if (rc == LLZ_OK) {

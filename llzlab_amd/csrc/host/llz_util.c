@@ -38,6 +38,22 @@ void *llz_stage_reserve(llz_stage_t *s, size_t bytes)
     return s->dev;
 }
 
+void *llz_stage_out(llz_stage_t *s, void *user, size_t bytes, int user_dev, int *rc)
+{
+    if (*rc != LLZ_OK || user_dev) return user;
+    void *d = llz_stage_reserve(s, bytes);
+    if (!d) *rc = LLZ_ERR_NOMEM;
+    return d;
+}
+
+const void *llz_stage_in(llz_stage_t *s, const void *user, size_t bytes, int user_dev, void *stream, int *rc)
+{
+    if (*rc != LLZ_OK || user_dev) return user;
+    void *d = llz_stage_out(s, NULL, bytes, 0, rc);
+    if (d) *rc = llzs_h2d(d, user, bytes, stream);
+    return d;
+}
+
 void llz_stage_release(llz_stage_t *s)
 {
     if (s->dev) llzs_free(s->dev);
