@@ -190,13 +190,36 @@ int llz_fir_stream_mc_reset(unsigned long handle);
 /* replace tap rows [first, first+count) between calls; taps: HOST [count][flt_len].  rows == channels: any range inside
  * [0, channels); rows == 1: only first 0, count 1.  Ordered on the handle's stream behind the calls already issued.  The
  * delay line is kept, and it holds INPUT spectra: from the next call on the output is the new taps applied to the whole
- * input so far (no crossfade). */
+ * input so far -- a step in the output; llz_fir_xfade_stream_mc below fades instead.  While a fade is in flight the call is
+ * refused (LLZ_ERR_ARG, the message gives the blocks left). */
 int llz_fir_stream_mc_set_taps(unsigned long handle, int first, int count, const float *taps);
 /* out = {N = 2 block, P = ceil(flt_len / block), ring slots R, blocks per call k}; nothing is launched */
 int llz_fir_stream_mc_plan(unsigned long handle, int out[4]);
 int llz_fir_stream_mc_flt_len(unsigned long handle);
 /* stream: a hipStream_t passed as void* (NULL = default stream) */
 int llz_fir_stream_mc_set_stream(unsigned long handle, void *stream);
+/* A click-free change of taps: rows [first, first+count) (taps: HOST [count][flt_len], ranges as _set_taps takes them) FADE to the
+ * new taps over fade_blocks blocks, 1..4096.  The fade starts with the first block processed after the call.  With F =
+ * fade_blocks, B = block and n = 0 .. F B - 1 counting samples from that block's first one, a fading row's output is
+ *     y[n] = fmaf(w[n], y_new[n] - y_old[n], y_old[n]),    w[n] = (float)n / (float)(F B), correctly rounded
+ * (F B <= 2^24, so n is exact in float32), where y_old is the output of the row's taps as they were, applied to the whole input
+ * so far -- what llz_fir_stream_mc computes without the fade -- and y_new the same for the new taps: both filters run on the
+ * one delay line, which holds input spectra.  From sample F B on the output is y_new alone and the handle is in exactly the
+ * state _set_taps(new) would have left it in.  w[0] = 0: the first faded sample is the old filter's value to the bit; equal old
+ * and new taps give y_new - y_old = 0: the whole fade is bit-equal to no fade; rows that do not fade keep their bits
+ * throughout.  A fade spans calls: a call of k blocks may hold its start and its end, blocks past the end are plain new-taps
+ * blocks, the weight depends on the sample's index within the fade alone, and how calls group the blocks does not change a bit.
+ * ONE fade at a time per handle: a call while one is in flight is refused -- except that until the first block of a pending
+ * fade has been processed, further calls with the same fade_blocks add or replace rows of that fade, so that a bank can fade
+ * rows that are not neighbours together.  The new rows' spectra go into a second buffer of rows x P x block x 8 bytes,
+ * allocated at the first fade and kept (a failed allocation names the bytes), built on the handle's stream behind the calls
+ * already issued.  Refused, each with a message of its own: a bad handle, NULL taps, rows outside the handle, fade_blocks
+ * outside 1..4096, a fade already in flight.  While a fade is in flight _set_taps is refused, _reset clears the delay line and
+ * adopts the new taps at once, and _flush goes on with the ramp through its zero blocks (flush block j is fade block done + j)
+ * and then leaves the handle reset WITH THE NEW TAPS adopted.  Returns 0 or a negative LLZ_ERR_* code. */
+int llz_fir_xfade_stream_mc(unsigned long handle, int first, int count, const float *taps, int fade_blocks);
+/* the blocks of the fade still to run (fade_blocks while it is pending), 0 when none is in flight; LLZ_ERR_ARG for a bad handle */
+int llz_fir_xfade_stream_mc_left(unsigned long handle);
 
 /* ---- Part 6: the matrix convolver -- many inputs into many outputs, y_o = sum_i x_i * h_{o,i} -------------------------- */
 

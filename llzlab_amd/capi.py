@@ -163,6 +163,8 @@ def lib():
     sig("llz_fir_stream_mc_plan", i, ul, C.POINTER(C.c_int))
     sig("llz_fir_stream_mc_flt_len", i, ul)
     sig("llz_fir_stream_mc_set_stream", i, ul, vp)
+    sig("llz_fir_xfade_stream_mc", i, ul, i, i, vp, i)
+    sig("llz_fir_xfade_stream_mc_left", i, ul)
     sig("llz_fir_matrix_mc_init", ul, i, i, i, i, vp, i)
     sig("llz_fir_matrix_mc_init_f64taps", ul, i, i, i, i, vp, i)
     sig("llz_fir_matrix_mc_uninit", None, ul)

@@ -70,4 +70,8 @@ __device__ __forceinline__ float2 split_inv(float2 a, float2 ym, float2 w)
 }
 __device__ __forceinline__ float2 split_inv0(float2 a) { return float2{a.x + a.y, a.x - a.y}; }
 
+// one sample of a crossfade between two filters' outputs (fir_stream_fade.hip): w = 0 gives y_old to the bit, equal outputs give
+// that output to the bit at any w
+__device__ __forceinline__ float fade_blend(float w, float y_old, float y_new) { return __builtin_fmaf(w, y_new - y_old, y_old); }
+
 } // namespace

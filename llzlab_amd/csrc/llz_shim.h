@@ -168,6 +168,16 @@ int llzs_fir_part_bank_f32(int nfft, const float *hbank, const float *tw, float 
 int llzs_fir_stream_f32(int block, const float *hspec, int bank, const float *tw, float *ring, float *prev, const float *in,
                         float *out, int channels, int nblk, int flush, long n_out, long in_pitch, long out_pitch, int P, int R,
                         int head, void *stream);
+/* llzs_fir_stream_f32 with a fade between tap sets in flight (fir_stream_fade.hip): the same launch arguments, then hspec_new =
+ * the new taps' spectra laid out as hspec (only rows marked fading are read), fading = one byte per tap row on the device
+ * (bank != 0: channels rows, else one), and the fade's position: block j of this launch is block fade_done + j of fade_blocks
+ * (1 .. 4096, 0 <= fade_done < fade_blocks).  A fading row's samples are fmaf(w, y_new - y_old, y_old), w = (float)n / (float)
+ * (fade_blocks block), n counted from the fade's first sample; from block fade_blocks on they are y_new alone; rows not marked
+ * get llzs_fir_stream_f32's bits. */
+int llzs_fir_stream_fade_f32(int block, const float *hspec, int bank, const float *tw, float *ring, float *prev, const float *in,
+                             float *out, int channels, int nblk, int flush, long n_out, long in_pitch, long out_pitch, int P,
+                             int R, int head, const float *hspec_new, const unsigned char *fading, int fade_done,
+                             int fade_blocks, void *stream);
 /* the many-in, many-out stream convolver (fir_matrix.hip): llzs_fir_stream_f32's block, tw and packed spectra, with a delay line
  * per INPUT and a sum over inputs, as three launches ordered by the stream.  ring = [inputs][R][block] complex; prev_in /
  * prev_out = [inputs][block], two different buffers (the caller swaps them after a call); hspec = [outputs][inputs][P][block]

@@ -271,6 +271,21 @@ class FirStreamMC:
         check(self._L.llz_fir_stream_mc_set_taps(self.handle, first, taps.shape[0], taps.ctypes.data),
               "llz_fir_stream_mc_set_taps")
 
+    def fade_taps(self, first, taps, blocks):
+        """fade tap rows first .. first + count - 1 to `taps` ([count, flt_len], or [flt_len] for one row) over the next
+        `blocks` blocks, 1 .. 4096: a linear per-sample crossfade between the old and the new filter's outputs
+        (llz_fir_xfade_stream_mc).  Until the first of those blocks has run, further calls with the same `blocks` add rows"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps = taps[None, :] if taps.ndim == 1 else taps
+        if taps.ndim != 2 or taps.shape[1] != self.flt_len:
+            raise LlzError(f"FirStreamMC.fade_taps: taps must be [count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_fir_xfade_stream_mc(self.handle, first, taps.shape[0], taps.ctypes.data, blocks),
+              "llz_fir_xfade_stream_mc")
+
+    def fade_left(self):
+        """blocks of the fade still to run; 0: none in flight"""
+        return check(self._L.llz_fir_xfade_stream_mc_left(self.handle), "llz_fir_xfade_stream_mc_left")
+
     def filter(self, x, out):
         """x, out: [channels, frame_len] float32 (torch device tensors or numpy). Returns out."""
         count = self.channels * self.frame_len
