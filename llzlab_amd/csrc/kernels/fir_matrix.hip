@@ -167,14 +167,6 @@ k_fir_matrix_inv(const float2 *__restrict__ Y, const float2 *__restrict__ tw, fl
 
 constexpr unsigned GRID_YZ_MAX = 65535u;
 
-bool matrix_log2(int block, int *log2b)
-{
-    int l = 0;
-    while ((1 << l) < block) l++;
-    *log2b = l;
-    return l >= 6 && l <= 12 && (1 << l) == block;
-}
-
 template <int LOG2B>
 int fwd_launch(const float *in, const float2 *tw, float2 *ring, const float *prev_in, float *prev_out, const matrix_geom &G,
                hipStream_t st)
@@ -203,17 +195,6 @@ int inv_launch(const float2 *Y, const float2 *tw, float *out, const matrix_geom 
     return LLZ_OK;
 }
 
-#define MATRIX_DISPATCH(log2b, call)                                                                                             \
-    switch (log2b) {                                                                                                             \
-    case 6: return call(6);                                                                                                      \
-    case 7: return call(7);                                                                                                      \
-    case 8: return call(8);                                                                                                      \
-    case 9: return call(9);                                                                                                      \
-    case 10: return call(10);                                                                                                    \
-    case 11: return call(11);                                                                                                    \
-    default: return call(12);                                                                                                    \
-    }
-
 // what the three entries share: the shape within the kernels' index ranges and the grid limits
 bool matrix_shape_ok(int log2ok, int inputs, int outputs, int nblk, int P, int R, int head)
 {
@@ -231,7 +212,7 @@ extern "C" int llzs_fir_matrix_fwd_f32(int block, const float *tw, float *ring, 
                                        void *stream)
 {
     int log2b;
-    const bool ok = matrix_log2(block, &log2b);
+    const bool ok = stream_log2(block, &log2b);
     if (!matrix_shape_ok(ok, inputs, 1, nblk, 1, R, head) || !tw || !ring || !prev_in ||
         (!flush && (!in || !prev_out || prev_out == prev_in || in_pitch < (long)nblk * block)) || (flush && nblk != 1)) {
         llzs_set_error("fir_matrix_fwd_f32: bad arguments (block=%d inputs=%d nblk=%d R=%d head=%d flush=%d)", block, inputs, nblk,
@@ -244,7 +225,7 @@ extern "C" int llzs_fir_matrix_fwd_f32(int block, const float *tw, float *ring, 
     float2 *rg = reinterpret_cast<float2 *>(ring);
     hipStream_t st = as_stream(stream);
 #define FWD(L) fwd_launch<L>(in, W, rg, prev_in, prev_out, G, st)
-    MATRIX_DISPATCH(log2b, FWD)
+    STREAM_DISPATCH(log2b, FWD)
 #undef FWD
 }
 
@@ -257,7 +238,7 @@ extern "C" int llzs_fir_matrix_mac_f32(int block, const float *hspec, const floa
                                        int groups, int group_size, void *stream)
 {
     int log2b;
-    const bool ok = matrix_log2(block, &log2b);
+    const bool ok = stream_log2(block, &log2b);
     if (!matrix_shape_ok(ok, inputs, outputs, nblk, P, R, head) || !hspec || !ring || !conn || !ypart || groups < 1 ||
         group_size < 1 || (long)groups * group_size < inputs || (long)(groups - 1) * group_size >= inputs ||
         (unsigned)groups * (unsigned)(block / 64) > GRID_YZ_MAX || j0 < 0 || (!flush && j0 != 0) ||
@@ -273,7 +254,7 @@ extern "C" int llzs_fir_matrix_mac_f32(int block, const float *hspec, const floa
     float2 *Y = reinterpret_cast<float2 *>(ypart);
     hipStream_t st = as_stream(stream);
 #define MAC(L) mac_launch<L>(H, rg, conn, Y, G, st)
-    MATRIX_DISPATCH(log2b, MAC)
+    STREAM_DISPATCH(log2b, MAC)
 #undef MAC
 }
 
@@ -283,7 +264,7 @@ extern "C" int llzs_fir_matrix_inv_f32(int block, const float *ypart, const floa
                                        int groups, long n_out, long out_pitch, void *stream)
 {
     int log2b;
-    const bool ok = matrix_log2(block, &log2b);
+    const bool ok = stream_log2(block, &log2b);
     if (!matrix_shape_ok(ok, 1, outputs, nblk, 1, 1, 0) || !ypart || !tw || !out || groups < 1 || n_out < 1 ||
         n_out > (long)nblk * block || out_pitch < n_out) {
         llzs_set_error("fir_matrix_inv_f32: bad arguments (block=%d outputs=%d nblk=%d groups=%d n_out=%ld out_pitch=%ld)", block,
@@ -295,6 +276,6 @@ extern "C" int llzs_fir_matrix_inv_f32(int block, const float *ypart, const floa
     const float2 *Y = reinterpret_cast<const float2 *>(ypart), *W = reinterpret_cast<const float2 *>(tw);
     hipStream_t st = as_stream(stream);
 #define INV(L) inv_launch<L>(Y, W, out, G, st)
-    MATRIX_DISPATCH(log2b, INV)
+    STREAM_DISPATCH(log2b, INV)
 #undef INV
 }

@@ -38,14 +38,6 @@
 
 namespace {
 
-struct stream_geom {
-    int P, R, head;             // partitions, ring slots, the slot block 0 of this launch writes
-    int nblk;                   // blocks of this launch (a flush: zero blocks, one per workgroup)
-    int flush;
-    long n_out;                 // samples per channel to store: <= nblk B
-    long in_pitch, out_pitch;
-};
-
 // K4f: workgroup c (a flush: (c, block)) -> channel c.  tw: [B / 2] W_B^m, then [B] split twiddles W_N^bitrev(i) by position.
 // BANK: H is [channels][P][B], channel c's own spectra
 template <int LOG2B, bool BANK>
@@ -85,15 +77,14 @@ k_fir_stream(const float *__restrict__ in, float *__restrict__ out, const float2
             lf[B + t] = G.flush ? 0.f : irow[(size_t)j * B + t];
         }
         part_fft_dif<LOG2B, T>(lds, tw, tid);
-        // split: bin k of the real transform (doubled) = (Z_k + conj Z_{B-k}) + W_N^k (-j) (Z_k - conj Z_{B-k})
+        // forward split (stream_bins.hpp) into the bins this thread owns
         float2 x[M];
 #pragma unroll
         for (int m = 0; m < M; m++) {
             const int i = pos[m / V] + m % V;
-            const float2 a = lds[i], b = c_conj(lds[mirror<LOG2B>(i)]);
-            const float2 e = c_add(a, b), d = c_sub(a, b);
-            x[m] = c_add(e, c_mul<false>(float2{d.y, -d.x}, spl[i]));
-            if (m == 0 && first) x[m] = float2{2.f * (a.x + a.y), 2.f * (a.x - a.y)};
+            const float2 a = lds[i];
+            x[m] = split_fwd(a, lds[mirror<LOG2B>(i)], spl[i]);
+            if (m == 0 && first) x[m] = split_fwd0(a);
         }
         float2 *slot = rc + (size_t)cur * B;
         const float2 *h0 = hc + (size_t)p0 * B;
@@ -131,7 +122,7 @@ k_fir_stream(const float *__restrict__ in, float *__restrict__ out, const float2
 #pragma unroll 1
         for (; p < G.P; p++) step(p);
 
-        // inverse split through LDS: Z''_k = (Y_k + conj Y_{B-k}) + j conj(W_N^k) (Y_k - conj Y_{B-k})
+        // inverse split (stream_bins.hpp) through LDS
         __syncthreads();                                    // every mirror read of the forward split is done
 #pragma unroll
         for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &acc[g * V]);
@@ -140,10 +131,8 @@ k_fir_stream(const float *__restrict__ in, float *__restrict__ out, const float2
 #pragma unroll
         for (int m = 0; m < M; m++) {
             const int i = pos[m / V] + m % V;
-            const float2 a = acc[m], b = c_conj(lds[mirror<LOG2B>(i)]);
-            const float2 e = c_add(a, b), d = c_sub(a, b);
-            zz[m] = c_add(e, c_mul<true>(float2{-d.y, d.x}, spl[i]));
-            if (m == 0 && first) zz[m] = float2{a.x + a.y, a.x - a.y};
+            zz[m] = split_inv(acc[m], lds[mirror<LOG2B>(i)], spl[i]);
+            if (m == 0 && first) zz[m] = split_inv0(acc[m]);
         }
         __syncthreads();
 #pragma unroll
@@ -182,29 +171,19 @@ extern "C" int llzs_fir_stream_f32(int block, const float *hspec, int bank, cons
                                    const float *in, float *out, int channels, int nblk, int flush, long n_out, long in_pitch,
                                    long out_pitch, int P, int R, int head, void *stream)
 {
-    int log2b = 0;
-    while ((1 << log2b) < block) log2b++;
-    if (log2b < 6 || log2b > 12 || (1 << log2b) != block || !hspec || !tw || !ring || !prev || !out || channels < 1 ||
-        channels > 65535 || nblk < 1 || P < 1 || R < P || head < 0 || head >= R || n_out < 1 || n_out > (long)nblk * block ||
-        out_pitch < n_out || (!flush && (!in || in_pitch < (long)nblk * block)) || (flush && (nblk > 65535 || nblk > P))) {
+    int log2b;
+    const bool ok = stream_log2(block, &log2b);
+    const stream_geom G = {P, R, head, nblk, flush ? 1 : 0, n_out, in_pitch, out_pitch};
+    if (!stream_launch_ok(G, ok, block, channels, hspec && tw && ring && prev && out, in)) {
         llzs_set_error("fir_stream_f32: bad arguments (block=%d channels=%d nblk=%d P=%d R=%d head=%d n_out=%ld)", block, channels,
                        nblk, P, R, head, n_out);
         return LLZ_ERR_ARG;
     }
-    stream_geom G;
-    G.P = P; G.R = R; G.head = head; G.nblk = nblk; G.flush = flush ? 1 : 0;
-    G.n_out = n_out; G.in_pitch = in_pitch; G.out_pitch = out_pitch;
     const float2 *H = reinterpret_cast<const float2 *>(hspec), *W = reinterpret_cast<const float2 *>(tw);
     float2 *rg = reinterpret_cast<float2 *>(ring);
     hipStream_t st = as_stream(stream);
     const bool bk = bank != 0;
-    switch (log2b) {
-    case 6: return stream_launch<6>(bk, in, out, H, W, rg, prev, G, channels, st);
-    case 7: return stream_launch<7>(bk, in, out, H, W, rg, prev, G, channels, st);
-    case 8: return stream_launch<8>(bk, in, out, H, W, rg, prev, G, channels, st);
-    case 9: return stream_launch<9>(bk, in, out, H, W, rg, prev, G, channels, st);
-    case 10: return stream_launch<10>(bk, in, out, H, W, rg, prev, G, channels, st);
-    case 11: return stream_launch<11>(bk, in, out, H, W, rg, prev, G, channels, st);
-    default: return stream_launch<12>(bk, in, out, H, W, rg, prev, G, channels, st);
-    }
+#define PLAIN(L) stream_launch<L>(bk, in, out, H, W, rg, prev, G, channels, st)
+    STREAM_DISPATCH(log2b, PLAIN)
+#undef PLAIN
 }

@@ -4,11 +4,12 @@
 // input and blends the two outputs sample by sample in the time domain (a ramp is not a per-bin operation):
 //     y[n] = fmaf(w[n], y_new[n] - y_old[n], y_old[n]),   w[n] = (float)n / (float)(F B), n counted from the fade's first sample.
 // The delay line holds INPUT spectra, so both filters share the forward transform and every ring slot: a fading block costs a
-// second product sum and a second inverse transform.  fir_stream.hip is not touched: calls with no fade in flight run it.
+// second product sum and a second inverse transform.  Calls with no fade in flight run k_fir_stream (fir_stream.hip); the two
+// kernels share the split steps and the launch preamble of stream_bins.hpp.
 //
 // Choices, with their reasons:
 //   * A workgroup-uniform branch per block: a row that does not fade, and a block of a fading row past the fade's end, go through
-//     the plain chain (bin_mac over p ascending from a zero accumulator, the split steps of k_fir_stream operation for operation:
+//     the plain chain (bin_mac over p ascending from a zero accumulator as in k_fir_stream, and the split steps it calls too:
 //     every operation there is an add, a subtract, a product that feeds an fma as its addend, or an explicit fma, so there is
 //     nothing for the compiler to contract differently) against the old spectra or, past the end, the new ones: the bits of
 //     k_fir_stream.  The old filter's half of a fading block is that same chain.
@@ -29,13 +30,8 @@
 
 namespace {
 
-struct fade_geom {
-    int P, R, head;             // partitions, ring slots, the slot block 0 of this launch writes
-    int nblk;                   // blocks of this launch (a flush: zero blocks, one per workgroup)
-    int flush;
+struct fade_geom : stream_geom {
     int fade_done, fade_blocks; // block j of this launch is block fade_done + j of the fade; from fade_blocks on: new taps alone
-    long n_out;                 // samples per channel to store: <= nblk B
-    long in_pitch, out_pitch;
 };
 
 // workgroup c (a flush: (c, block)) -> channel c.  H: the handle's spectra, Hn: the new taps' (same layout; only fading rows are
@@ -80,15 +76,14 @@ k_fir_stream_fade(const float *__restrict__ in, float *__restrict__ out, const f
             lf[B + t] = G.flush ? 0.f : irow[(size_t)j * B + t];
         }
         part_fft_dif<LOG2B, T>(lds, tw, tid);
-        // split: bin k of the real transform (doubled) = (Z_k + conj Z_{B-k}) + W_N^k (-j) (Z_k - conj Z_{B-k})
+        // forward split (stream_bins.hpp) into the bins this thread owns
         float2 x[M];
 #pragma unroll
         for (int m = 0; m < M; m++) {
             const int i = pos[m / V] + m % V;
-            const float2 a = lds[i], b = c_conj(lds[mirror<LOG2B>(i)]);
-            const float2 e = c_add(a, b), d = c_sub(a, b);
-            x[m] = c_add(e, c_mul<false>(float2{d.y, -d.x}, spl[i]));
-            if (m == 0 && first) x[m] = float2{2.f * (a.x + a.y), 2.f * (a.x - a.y)};
+            const float2 a = lds[i];
+            x[m] = split_fwd(a, lds[mirror<LOG2B>(i)], spl[i]);
+            if (m == 0 && first) x[m] = split_fwd0(a);
         }
         if (!G.flush) {
             float2 *slot = rc + (size_t)cur * B;
@@ -184,10 +179,8 @@ k_fir_stream_fade(const float *__restrict__ in, float *__restrict__ out, const f
 #pragma unroll
             for (int m = 0; m < M; m++) {
                 const int i = pos[m / V] + m % V;
-                const float2 a = acc[m], b = c_conj(lds[mirror<LOG2B>(i)]);
-                const float2 e = c_add(a, b), d = c_sub(a, b);
-                zz[m] = c_add(e, c_mul<true>(float2{-d.y, d.x}, spl[i]));
-                if (m == 0 && first) zz[m] = float2{a.x + a.y, a.x - a.y};
+                zz[m] = split_inv(acc[m], lds[mirror<LOG2B>(i)], spl[i]);
+                if (m == 0 && first) zz[m] = split_inv0(acc[m]);
             }
             __syncthreads();
 #pragma unroll
@@ -283,32 +276,21 @@ extern "C" int llzs_fir_stream_fade_f32(int block, const float *hspec, int bank,
                                         long out_pitch, int P, int R, int head, const float *hspec_new,
                                         const unsigned char *fading, int fade_done, int fade_blocks, void *stream)
 {
-    int log2b = 0;
-    while ((1 << log2b) < block) log2b++;
-    if (log2b < 6 || log2b > 12 || (1 << log2b) != block || !hspec || !hspec_new || !fading || !tw || !ring || !prev || !out ||
-        channels < 1 || channels > 65535 || nblk < 1 || P < 1 || R < P || head < 0 || head >= R || n_out < 1 ||
-        n_out > (long)nblk * block || out_pitch < n_out || (!flush && (!in || in_pitch < (long)nblk * block)) ||
-        (flush && (nblk > 65535 || nblk > P)) || fade_blocks < 1 || fade_blocks > 4096 || fade_done < 0 || fade_done >= fade_blocks) {
+    int log2b;
+    const bool ok = stream_log2(block, &log2b);
+    fade_geom G = {{P, R, head, nblk, flush ? 1 : 0, n_out, in_pitch, out_pitch}, fade_done, fade_blocks};
+    if (!stream_launch_ok(G, ok, block, channels, hspec && hspec_new && fading && tw && ring && prev && out, in) ||
+        fade_blocks < 1 || fade_blocks > 4096 || fade_done < 0 || fade_done >= fade_blocks) {
         llzs_set_error("fir_stream_fade_f32: bad arguments (block=%d channels=%d nblk=%d P=%d R=%d head=%d n_out=%ld fade %d of %d)",
                        block, channels, nblk, P, R, head, n_out, fade_done, fade_blocks);
         return LLZ_ERR_ARG;
     }
-    fade_geom G;
-    G.P = P; G.R = R; G.head = head; G.nblk = nblk; G.flush = flush ? 1 : 0;
-    G.fade_done = fade_done; G.fade_blocks = fade_blocks;
-    G.n_out = n_out; G.in_pitch = in_pitch; G.out_pitch = out_pitch;
     const float2 *H = reinterpret_cast<const float2 *>(hspec), *Hn = reinterpret_cast<const float2 *>(hspec_new);
     const float2 *W = reinterpret_cast<const float2 *>(tw);
     float2 *rg = reinterpret_cast<float2 *>(ring);
     hipStream_t st = as_stream(stream);
     const bool bk = bank != 0;
-    switch (log2b) {
-    case 6: return fade_launch<6>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    case 7: return fade_launch<7>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    case 8: return fade_launch<8>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    case 9: return fade_launch<9>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    case 10: return fade_launch<10>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    case 11: return fade_launch<11>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    default: return fade_launch<12>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st);
-    }
+#define FADE(L) fade_launch<L>(bk, in, out, H, Hn, fading, W, rg, prev, G, channels, st)
+    STREAM_DISPATCH(log2b, FADE)
+#undef FADE
 }

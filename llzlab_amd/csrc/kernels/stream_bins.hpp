@@ -1,10 +1,9 @@
-// stream_bins.hpp -- what the two frequency-domain delay lines share: fir_stream.hip (K4f) and fir_matrix.hip (K4g).  The packed
-// half-spectrum of a real block pair (B bins by position, position i holds bin bitrev(i), position 0 packs DC and Nyquist), its
-// product step, the loads and stores of neighbouring bins, and the two split steps between the B-point complex transform
-// (part_fft.hpp) and that half-spectrum.  The product step, mirror and the loads and stores are used by both files;
-// k_fir_stream keeps its own in-line copy of the two split steps (as functions they changed its register assignment), which
-// split_fwd / split_inv below restate operation for operation, so that one path of the matrix form gives the stream
-// convolver's values.
+// stream_bins.hpp -- what the frequency-domain delay lines share: fir_stream.hip (K4f), fir_stream_fade.hip (K4f while taps
+// fade) and fir_matrix.hip (K4g).  The packed half-spectrum of a real block pair (B bins by position, position i holds bin
+// bitrev(i), position 0 packs DC and Nyquist), its product step, the loads and stores of neighbouring bins, the two split
+// steps between the B-point complex transform (part_fft.hpp) and that half-spectrum -- called by all three files, so that a
+// block of the fade kernel that does not fade, and one path of the matrix form, give the stream convolver's values -- and
+// the launch preamble of their five launchers: block size, dispatch over the seven sizes, K4f's geometry and argument check.
 #pragma once
 #include "common.hpp"
 #include "part_fft.hpp"
@@ -73,5 +72,45 @@ __device__ __forceinline__ float2 split_inv0(float2 a) { return float2{a.x + a.y
 // one sample of a crossfade between two filters' outputs (fir_stream_fade.hip): w = 0 gives y_old to the bit, equal outputs give
 // that output to the bit at any w
 __device__ __forceinline__ float fade_blend(float w, float y_old, float y_new) { return __builtin_fmaf(w, y_new - y_old, y_old); }
+
+// ------------------------------------------------------------------------------------------------ the launch preamble
+// block = 2^*log2b, 64 .. 4096
+bool stream_log2(int block, int *log2b)
+{
+    int l = 0;
+    while ((1 << l) < block) l++;
+    *log2b = l;
+    return l >= 6 && l <= 12 && (1 << l) == block;
+}
+
+// `return call(LOG2B);` for the block size; call: a macro of one argument
+#define STREAM_DISPATCH(log2b, call)                                                                                             \
+    switch (log2b) {                                                                                                             \
+    case 6: return call(6);                                                                                                      \
+    case 7: return call(7);                                                                                                      \
+    case 8: return call(8);                                                                                                      \
+    case 9: return call(9);                                                                                                      \
+    case 10: return call(10);                                                                                                    \
+    case 11: return call(11);                                                                                                    \
+    default: return call(12);                                                                                                    \
+    }
+
+// one K4f launch, plain or fading (fir_stream_fade.hip derives its own from it)
+struct stream_geom {
+    int P, R, head;             // partitions, ring slots, the slot block 0 of this launch writes
+    int nblk;                   // blocks of this launch (a flush: zero blocks, one per workgroup)
+    int flush;
+    long n_out;                 // samples per channel to store: <= nblk B
+    long in_pitch, out_pitch;
+};
+
+// G and the buffers of a K4f launch within the kernels' index ranges and the grid limits; in: null only for a flush
+bool stream_launch_ok(const stream_geom &G, bool log2ok, int block, int channels, bool buffers, const float *in)
+{
+    const long n = (long)G.nblk * block;
+    return log2ok && buffers && channels >= 1 && channels <= 65535 && G.nblk >= 1 && G.P >= 1 && G.R >= G.P && G.head >= 0 &&
+           G.head < G.R && G.n_out >= 1 && G.n_out <= n && G.out_pitch >= G.n_out && (G.flush || (in && G.in_pitch >= n)) &&
+           (!G.flush || (G.nblk <= 65535 && G.nblk <= G.P));
+}
 
 } // namespace

@@ -43,7 +43,7 @@ def test_longest_filter(dev, oracle):
 
 
 # ------------------------------------------------------------------------------------------------ 2. bit pins
-@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300)])
+@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300), (1024, 1300), (2048, 2300)])
 def test_bit_pins(dev, oracle, block, T):
     """the first faded sample equals the old-taps handle's; a fade to equal taps is bit-equal to no fade; every block after the
     fade is bit-equal to a handle given set_taps(new) at the block where the fade ends"""

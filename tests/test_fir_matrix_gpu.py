@@ -75,7 +75,7 @@ def test_ring_wraps_and_call_grouping_keeps_the_bits(dev, oracle):
 
 
 # ------------------------------------------------------------------------------------------------ 3. paths
-@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300)])
+@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300), (2048, 2300)])
 def test_one_path_at_a_time_is_the_stream_convolver(dev, oracle, block, T):
     """3 -> 2, six distinct dense tap sets: with every input but i zeroed, output o equals -- value for value -- a one-channel
     FirStreamMC with h[o][i] on x_i, frames and flush; held against h[i'][o'] of the transposed indexing it misses the gate"""

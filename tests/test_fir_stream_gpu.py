@@ -63,7 +63,7 @@ def test_ring_wraps_and_call_grouping_keeps_the_bits(dev, oracle):
 
 
 # ------------------------------------------------------------------------------------------------ 3. isolation
-@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300)])
+@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300), (2048, 2300)])
 def test_channels_are_independent_to_the_bit(dev, oracle, block, T):
     """run B = run A with channels 1 and 4 zeroed and channels 2 and 5 scaled by 2^20: channels 0 and 3 keep their bits, the
     zeroed ones give exactly 0.0, the scaled ones 2^20 times run A bit for bit; run A on a fresh handle repeats its bits"""
@@ -84,7 +84,7 @@ def test_channels_are_independent_to_the_bit(dev, oracle, block, T):
         assert np.array_equal(sc.bits(ya[c] * np.float32(2.0 ** 20)), sc.bits(yb[c])), f"channel {c}: not 2^20 times run A"
 
 
-@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300)])
+@pytest.mark.parametrize("block,T", [(64, 199), (512, 1300), (2048, 2300)])
 def test_rows_that_differ_and_rows_that_are_equal(dev, oracle, block, T):
     """a tap row per channel, every row different: each channel is held to its own taps, and its neighbour's taps miss the
     gate; rows that are all equal give the bits of the shared handle"""
