@@ -266,7 +266,8 @@ int llz_fir_matrix_mc_reset(unsigned long handle);
  * [out_count][in_count][flt_len].  A range outside the matrix is refused.  Ordered on the handle's stream behind the calls
  * already issued, the connection table too: a path is connected from then on exactly when its new taps are not all zero.  The
  * delay lines are kept, and they hold INPUT spectra: from the next call on the output is the new taps applied to the whole
- * input so far (no crossfade). */
+ * input so far (no crossfade: llz_fir_xfade_matrix_mc below fades instead, and while its fade is pending or in flight this
+ * call is refused with LLZ_ERR_ARG, the message giving the blocks left). */
 int llz_fir_matrix_mc_set_taps(unsigned long handle, int out_first, int out_count, int in_first, int in_count, const float *taps);
 /* out = {N = 2 block, P = ceil(flt_len / block), ring slots R, blocks per call k, input groups G, connected paths}; nothing is
  * launched */
@@ -274,6 +275,42 @@ int llz_fir_matrix_mc_plan(unsigned long handle, int out[6]);
 int llz_fir_matrix_mc_flt_len(unsigned long handle);
 /* stream: a hipStream_t passed as void* (NULL = default stream) */
 int llz_fir_matrix_mc_set_stream(unsigned long handle, void *stream);
+/* A click-free change of paths: the sub-matrix [out_first, out_first+out_count) x [in_first, in_first+in_count) (taps: HOST
+ * [out_count][in_count][flt_len], ranges as _set_taps takes them) FADES to the new taps over fade_blocks blocks, 1..4096: part 5's
+ * fade carried to outputs that sum inputs.  An output FADES when at least one of its paths is in the fade.  The fade starts with
+ * the first block processed after the call.  With F = fade_blocks, B = block and n = 0 .. F B - 1 counting samples from that
+ * block's first one, a fading output o is
+ *     y_o[n] = fmaf(w[n], y_new_o[n] - y_old_o[n], y_old_o[n]),    w[n] = (float)n / (float)(F B), correctly rounded
+ * (F B <= 2^24, so n is exact in float32), where y_old_o is exactly what llz_fir_matrix_mc computes with the row's taps as they
+ * were -- the same G groups, the same chain order -- and y_new_o the same with the faded paths replaced; both run on the one
+ * set of delay lines, which hold input spectra (one walk of the rings serves both sums).  The blend is per OUTPUT, after the sum
+ * over inputs, not per path.  From sample F B on the output is y_new alone and the handle is in exactly the state
+ * _set_taps(new) would have left it in: the spectra, the connection table and _plan's out[5].  For finite data: w[0] = 0, so the
+ * first faded sample has the old filter's bits; a fade to equal taps is bit-equal to no fade; an output with no path in the fade
+ * keeps its bits throughout; and the weight depends on the sample's index within the fade alone, so a fade spans calls (a call
+ * of k blocks may hold its start and its end, blocks past the end are plain new-taps blocks) and how calls group the blocks
+ * changes no bit.
+ * The connection follows the tap set: the old sum skips the paths whose old taps are all zero, the new sum those whose new taps
+ * are.  A path fading FROM all-zero taps is a source fading in; a path fading TO all-zero taps is a source fading out, and it is
+ * unconnected and free of traffic once the fade is over.  While the fade runs a NaN or an Inf of x_i reaches y_o if (o, i) is
+ * connected under EITHER tap set.  _plan's out[5], while a fade is pending or in flight, counts the paths connected under the
+ * old or the new taps -- what a fading block reads -- and the new taps' count afterwards.
+ * ONE fade at a time per handle: a call while one is in flight is refused -- except that until the first block of a pending
+ * fade has been processed, further calls with the same fade_blocks add or replace paths of that fade (a later call to the same
+ * path replaces the earlier one), so that a renderer can fade columns that are not neighbours together.  The new paths' spectra
+ * go into a second buffer of the tap spectra's size and the new sums' partial spectra into a second scratch, both allocated at
+ * the first fade and kept (a failed allocation names the bytes); the spectra are built as _set_taps builds them, on the handle's
+ * stream behind the calls already issued.  A handle that never fades allocates nothing of this and launches its three kernels
+ * untouched.  Refused, each with a message of its own, none of them starting or altering a fade: a bad handle, NULL taps, an
+ * output range outside the handle, an input range outside it, fade_blocks outside 1..4096, a fade already in flight (a pending
+ * one with another fade_blocks gets a hint).  While a fade is pending or in flight _set_taps is refused (LLZ_ERR_ARG, the message
+ * gives the blocks left), _reset clears the delay lines and adopts the new taps at once, _flush goes on with the ramp through
+ * its zero blocks (flush block j is fade block done + j, across the flush's scratch passes too) and then leaves the handle reset
+ * WITH THE NEW TAPS adopted, and _uninit is clean.  Returns 0 or a negative LLZ_ERR_* code. */
+int llz_fir_xfade_matrix_mc(unsigned long handle, int out_first, int out_count, int in_first, int in_count, const float *taps,
+                            int fade_blocks);
+/* the blocks of the fade still to run (fade_blocks while it is pending), 0 when none is in flight; LLZ_ERR_ARG for a bad handle */
+int llz_fir_xfade_matrix_mc_left(unsigned long handle);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,8 @@ def lib():
     sig("llz_fir_matrix_mc_plan", i, ul, C.POINTER(C.c_int))
     sig("llz_fir_matrix_mc_flt_len", i, ul)
     sig("llz_fir_matrix_mc_set_stream", i, ul, vp)
+    sig("llz_fir_xfade_matrix_mc", i, ul, i, i, i, i, vp, i)
+    sig("llz_fir_xfade_matrix_mc_left", i, ul)
     # llz_iir.h
     sig("llz_iir_filter_init", ul, i, dp, i, dp)
     sig("llz_iir_filter_uninit", None, ul)

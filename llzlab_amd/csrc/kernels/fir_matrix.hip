@@ -25,21 +25,9 @@
 #include "common.hpp"
 #include "part_fft.hpp"
 #include "stream_bins.hpp"
+#include "fir_matrix.hpp"
 
 namespace {
-
-struct matrix_geom {
-    int inputs, outputs, P, R, head;
-    int nblk;                   // blocks of this launch
-    int flush, j0;              // a flush in several passes: the block of the flush that is block 0 of this launch
-    int G, gsize;               // input groups, inputs per group (the last group may hold fewer)
-    long n_out;                 // samples per output to store: <= nblk B
-    long in_pitch, out_pitch;
-};
-
-// bins per thread and per workgroup of the product
-constexpr int mac_v(int log2b) { return log2b >= 9 ? 2 : 1; }
-constexpr int mac_tiles(int log2b) { return (1 << log2b) / (stream_threads(log2b) * mac_v(log2b)); }
 
 // 1. workgroup (i, j): the spectrum of input i's block pair (j - 1, j) into its ring slot
 template <int LOG2B>
@@ -165,8 +153,6 @@ k_fir_matrix_inv(const float2 *__restrict__ Y, const float2 *__restrict__ tw, fl
     }
 }
 
-constexpr unsigned GRID_YZ_MAX = 65535u;
-
 template <int LOG2B>
 int fwd_launch(const float *in, const float2 *tw, float2 *ring, const float *prev_in, float *prev_out, const matrix_geom &G,
                hipStream_t st)
@@ -193,13 +179,6 @@ int inv_launch(const float2 *Y, const float2 *tw, float *out, const matrix_geom 
     hipLaunchKernelGGL((k_fir_matrix_inv<LOG2B>), grid, wg, 0, st, Y, tw, out, G);
     LLZ_LAUNCH_CHECK("k_fir_matrix_inv");
     return LLZ_OK;
-}
-
-// what the three entries share: the shape within the kernels' index ranges and the grid limits
-bool matrix_shape_ok(int log2ok, int inputs, int outputs, int nblk, int P, int R, int head)
-{
-    return log2ok && inputs >= 1 && inputs <= 4096 && outputs >= 1 && outputs <= 4096 && nblk >= 1 &&
-           (unsigned)nblk <= GRID_YZ_MAX && P >= 1 && R >= P && head >= 0 && head < R;
 }
 
 } // namespace
@@ -239,10 +218,8 @@ extern "C" int llzs_fir_matrix_mac_f32(int block, const float *hspec, const floa
 {
     int log2b;
     const bool ok = stream_log2(block, &log2b);
-    if (!matrix_shape_ok(ok, inputs, outputs, nblk, P, R, head) || !hspec || !ring || !conn || !ypart || groups < 1 ||
-        group_size < 1 || (long)groups * group_size < inputs || (long)(groups - 1) * group_size >= inputs ||
-        (unsigned)groups * (unsigned)(block / 64) > GRID_YZ_MAX || j0 < 0 || (!flush && j0 != 0) ||
-        (flush && (long)j0 + nblk > P)) {
+    if (!matrix_shape_ok(ok, inputs, outputs, nblk, P, R, head) || !hspec || !ring || !conn || !ypart ||
+        !matrix_groups_ok(block, inputs, nblk, flush, j0, P, groups, group_size)) {
         llzs_set_error("fir_matrix_mac_f32: bad arguments (block=%d inputs=%d outputs=%d nblk=%d j0=%d P=%d R=%d head=%d groups=%d x "
                        "%d)", block, inputs, outputs, nblk, j0, P, R, head, groups, group_size);
         return LLZ_ERR_ARG;

@@ -198,6 +198,23 @@ int llzs_fir_matrix_mac_f32(int block, const float *hspec, const float *ring, co
                             void *stream);
 int llzs_fir_matrix_inv_f32(int block, const float *ypart, const float *tw, float *out, int outputs, int nblk, int groups,
                             long n_out, long out_pitch, void *stream);
+/* the product and the inverse of the matrix convolver with a fade between tap sets pending or in flight (fir_matrix_fade.hip;
+ * the forward launch does not change: the rings hold input spectra).  The plain launches' arguments, and: hspec_new / conn_new =
+ * the new taps' spectra and connection table laid out as hspec / conn, read only where fade[o][i] != 0; fade = [outputs][inputs]
+ * bytes, the paths in the fade; ofade = [outputs] bytes, the outputs with at least one such path; ypart_new = a second scratch
+ * of ypart's size; the fade's position: block j of the launch is block fade_done + j0 + j of fade_blocks (1 .. 4096, 0 <=
+ * fade_done < fade_blocks; the inverse takes j0 for it, the same value as its product).  An output marked in ofade: inside the
+ * fade ypart holds the old taps' partial sums, ypart_new the new taps' (one walk of the rings for both) and its samples are
+ * fmaf(w, y_new - y_old, y_old), w = (float)n / (float)(fade_blocks block), n counted from the fade's first sample; from block
+ * fade_blocks on it is the new taps' output alone.  Outputs not marked get the plain launches' bits. */
+int llzs_fir_matrix_mac_fade_f32(int block, const float *hspec, const float *hspec_new, const float *ring,
+                                 const unsigned char *conn, const unsigned char *conn_new, const unsigned char *fade,
+                                 const unsigned char *ofade, float *ypart, float *ypart_new, int inputs, int outputs, int nblk,
+                                 int flush, int j0, int P, int R, int head, int groups, int group_size, int fade_done,
+                                 int fade_blocks, void *stream);
+int llzs_fir_matrix_inv_fade_f32(int block, const float *ypart, const float *ypart_new, const unsigned char *ofade,
+                                 const float *tw, float *out, int outputs, int nblk, int j0, int groups, long n_out,
+                                 long out_pitch, int fade_done, int fade_blocks, void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

@@ -351,6 +351,22 @@ class FirMatrixMC:
         check(self._L.llz_fir_matrix_mc_set_taps(self.handle, out_first, taps.shape[0], in_first, taps.shape[1], taps.ctypes.data),
               "llz_fir_matrix_mc_set_taps")
 
+    def fade_taps(self, out_first, in_first, taps, blocks):
+        """fade the paths [out_first, +out_count) x [in_first, +in_count) to `taps` ([out_count, in_count, flt_len], or [flt_len]
+        for one path) over the next `blocks` blocks, 1 .. 4096: a linear per-sample crossfade between the old and the new
+        matrix's outputs, per output after the sum over inputs (llz_fir_xfade_matrix_mc).  Until the first of those blocks has
+        run, further calls with the same `blocks` add paths"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps = taps[None, None, :] if taps.ndim == 1 else taps
+        if taps.ndim != 3 or taps.shape[2] != self.flt_len:
+            raise LlzError(f"FirMatrixMC.fade_taps: taps must be [out_count, in_count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_fir_xfade_matrix_mc(self.handle, out_first, taps.shape[0], in_first, taps.shape[1], taps.ctypes.data,
+                                              blocks), "llz_fir_xfade_matrix_mc")
+
+    def fade_left(self):
+        """blocks of the fade still to run; 0: none in flight"""
+        return check(self._L.llz_fir_xfade_matrix_mc_left(self.handle), "llz_fir_xfade_matrix_mc_left")
+
     def filter(self, x, out):
         """x: [inputs, frame_len], out: [outputs, frame_len] float32 (torch device tensors or numpy). Returns out."""
         check(self._L.llz_fir_matrix_mc(self.handle, _typed(x, "float32", self.inputs * self.frame_len, "FirMatrixMC.filter x"),
