@@ -190,8 +190,8 @@ int llz_fir_stream_mc_reset(unsigned long handle);
 /* replace tap rows [first, first+count) between calls; taps: HOST [count][flt_len].  rows == channels: any range inside
  * [0, channels); rows == 1: only first 0, count 1.  Ordered on the handle's stream behind the calls already issued.  The
  * delay line is kept, and it holds INPUT spectra: from the next call on the output is the new taps applied to the whole
- * input so far -- a step in the output; llz_fir_xfade_stream_mc below fades instead.  While a fade is in flight the call is
- * refused (LLZ_ERR_ARG, the message gives the blocks left). */
+ * input so far -- a step in the output; llz_fir_xfade_stream_mc below fades instead.  While a fade is pending or in flight the
+ * call is refused (LLZ_ERR_ARG, the message gives the blocks left). */
 int llz_fir_stream_mc_set_taps(unsigned long handle, int first, int count, const float *taps);
 /* out = {N = 2 block, P = ceil(flt_len / block), ring slots R, blocks per call k}; nothing is launched */
 int llz_fir_stream_mc_plan(unsigned long handle, int out[4]);
@@ -214,11 +214,13 @@ int llz_fir_stream_mc_set_stream(unsigned long handle, void *stream);
  * rows that are not neighbours together.  The new rows' spectra go into a second buffer of rows x P x block x 8 bytes,
  * allocated at the first fade and kept (a failed allocation names the bytes), built on the handle's stream behind the calls
  * already issued.  Refused, each with a message of its own: a bad handle, NULL taps, rows outside the handle, fade_blocks
- * outside 1..4096, a fade already in flight.  While a fade is in flight _set_taps is refused, _reset clears the delay line and
- * adopts the new taps at once, and _flush goes on with the ramp through its zero blocks (flush block j is fade block done + j)
- * and then leaves the handle reset WITH THE NEW TAPS adopted.  Returns 0 or a negative LLZ_ERR_* code. */
+ * outside 1..4096, a fade already in flight (a pending one with another fade_blocks gets a hint).  While a fade is pending or in
+ * flight _set_taps is refused, _reset clears the delay line and adopts the new taps at once, and _flush goes on with the ramp
+ * through its zero blocks (flush block j is fade block done + j) and then leaves the handle reset WITH THE NEW TAPS adopted.
+ * Returns 0 or a negative LLZ_ERR_* code. */
 int llz_fir_xfade_stream_mc(unsigned long handle, int first, int count, const float *taps, int fade_blocks);
-/* the blocks of the fade still to run (fade_blocks while it is pending), 0 when none is in flight; LLZ_ERR_ARG for a bad handle */
+/* the blocks of the fade still to run (fade_blocks while it is pending), 0 when none is pending or in flight; LLZ_ERR_ARG for a
+ * bad handle */
 int llz_fir_xfade_stream_mc_left(unsigned long handle);
 
 /* ---- Part 6: the matrix convolver -- many inputs into many outputs, y_o = sum_i x_i * h_{o,i} -------------------------- */
@@ -309,7 +311,8 @@ int llz_fir_matrix_mc_set_stream(unsigned long handle, void *stream);
  * WITH THE NEW TAPS adopted, and _uninit is clean.  Returns 0 or a negative LLZ_ERR_* code. */
 int llz_fir_xfade_matrix_mc(unsigned long handle, int out_first, int out_count, int in_first, int in_count, const float *taps,
                             int fade_blocks);
-/* the blocks of the fade still to run (fade_blocks while it is pending), 0 when none is in flight; LLZ_ERR_ARG for a bad handle */
+/* the blocks of the fade still to run (fade_blocks while it is pending), 0 when none is pending or in flight; LLZ_ERR_ARG for a
+ * bad handle */
 int llz_fir_xfade_matrix_mc_left(unsigned long handle);
 
 #ifdef __cplusplus

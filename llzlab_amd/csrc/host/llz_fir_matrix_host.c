@@ -4,13 +4,14 @@
  * transforms.  The tap spectra and the twiddles come from the builders the stream convolver uses (llz_spectra.c), so one
  * path of the matrix is a stream channel.  Staging, pointer classification and error conventions are those of llz_fir_host.c.
  *
- * llz_fir_xfade_matrix_mc fades paths to new taps over fade_blocks blocks, as llz_fir_stream_host.c fades rows: the new paths'
- * spectra go into a second buffer of d_h's size, the paths, the outputs they end in and the new taps' connections are marked in
- * byte tables, and while the fade is pending or in flight the product and the inverse of every call go to fir_matrix_fade.hip
- * with the fade's position by value.  When the last faded block has been launched, or at a reset or a flush, the new paths are
- * adopted on the stream behind it (the buffers swapped when every path faded, else each run of faded paths copied into d_h, the
- * connection table updated) and the next call runs the three untouched kernels.  A handle that never fades allocates and
- * launches nothing of this. */
+ * llz_fir_xfade_matrix_mc fades paths to new taps over fade_blocks blocks.  The fade's state and rules are llz_fade.c's, with
+ * the paths in [outputs][inputs] order as its rows (the second spectra buffer, the table of fading paths, the refusals, the
+ * adoption); what is the handle's own is here: the second scratch of partial spectra, the tables of the outputs that fade and of
+ * the new taps' connections (taken by the handle only when all tables are up), and the connection table's update at adoption.
+ * While the fade is pending or in flight the product and the inverse of every call go to fir_matrix_fade.hip with the fade's
+ * position by value; after the launches of a call or of a whole flush the handle moves the fade on by the blocks launched and
+ * adopts at its end, so that the next call runs the three untouched kernels.  A handle that never fades allocates and launches
+ * nothing of this. */
 #include <stdlib.h>
 #include <string.h>
 #include "llz_host.h"
@@ -22,7 +23,6 @@
 #define FIRX_WG_TARGET 1024                     /* workgroups of the product asked for before the sum over inputs stays whole */
 #define FIRX_MAX_GROUPS 32
 #define FIRX_SCRATCH_BYTES ((size_t)64 << 20)   /* the partial spectra of a flush beyond this go in several passes */
-#define FIRX_MAX_FADE 4096                      /* fade_blocks x block <= 2^24: a sample's index within the fade is exact in float */
 
 typedef struct {
     int tag;                    /* LLZ_TAG_FIRX */
@@ -42,13 +42,11 @@ typedef struct {
     float *d_prev[2];           /* [inputs][block]: the last input block, double-buffered */
     float *d_y;                 /* [G][outputs][ycap][block] complex: the groups' partial spectra */
     /* the fade (llz_fir_xfade_matrix_mc): everything below is allocated at the first fade and kept */
-    float *d_hn;                /* d_h's size and layout: the spectra the paths in the fade go to */
+    llz_fade_t fade;            /* over the paths of d_h in [outputs][inputs] order (llz_fade.c) */
     float *d_yn;                /* d_y's size: the new taps' partial spectra of a blending block */
-    unsigned char *h_fade;      /* HOST [outputs][inputs]: 1 = the path is in the fade */
     unsigned char *h_ofade;     /* HOST [outputs]: 1 = the output has a path in the fade */
     unsigned char *conn_new;    /* HOST [outputs][inputs]: connected under the new taps (only the fade's paths are read) */
-    unsigned char *d_fade, *d_ofade, *d_conn_new;  /* their device copies, updated on the handle's stream */
-    int fade_blocks, fade_done; /* the fade's length (0: none pending or in flight) and the blocks of it already launched */
+    unsigned char *d_ofade, *d_conn_new;    /* their device copies, updated on the handle's stream */
     void *stream;
     llz_stage_t st_in, st_out;  /* only for callers passing host memory */
 } firx_t;
@@ -58,8 +56,9 @@ static void firx_destroy(firx_t *f)
     if (!f) return;
     llzs_free(f->d_h); llzs_free(f->d_tw); llzs_free(f->d_ring); llzs_free(f->d_prev[0]); llzs_free(f->d_prev[1]);
     llzs_free(f->d_y); llzs_free(f->d_conn);
-    llzs_free(f->d_hn); llzs_free(f->d_yn); llzs_free(f->d_fade); llzs_free(f->d_ofade); llzs_free(f->d_conn_new);
-    free(f->h_fade); free(f->h_ofade); free(f->conn_new);
+    llz_fade_release(&f->fade);
+    llzs_free(f->d_yn); llzs_free(f->d_ofade); llzs_free(f->d_conn_new);
+    free(f->h_ofade); free(f->conn_new);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     free(f->conn);
     f->tag = 0;
@@ -239,36 +238,19 @@ void llz_fir_matrix_mc_uninit(unsigned long handle)
     }
 }
 
-/* the fade is over (its last block launched, a reset, a flush): the new paths become the handle's, on the stream behind the
- * launches already issued -- the spectra buffers swapped when every path faded, else each run of faded paths (neighbours in
- * [outputs][inputs] order) copied into d_h; the connection table follows the new taps */
+/* the fade is over (its last block launched, a reset, a flush): the new paths become the handle's and the connection table
+ * follows the new taps, on the stream behind the launches already issued */
 static int firx_adopt(firx_t *f)
 {
     const size_t paths = (size_t)f->outputs * (size_t)f->inputs;
-    const size_t row = 2 * (size_t)f->P * (size_t)f->block;
-    int rc = LLZ_OK, all = 1;
-    for (size_t q = 0; q < paths; q++) all &= f->h_fade[q];
-    if (all) {
-        float *t = f->d_h;
-        f->d_h = f->d_hn;
-        f->d_hn = t;
-    } else {
-        for (size_t q = 0; q < paths && rc == LLZ_OK;) {
-            size_t e = q;
-            while (e < paths && f->h_fade[e] == f->h_fade[q]) e++;
-            if (f->h_fade[q]) rc = llzs_d2d(f->d_h + q * row, f->d_hn + q * row, sizeof(float) * row * (e - q), f->stream);
-            q = e;
-        }
-    }
     f->connected = 0;
     for (size_t q = 0; q < paths; q++) {
-        if (f->h_fade[q]) f->conn[q] = f->conn_new[q];
+        if (f->fade.h_rows[q]) f->conn[q] = f->conn_new[q];
         f->connected += f->conn[q];
     }
+    int rc = llz_fade_adopt(&f->fade, &f->d_h, paths, 2 * (size_t)f->P * (size_t)f->block, f->stream);
     if (rc == LLZ_OK) rc = llzs_h2d(f->d_conn, f->conn, paths, f->stream);
-    memset(f->h_fade, 0, paths);
     memset(f->h_ofade, 0, (size_t)f->outputs);
-    f->fade_blocks = f->fade_done = 0;
     return rc;
 }
 
@@ -277,19 +259,19 @@ static int firx_adopt(firx_t *f)
 static int firx_launch(firx_t *f, float *d_out, int nblk, int flush, int j0, int head, long n_out, long out_pitch)
 {
     int rc;
-    if (!f->fade_blocks) {
+    if (!f->fade.blocks) {
         rc = llzs_fir_matrix_mac_f32(f->block, f->d_h, f->d_ring, f->d_conn, f->d_y, f->inputs, f->outputs, nblk, flush, j0, f->P,
                                      f->R, head, f->G, f->gsize, f->stream);
         if (rc == LLZ_OK)
             rc = llzs_fir_matrix_inv_f32(f->block, f->d_y, f->d_tw, d_out, f->outputs, nblk, f->G, n_out, out_pitch, f->stream);
         return rc;
     }
-    rc = llzs_fir_matrix_mac_fade_f32(f->block, f->d_h, f->d_hn, f->d_ring, f->d_conn, f->d_conn_new, f->d_fade, f->d_ofade, f->d_y,
-                                      f->d_yn, f->inputs, f->outputs, nblk, flush, j0, f->P, f->R, head, f->G, f->gsize,
-                                      f->fade_done, f->fade_blocks, f->stream);
+    rc = llzs_fir_matrix_mac_fade_f32(f->block, f->d_h, f->fade.d_new, f->d_ring, f->d_conn, f->d_conn_new, f->fade.d_rows,
+                                      f->d_ofade, f->d_y, f->d_yn, f->inputs, f->outputs, nblk, flush, j0, f->P, f->R, head, f->G,
+                                      f->gsize, f->fade.done, f->fade.blocks, f->stream);
     if (rc == LLZ_OK)
         rc = llzs_fir_matrix_inv_fade_f32(f->block, f->d_y, f->d_yn, f->d_ofade, f->d_tw, d_out, f->outputs, nblk, j0, f->G, n_out,
-                                          out_pitch, f->fade_done, f->fade_blocks, f->stream);
+                                          out_pitch, f->fade.done, f->fade.blocks, f->stream);
     return rc;
 }
 
@@ -320,9 +302,9 @@ static int firx_process(firx_t *f, const float *in, float *out, int frame_len)
         f->head = (f->head + f->k) % f->R;
         f->cur ^= 1;
         rc = firx_launch(f, d_out, f->k, 0, 0, head, frame_len, frame_len);
-        if (rc == LLZ_OK && f->fade_blocks) {
-            f->fade_done += f->k;
-            if (f->fade_done >= f->fade_blocks) rc = firx_adopt(f);
+        if (rc == LLZ_OK && f->fade.blocks) {
+            f->fade.done += f->k;
+            if (f->fade.done >= f->fade.blocks) rc = firx_adopt(f);
         }
     }
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, obytes, f->stream);
@@ -346,7 +328,7 @@ static int firx_flush(firx_t *f, float *out)
 {
     const int keep = f->flt_len - 1, B = f->block;
     if (keep == 0) {                                              /* nothing to emit; the handle still starts over */
-        int rc0 = f->fade_blocks ? firx_adopt(f) : LLZ_OK;
+        int rc0 = f->fade.blocks ? firx_adopt(f) : LLZ_OK;
         if (rc0 == LLZ_OK) rc0 = firx_clear(f);
         return rc0 == LLZ_OK ? 0 : rc0;
     }
@@ -358,7 +340,7 @@ static int firx_flush(firx_t *f, float *out)
     if (rc != LLZ_OK) return rc;
     /* behind the input only the spectrum of (last block, zeros) is new: it goes into slot `head`, which the reset below gives
      * up anyway; then the ceil(keep / block) zero blocks side by side, as many at a time as the scratch holds.  A fade pending
-     * or in flight goes on through them -- flush block j is fade block fade_done + j, whichever pass it falls in -- and the
+     * or in flight goes on through them -- flush block j is fade block done + j, whichever pass it falls in -- and the
      * handle starts over on the new taps */
     const int nblk = (keep + B - 1) / B;
     rc = llzs_fir_matrix_fwd_f32(B, f->d_tw, f->d_ring, f->d_prev[f->cur], NULL, NULL, f->inputs, 1, 1, 0, f->R, f->head, f->stream);
@@ -367,7 +349,7 @@ static int firx_flush(firx_t *f, float *out)
         const long left = (long)keep - (long)j0 * B, n_out = left < (long)nb * B ? left : (long)nb * B;
         rc = firx_launch(f, d_out + (size_t)j0 * (size_t)B, nb, 1, j0, f->head, n_out, keep);
     }
-    if (rc == LLZ_OK && f->fade_blocks) rc = firx_adopt(f);
+    if (rc == LLZ_OK && f->fade.blocks) rc = firx_adopt(f);
     if (rc == LLZ_OK) rc = firx_clear(f);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? keep : rc;
@@ -395,7 +377,7 @@ int llz_fir_matrix_mc_reset(unsigned long handle)
     }
     firx_t *f = (firx_t *)handle;
     const int prev = llzs_device_enter(f->device);
-    int rc = f->fade_blocks ? firx_adopt(f) : LLZ_OK;             /* a fade pending or in flight: the new taps at once */
+    int rc = f->fade.blocks ? firx_adopt(f) : LLZ_OK;             /* a fade pending or in flight: the new taps at once */
     if (rc == LLZ_OK) rc = firx_clear(f);
     llzs_device_leave(prev);
     return rc;
@@ -418,11 +400,7 @@ int llz_fir_matrix_mc_set_taps(unsigned long handle, int out_first, int out_coun
                        f->inputs);
         return LLZ_ERR_ARG;
     }
-    if (f->fade_blocks) {
-        llzs_set_error("llz_fir_matrix_mc_set_taps: refused while a fade is in flight (%d of its %d blocks left)",
-                       f->fade_blocks - f->fade_done, f->fade_blocks);
-        return LLZ_ERR_ARG;
-    }
+    if (llz_fade_refuse_set_taps(&f->fade, "llz_fir_matrix_mc_set_taps")) return LLZ_ERR_ARG;
     const int prev = llzs_device_enter(f->device);
     int rc = LLZ_OK;
     for (int o = 0; o < out_count && rc == LLZ_OK; o++)
@@ -431,39 +409,25 @@ int llz_fir_matrix_mc_set_taps(unsigned long handle, int out_first, int out_coun
     return rc;
 }
 
-/* the buffers and tables of a fade, at the handle's first one */
+/* the handle's own buffers and tables of a fade, at its first one, behind llz_fade.c's */
 static int firx_fade_alloc(firx_t *f, const char *who)
 {
-    if (f->d_hn) return LLZ_OK;
+    if (f->d_yn) return LLZ_OK;
     const size_t paths = (size_t)f->outputs * (size_t)f->inputs;
-    const size_t hbytes = sizeof(float) * 2 * paths * (size_t)f->P * (size_t)f->block;
     const size_t ybytes = sizeof(float) * 2 * (size_t)f->G * (size_t)f->outputs * (size_t)f->ycap * (size_t)f->block;
-    float *hn = (float *)llzs_malloc(hbytes);
-    if (!hn) {
-        llzs_set_error("%s: no device memory for the new taps' spectra: %zu B asked for (%d outputs x %d inputs x %d partitions x "
-                       "%d bins)", who, hbytes, f->outputs, f->inputs, f->P, f->block);
-        return LLZ_ERR_NOMEM;
-    }
+    const int rc = llz_fade_reserve(&f->fade, who, "paths", paths, 2 * (size_t)f->P * (size_t)f->block);
+    if (rc != LLZ_OK) return rc;
     float *yn = (float *)llzs_malloc(ybytes);
-    if (!yn) {
-        llzs_set_error("%s: no device memory for the new taps' partial spectra: %zu B asked for (%d groups x %d outputs x %d "
-                       "blocks x %d bins)", who, ybytes, f->G, f->outputs, f->ycap, f->block);
-        llzs_free(hn);
+    unsigned char *dc = (unsigned char *)llzs_malloc(paths), *dof = (unsigned char *)llzs_malloc((size_t)f->outputs);
+    unsigned char *hc = (unsigned char *)calloc(paths, 1), *hof = (unsigned char *)calloc((size_t)f->outputs, 1);
+    if (!yn || !dc || !dof || !hc || !hof) {
+        llzs_set_error("%s: no memory for the new taps' partial spectra and the tables of the fade: %zu B of device memory asked for "
+                       "(%d groups x %d outputs x %d blocks x %d bins), and %zu B and %d B on the device and on the host", who,
+                       ybytes, f->G, f->outputs, f->ycap, f->block, paths, f->outputs);
+        llzs_free(yn); llzs_free(dc); llzs_free(dof); free(hc); free(hof);
         return LLZ_ERR_NOMEM;
     }
-    unsigned char *df = (unsigned char *)llzs_malloc(paths), *dc = (unsigned char *)llzs_malloc(paths);
-    unsigned char *dof = (unsigned char *)llzs_malloc((size_t)f->outputs);
-    unsigned char *hf = (unsigned char *)calloc(paths, 1), *hc = (unsigned char *)calloc(paths, 1);
-    unsigned char *hof = (unsigned char *)calloc((size_t)f->outputs, 1);
-    if (!df || !dc || !dof || !hf || !hc || !hof) {
-        llzs_set_error("%s: no memory for the tables of the fade: 2 x %zu B and %d B asked for, on the device and on the host", who,
-                       paths, f->outputs);
-        llzs_free(hn); llzs_free(yn); llzs_free(df); llzs_free(dc); llzs_free(dof);
-        free(hf); free(hc); free(hof);
-        return LLZ_ERR_NOMEM;
-    }
-    f->d_hn = hn; f->d_yn = yn; f->d_fade = df; f->d_conn_new = dc; f->d_ofade = dof;
-    f->h_fade = hf; f->conn_new = hc; f->h_ofade = hof;
+    f->d_yn = yn; f->d_conn_new = dc; f->d_ofade = dof; f->conn_new = hc; f->h_ofade = hof;
     return LLZ_OK;
 }
 
@@ -488,37 +452,28 @@ int llz_fir_xfade_matrix_mc(unsigned long handle, int out_first, int out_count, 
         llzs_set_error("%s: inputs [%d, %d + %d) outside the handle's [0, %d)", who, in_first, in_first, in_count, f->inputs);
         return LLZ_ERR_ARG;
     }
-    if (fade_blocks < 1 || fade_blocks > FIRX_MAX_FADE) {
-        llzs_set_error("%s: fade_blocks %d outside 1..%d", who, fade_blocks, FIRX_MAX_FADE);
-        return LLZ_ERR_ARG;
-    }
-    /* one fade at a time; until its first block has run, calls with the same length add or replace paths of it */
-    if (f->fade_blocks && (f->fade_done > 0 || fade_blocks != f->fade_blocks)) {
-        llzs_set_error("%s: a fade is already in flight (%d of its %d blocks left)%s", who, f->fade_blocks - f->fade_done,
-                       f->fade_blocks, f->fade_done ? "" : ": paths join a pending fade only with the same fade_blocks");
-        return LLZ_ERR_ARG;
-    }
+    if (llz_fade_refuse(&f->fade, who, "paths", fade_blocks)) return LLZ_ERR_ARG;
     const int prev = llzs_device_enter(f->device);
     const size_t paths = (size_t)f->outputs * (size_t)f->inputs;
     const size_t row = 2 * (size_t)f->P * (size_t)f->block;         /* floats of one path's spectra */
     int rc = firx_fade_alloc(f, who);
     /* the spectra as set_taps would upload them, on the stream behind the calls already issued: no launch reads these paths of
-     * d_hn before the tables below mark them */
+     * the new buffer before the tables below mark them */
     for (int o = 0; o < out_count && rc == LLZ_OK; o++) {
         const size_t first = (size_t)(out_first + o) * (size_t)f->inputs + (size_t)in_first;
-        rc = llz_host_load_spectra(who, f->d_hn + first * row, row, in_count, taps + (size_t)o * (size_t)in_count * (size_t)f->flt_len,
-                                   f->flt_len, 2 * f->block, 1, 0, f->stream);
+        rc = llz_host_load_spectra(who, f->fade.d_new + first * row, row, in_count,
+                                   taps + (size_t)o * (size_t)in_count * (size_t)f->flt_len, f->flt_len, 2 * f->block, 1, 0, f->stream);
     }
     if (rc == LLZ_OK) {
         /* the tables are built aside and go up on the stream, behind the last launch that read them; the handle takes them
-         * only when all three are up */
+         * only when all three are up: the fade's own goes last, and with it the fade is committed */
         unsigned char *t = (unsigned char *)malloc(2 * paths + (size_t)f->outputs);
         if (!t) {
             llzs_set_error("%s: out of host memory (%zu B)", who, 2 * paths + (size_t)f->outputs);
             rc = LLZ_ERR_NOMEM;
         } else {
             unsigned char *tf = t, *tc = t + paths, *to = t + 2 * paths;
-            memcpy(tf, f->h_fade, paths);
+            memcpy(tf, f->fade.h_rows, paths);
             memcpy(tc, f->conn_new, paths);
             memcpy(to, f->h_ofade, (size_t)f->outputs);
             for (int o = 0; o < out_count; o++) {
@@ -530,15 +485,12 @@ int llz_fir_xfade_matrix_mc(unsigned long handle, int out_first, int out_count, 
                 }
                 to[out_first + o] = 1;
             }
-            rc = llzs_h2d(f->d_fade, tf, paths, f->stream);
-            if (rc == LLZ_OK) rc = llzs_h2d(f->d_conn_new, tc, paths, f->stream);
+            rc = llzs_h2d(f->d_conn_new, tc, paths, f->stream);
             if (rc == LLZ_OK) rc = llzs_h2d(f->d_ofade, to, (size_t)f->outputs, f->stream);
+            if (rc == LLZ_OK) rc = llz_fade_commit(&f->fade, tf, paths, fade_blocks, f->stream);
             if (rc == LLZ_OK) {
-                memcpy(f->h_fade, tf, paths);
                 memcpy(f->conn_new, tc, paths);
                 memcpy(f->h_ofade, to, (size_t)f->outputs);
-                f->fade_blocks = fade_blocks;
-                f->fade_done = 0;
             }
             free(t);
         }
@@ -550,8 +502,7 @@ int llz_fir_xfade_matrix_mc(unsigned long handle, int out_first, int out_count, 
 int llz_fir_xfade_matrix_mc_left(unsigned long handle)
 {
     if (!LLZ_HANDLE_OK(handle, firx_t, LLZ_TAG_FIRX)) return LLZ_ERR_ARG;
-    const firx_t *f = (const firx_t *)handle;
-    return f->fade_blocks ? f->fade_blocks - f->fade_done : 0;
+    return llz_fade_left(&((const firx_t *)handle)->fade);
 }
 
 int llz_fir_matrix_mc_plan(unsigned long handle, int out[6])
@@ -562,11 +513,11 @@ int llz_fir_matrix_mc_plan(unsigned long handle, int out[6])
     }
     const firx_t *f = (const firx_t *)handle;
     out[0] = 2 * f->block; out[1] = f->P; out[2] = f->R; out[3] = f->k; out[4] = f->G; out[5] = f->connected;
-    if (f->fade_blocks) {
+    if (f->fade.blocks) {
         /* what a fading block reads: the paths connected under the old or the new taps */
         const size_t paths = (size_t)f->outputs * (size_t)f->inputs;
         out[5] = 0;
-        for (size_t q = 0; q < paths; q++) out[5] += f->conn[q] || (f->h_fade[q] && f->conn_new[q]);
+        for (size_t q = 0; q < paths; q++) out[5] += f->conn[q] || (f->fade.h_rows[q] && f->conn_new[q]);
     }
     return LLZ_OK;
 }

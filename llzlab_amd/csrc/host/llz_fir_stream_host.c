@@ -3,17 +3,17 @@
  * samples and the tail kernel) does not apply here -- the history lives as a ring of input spectra plus the last input block.
  * Staging, pointer classification and error conventions are those of llz_fir_host.c.
  *
- * llz_fir_xfade_stream_mc fades rows to new taps over fade_blocks blocks: the new rows' spectra go into a second buffer of d_h's
- * size, the rows are marked in a byte table, and while the fade is in flight every launch goes to fir_stream_fade.hip with the
- * fade's position by value.  When the last faded block has been launched the new rows are adopted on the stream behind it (the
- * buffers swapped when every row faded, else the rows copied into d_h) and the next call runs the untouched kernel. */
+ * llz_fir_xfade_stream_mc fades rows to new taps over fade_blocks blocks.  The fade's state and rules are llz_fade.c's (the second
+ * spectra buffer, the table of fading rows, the refusals, the adoption); what is the handle's own is here: while a fade is pending
+ * or in flight every launch goes to fir_stream_fade.hip with the fade's position by value, and after the launch of a call or a
+ * flush the handle moves the fade on by the blocks launched and adopts at its end, so that the next call runs the untouched
+ * kernel. */
 #include <stdlib.h>
 #include <string.h>
 #include "llz_host.h"
 
 #define FIRS_MIN_BLOCK 64
 #define FIRS_MAX_BLOCK 4096
-#define FIRS_MAX_FADE 4096      /* fade_blocks x block <= 2^24: a sample's index within the fade is exact in float */
 
 typedef struct {
     int tag;                    /* LLZ_TAG_FIRS */
@@ -25,10 +25,7 @@ typedef struct {
     float *d_tw;                /* [block / 2] complex W_block^m, then [block] complex W_N^bitrev(i) */
     float *d_ring;              /* [channels][R][block] complex: spectra of the last R input blocks */
     float *d_prev;              /* [channels][block]: the last input block */
-    float *d_hn;                /* d_h's size: the spectra a fade goes to; allocated at the first fade and kept */
-    unsigned char *d_fade;      /* [rows]: 1 = the row fades; the fade kernel's table */
-    unsigned char *h_fade;      /* the host copy of it */
-    int fade_blocks, fade_done; /* the fade's length (0: none in flight) and the blocks of it already launched */
+    llz_fade_t fade;            /* over the rows of d_h (llz_fade.c); allocated at the first fade and kept */
     void *stream;
     llz_stage_t st_in, st_out;  /* only for callers passing host memory */
 } firs_t;
@@ -37,7 +34,7 @@ static void firs_destroy(firs_t *f)
 {
     if (!f) return;
     llzs_free(f->d_h); llzs_free(f->d_tw); llzs_free(f->d_ring); llzs_free(f->d_prev);
-    llzs_free(f->d_hn); llzs_free(f->d_fade); free(f->h_fade);
+    llz_fade_release(&f->fade);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
     f->tag = 0;
     free(f);
@@ -85,44 +82,18 @@ static int firs_clear(firs_t *f)
 /* floats of one row's spectra */
 static size_t firs_row(const firs_t *f) { return 2 * (size_t)f->P * (size_t)f->block; }
 
-/* the fade is over (its last block launched, or a reset): the new rows become the handle's, on the stream behind the launches
- * already issued -- the buffers swapped when every row faded, else each run of faded rows copied into d_h */
-static int firs_adopt(firs_t *f)
-{
-    int rc = LLZ_OK, all = 1;
-    for (int r = 0; r < f->rows; r++) all &= f->h_fade[r];
-    if (all) {
-        float *t = f->d_h;
-        f->d_h = f->d_hn;
-        f->d_hn = t;
-    } else {
-        const size_t row = firs_row(f);
-        for (int r = 0; r < f->rows && rc == LLZ_OK;) {
-            int e = r;
-            while (e < f->rows && f->h_fade[e] == f->h_fade[r]) e++;
-            if (f->h_fade[r])
-                rc = llzs_d2d(f->d_h + (size_t)r * row, f->d_hn + (size_t)r * row, sizeof(float) * row * (size_t)(e - r), f->stream);
-            r = e;
-        }
-    }
-    memset(f->h_fade, 0, (size_t)f->rows);
-    f->fade_blocks = f->fade_done = 0;
-    return rc;
-}
+/* the fade is over (its last block launched, a reset, a flush): the new rows become the handle's */
+static int firs_adopt(firs_t *f) { return llz_fade_adopt(&f->fade, &f->d_h, (size_t)f->rows, firs_row(f), f->stream); }
 
-/* one launch of nblk blocks: the fade kernel exactly while a fade is in flight, which then moves on by the blocks launched */
+/* one launch of nblk blocks: the fade kernel exactly while a fade is pending or in flight.  The caller moves the fade on */
 static int firs_launch(firs_t *f, const float *d_in, float *d_out, int nblk, int flush, long n_out, long in_pitch, long out_pitch)
 {
-    if (!f->fade_blocks)
+    if (!f->fade.blocks)
         return llzs_fir_stream_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, d_in, d_out, f->channels, nblk,
                                    flush, n_out, in_pitch, out_pitch, f->P, f->R, f->head, f->stream);
-    int rc = llzs_fir_stream_fade_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, d_in, d_out, f->channels, nblk,
-                                      flush, n_out, in_pitch, out_pitch, f->P, f->R, f->head, f->d_hn, f->d_fade, f->fade_done,
-                                      f->fade_blocks, f->stream);
-    if (rc != LLZ_OK) return rc;
-    f->fade_done += nblk;
-    if (flush || f->fade_done >= f->fade_blocks) rc = firs_adopt(f);      /* a flush leaves the handle on the new taps */
-    return rc;
+    return llzs_fir_stream_fade_f32(f->block, f->d_h, f->rows > 1, f->d_tw, f->d_ring, f->d_prev, d_in, d_out, f->channels, nblk,
+                                    flush, n_out, in_pitch, out_pitch, f->P, f->R, f->head, f->fade.d_new, f->fade.d_rows,
+                                    f->fade.done, f->fade.blocks, f->stream);
 }
 
 unsigned long llz_fir_stream_mc_init(int channels, int block, int frame_len, const float *taps, int rows, int flt_len)
@@ -213,6 +184,10 @@ static int firs_process(firs_t *f, const float *in, float *out, int frame_len)
     const float *d_in = llz_stage_in(&f->st_in, in, bytes, in_dev, f->stream, &rc);
     float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
     if (rc == LLZ_OK) rc = firs_launch(f, d_in, d_out, f->k, 0, frame_len, frame_len, frame_len);
+    if (rc == LLZ_OK && f->fade.blocks) {
+        f->fade.done += f->k;
+        if (f->fade.done >= f->fade.blocks) rc = firs_adopt(f);
+    }
     if (rc == LLZ_OK) f->head = (f->head + f->k) % f->R;
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? frame_len : rc;
@@ -235,7 +210,7 @@ static int firs_flush(firs_t *f, float *out)
 {
     const int keep = f->flt_len - 1;
     if (keep == 0) {                                              /* nothing to emit; the handle still starts over */
-        int rc0 = f->fade_blocks ? firs_adopt(f) : LLZ_OK;
+        int rc0 = f->fade.blocks ? firs_adopt(f) : LLZ_OK;
         if (rc0 == LLZ_OK) rc0 = firs_clear(f);
         return rc0 == LLZ_OK ? 0 : rc0;
     }
@@ -245,9 +220,10 @@ static int firs_flush(firs_t *f, float *out)
     int rc = LLZ_OK;
     float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
     if (rc != LLZ_OK) return rc;
-    /* ceil(keep / block) zero blocks behind the input so far (a fade in flight goes on through them: flush block j is fade block
-     * fade_done + j), then the delay line to zeros: the handle starts over, on the new taps */
+    /* ceil(keep / block) zero blocks behind the input so far (a fade pending or in flight goes on through them: flush block j is
+     * fade block done + j), then the delay line to zeros: the handle starts over, on the new taps */
     rc = firs_launch(f, NULL, d_out, (keep + f->block - 1) / f->block, 1, keep, 0, keep);
+    if (rc == LLZ_OK && f->fade.blocks) rc = firs_adopt(f);
     if (rc == LLZ_OK) rc = firs_clear(f);
     if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
     return rc == LLZ_OK ? keep : rc;
@@ -275,7 +251,7 @@ int llz_fir_stream_mc_reset(unsigned long handle)
     }
     firs_t *f = (firs_t *)handle;
     const int prev = llzs_device_enter(f->device);
-    int rc = f->fade_blocks ? firs_adopt(f) : LLZ_OK;             /* a fade in flight: the new taps at once */
+    int rc = f->fade.blocks ? firs_adopt(f) : LLZ_OK;             /* a fade pending or in flight: the new taps at once */
     if (rc == LLZ_OK) rc = firs_clear(f);
     llzs_device_leave(prev);
     return rc;
@@ -293,11 +269,7 @@ int llz_fir_stream_mc_set_taps(unsigned long handle, int first, int count, const
                        f->rows, f->rows == 1 && f->channels > 1 ? " (one tap set for all channels: only first 0, count 1)" : "");
         return LLZ_ERR_ARG;
     }
-    if (f->fade_blocks) {
-        llzs_set_error("llz_fir_stream_mc_set_taps: refused while a fade is in flight (%d of its %d blocks left)",
-                       f->fade_blocks - f->fade_done, f->fade_blocks);
-        return LLZ_ERR_ARG;
-    }
+    if (llz_fade_refuse_set_taps(&f->fade, "llz_fir_stream_mc_set_taps")) return LLZ_ERR_ARG;
     const int prev = llzs_device_enter(f->device);
     const size_t row = firs_row(f);
     const int rc = llz_host_load_spectra("llz_fir_stream_mc_set_taps", f->d_h + (size_t)first * row, row, count, taps, f->flt_len,
@@ -323,49 +295,22 @@ int llz_fir_xfade_stream_mc(unsigned long handle, int first, int count, const fl
                        f->rows == 1 && f->channels > 1 ? " (one tap set for all channels: only first 0, count 1)" : "");
         return LLZ_ERR_ARG;
     }
-    if (fade_blocks < 1 || fade_blocks > FIRS_MAX_FADE) {
-        llzs_set_error("%s: fade_blocks %d outside 1..%d", who, fade_blocks, FIRS_MAX_FADE);
-        return LLZ_ERR_ARG;
-    }
-    /* one fade at a time; until its first block has run, calls with the same length add or replace rows of it */
-    if (f->fade_blocks && (f->fade_done > 0 || fade_blocks != f->fade_blocks)) {
-        llzs_set_error("%s: a fade is already in flight (%d of its %d blocks left)%s", who, f->fade_blocks - f->fade_done,
-                       f->fade_blocks, f->fade_done ? "" : ": rows join a pending fade only with the same fade_blocks");
-        return LLZ_ERR_ARG;
-    }
+    if (llz_fade_refuse(&f->fade, who, "rows", fade_blocks)) return LLZ_ERR_ARG;
     const int prev = llzs_device_enter(f->device);
-    const size_t row = firs_row(f), hbytes = sizeof(float) * row * (size_t)f->rows;
-    int rc = LLZ_OK;
-    if (!f->d_hn) {                                               /* the first fade: the second buffer, kept from here on */
-        float *hn = (float *)llzs_malloc(hbytes);
-        unsigned char *df = (unsigned char *)llzs_malloc((size_t)f->rows);
-        unsigned char *hf = (unsigned char *)calloc((size_t)f->rows, 1);
-        if (!hn || !df || !hf) {
-            llzs_set_error("%s: no memory for the new taps' spectra: %zu B of device memory asked for (%d rows x %d partitions x %d "
-                           "bins) and %d B for the table of fading rows", who, hbytes, f->rows, f->P, f->block, f->rows);
-            llzs_free(hn); llzs_free(df); free(hf);
-            rc = LLZ_ERR_NOMEM;
-        } else {
-            f->d_hn = hn; f->d_fade = df; f->h_fade = hf;
-        }
-    }
+    const size_t row = firs_row(f);
+    int rc = llz_fade_reserve(&f->fade, who, "rows", (size_t)f->rows, row);
     if (rc == LLZ_OK)
-        rc = llz_host_load_spectra(who, f->d_hn + (size_t)first * row, row, count, taps, f->flt_len, 2 * f->block, 1, 0, f->stream);
+        rc = llz_host_load_spectra(who, f->fade.d_new + (size_t)first * row, row, count, taps, f->flt_len, 2 * f->block, 1, 0,
+                                   f->stream);
     if (rc == LLZ_OK) {
-        /* the table goes up on the stream, behind the last launch that read it */
         unsigned char *t = (unsigned char *)malloc((size_t)f->rows);
         if (!t) {
             llzs_set_error("%s: out of host memory (%d B)", who, f->rows);
             rc = LLZ_ERR_NOMEM;
         } else {
-            memcpy(t, f->h_fade, (size_t)f->rows);
+            memcpy(t, f->fade.h_rows, (size_t)f->rows);
             memset(t + first, 1, (size_t)count);
-            rc = llzs_h2d(f->d_fade, t, (size_t)f->rows, f->stream);
-            if (rc == LLZ_OK) {
-                memcpy(f->h_fade, t, (size_t)f->rows);
-                f->fade_blocks = fade_blocks;
-                f->fade_done = 0;
-            }
+            rc = llz_fade_commit(&f->fade, t, (size_t)f->rows, fade_blocks, f->stream);
             free(t);
         }
     }
@@ -376,8 +321,7 @@ int llz_fir_xfade_stream_mc(unsigned long handle, int first, int count, const fl
 int llz_fir_xfade_stream_mc_left(unsigned long handle)
 {
     if (!LLZ_HANDLE_OK(handle, firs_t, LLZ_TAG_FIRS)) return LLZ_ERR_ARG;
-    const firs_t *f = (const firs_t *)handle;
-    return f->fade_blocks ? f->fade_blocks - f->fade_done : 0;
+    return llz_fade_left(&((const firs_t *)handle)->fade);
 }
 
 int llz_fir_stream_mc_plan(unsigned long handle, int out[4])

@@ -103,4 +103,35 @@ void  llz_stage_release(llz_stage_t *s);
 const void *llz_stage_in(llz_stage_t *s, const void *user, size_t bytes, int user_dev, void *stream, int *rc);
 void *llz_stage_out(llz_stage_t *s, void *user, size_t bytes, int user_dev, int *rc);
 
+/* ---- llz_fade.c: the crossfade state of the delay-line convolvers (llz_fir_xfade_stream_mc, llz_fir_xfade_matrix_mc) ---- */
+
+#define LLZ_FADE_MAX_BLOCKS 4096        /* fade_blocks x block <= 2^24: a sample's index within the fade is exact in float */
+
+/* A fade over `rows` rows of spectra of `row` floats each (the stream handle's tap rows, the matrix handle's paths in
+ * [outputs][inputs] order): the same rows and row go with every call below.  Zeroed = a handle that has never faded. */
+typedef struct {
+    float *d_new;               /* the handle's spectra buffer's size and layout: the spectra the rows in the fade go to */
+    unsigned char *h_rows;      /* HOST [rows]: 1 = the row is in the fade */
+    unsigned char *d_rows;      /* its device copy, updated on the handle's stream: the fade kernels' table */
+    int blocks, done;           /* the fade's length (0: none pending or in flight) and the blocks of it already launched */
+} llz_fade_t;
+
+/* the refusals of a fade request, with a message naming `who`: fade_blocks outside 1..LLZ_FADE_MAX_BLOCKS, and one fade at a
+ * time -- until its first block has run, requests with the same fade_blocks add or replace rows (`noun`: "rows", "paths") */
+int  llz_fade_refuse(const llz_fade_t *fd, const char *who, const char *noun, int fade_blocks);
+/* set_taps while a fade is pending or in flight: refused with the blocks left */
+int  llz_fade_refuse_set_taps(const llz_fade_t *fd, const char *who);
+/* the handle's first fade: d_new and the two tables, kept until the release; LLZ_ERR_NOMEM with a message naming who and the bytes */
+int  llz_fade_reserve(llz_fade_t *fd, const char *who, const char *noun, size_t rows, size_t row);
+/* `table` (h_rows with the request's rows set) goes up on the stream, behind the last launch that read d_rows; the host copy,
+ * blocks = fade_blocks and done = 0 are taken only when the upload succeeded */
+int  llz_fade_commit(llz_fade_t *fd, const unsigned char *table, size_t rows, int fade_blocks, void *stream);
+/* the fade is over (its last block launched, a reset, a flush): the new rows become the handle's, on the stream behind the
+ * launches already issued -- *d_h and d_new swapped when every row faded, else each run of faded rows copied into *d_h; the
+ * table is cleared and blocks = done = 0 */
+int  llz_fade_adopt(llz_fade_t *fd, float **d_h, size_t rows, size_t row, void *stream);
+/* blocks of the fade still to be launched; 0: none pending or in flight */
+int  llz_fade_left(const llz_fade_t *fd);
+void llz_fade_release(llz_fade_t *fd);
+
 #endif

@@ -1,6 +1,7 @@
 // fir_matrix.hpp -- what fir_matrix.hip (K4g) and fir_matrix_fade.hip (K4g while paths fade) share beyond stream_bins.hpp: the
 // geometry of a launch, the product's bins per thread and tiles per block, and the shape check of the entries.  No device code
-// lives here: the kernels of the two files are written out side by side ("Shared code").
+// lives here: the kernels of the two files are written out side by side, the inverse included, whose fold into one function
+// of this header was built, measured and taken out again ("Shared code").
 #pragma once
 #include "stream_bins.hpp"
 

@@ -4,7 +4,9 @@
 // blends the two outputs sample by sample in the time domain, after the sum over inputs:
 //     y_o[n] = fmaf(w[n], y_new_o[n] - y_old_o[n], y_old_o[n]),   w[n] = (float)n / (float)(F B), n from the fade's first sample.
 // The delay lines hold INPUT spectra, so k_fir_matrix_fwd (fir_matrix.hip) serves a fade unchanged.  Calls with no fade pending
-// or in flight run k_fir_matrix_mac / _inv; the files share stream_bins.hpp and the geometry of fir_matrix.hpp.
+// or in flight run k_fir_matrix_mac / _inv; the files share stream_bins.hpp (the fade's position, fade_pos, with K4f's fade too) and
+// the geometry of fir_matrix.hpp.  The inverse stays written out in both files: as one function of fir_matrix.hpp it kept every
+// register limit, but a fading call at 2 -> 64, block 2048 took 0.4 % longer ("Shared code").
 //
 //   1. k_fir_matrix_mac_fade: k_fir_matrix_mac's grid, thread-to-bin ownership and U = 8 / V partitions in flight.  The block of
 //      the fade, fb = fade_done + j0 + j, is the same for a whole workgroup, and so is each of its three cases:
@@ -32,9 +34,7 @@
 
 namespace {
 
-struct matrix_fade_geom : matrix_geom {
-    int fade_done, fade_blocks; // block j of this launch is block fade_done + j0 + j of the fade; from fade_blocks on: new taps alone
-};
+struct matrix_fade_geom : matrix_geom, fade_pos {};     // block j of this launch is block fade_done + j0 + j of the fade
 
 // workgroup (o, j, tile + tiles g).  H / conn: the handle's spectra and connection table; Hn / conn_new: the new taps' (same
 // layouts; read only where fade[o][i] is set); ofade[o]: 1 = output o has a path in the fade; Y / Yn: the old and the new
@@ -222,11 +222,6 @@ int inv_fade_launch(const float2 *Y, const float2 *Yn, const unsigned char *ofad
     return LLZ_OK;
 }
 
-bool fade_position_ok(int fade_done, int fade_blocks)
-{
-    return fade_blocks >= 1 && fade_blocks <= 4096 && fade_done >= 0 && fade_done < fade_blocks;
-}
-
 } // namespace
 
 // llzs_fir_matrix_mac_f32's launch with a fade pending or in flight.  hspec_new, conn_new: the new taps' spectra and connection
@@ -243,7 +238,7 @@ extern "C" int llzs_fir_matrix_mac_fade_f32(int block, const float *hspec, const
     const bool ok = stream_log2(block, &log2b);
     if (!matrix_shape_ok(ok, inputs, outputs, nblk, P, R, head) || !hspec || !hspec_new || !ring || !conn || !conn_new || !fade ||
         !ofade || !ypart || !ypart_new || ypart == ypart_new ||
-        !matrix_groups_ok(block, inputs, nblk, flush, j0, P, groups, group_size) || !fade_position_ok(fade_done, fade_blocks)) {
+        !matrix_groups_ok(block, inputs, nblk, flush, j0, P, groups, group_size) || !fade_pos_ok({fade_done, fade_blocks})) {
         llzs_set_error("fir_matrix_mac_fade_f32: bad arguments (block=%d inputs=%d outputs=%d nblk=%d j0=%d P=%d R=%d head=%d "
                        "groups=%d x %d fade %d of %d)", block, inputs, outputs, nblk, j0, P, R, head, groups, group_size, fade_done,
                        fade_blocks);
@@ -270,7 +265,7 @@ extern "C" int llzs_fir_matrix_inv_fade_f32(int block, const float *ypart, const
     int log2b;
     const bool ok = stream_log2(block, &log2b);
     if (!matrix_shape_ok(ok, 1, outputs, nblk, 1, 1, 0) || !ypart || !ypart_new || !ofade || !tw || !out || groups < 1 || j0 < 0 ||
-        n_out < 1 || n_out > (long)nblk * block || out_pitch < n_out || !fade_position_ok(fade_done, fade_blocks)) {
+        n_out < 1 || n_out > (long)nblk * block || out_pitch < n_out || !fade_pos_ok({fade_done, fade_blocks})) {
         llzs_set_error("fir_matrix_inv_fade_f32: bad arguments (block=%d outputs=%d nblk=%d j0=%d groups=%d n_out=%ld out_pitch=%ld "
                        "fade %d of %d)", block, outputs, nblk, j0, groups, n_out, out_pitch, fade_done, fade_blocks);
         return LLZ_ERR_ARG;

@@ -30,9 +30,7 @@
 
 namespace {
 
-struct fade_geom : stream_geom {
-    int fade_done, fade_blocks; // block j of this launch is block fade_done + j of the fade; from fade_blocks on: new taps alone
-};
+struct fade_geom : stream_geom, fade_pos {};   // block j of this launch is block fade_done + j of the fade
 
 // workgroup c (a flush: (c, block)) -> channel c.  H: the handle's spectra, Hn: the new taps' (same layout; only fading rows are
 // read), fading: one byte per tap row.  tw: as k_fir_stream's
@@ -278,9 +276,9 @@ extern "C" int llzs_fir_stream_fade_f32(int block, const float *hspec, int bank,
 {
     int log2b;
     const bool ok = stream_log2(block, &log2b);
-    fade_geom G = {{P, R, head, nblk, flush ? 1 : 0, n_out, in_pitch, out_pitch}, fade_done, fade_blocks};
+    fade_geom G = {{P, R, head, nblk, flush ? 1 : 0, n_out, in_pitch, out_pitch}, {fade_done, fade_blocks}};
     if (!stream_launch_ok(G, ok, block, channels, hspec && hspec_new && fading && tw && ring && prev && out, in) ||
-        fade_blocks < 1 || fade_blocks > 4096 || fade_done < 0 || fade_done >= fade_blocks) {
+        !fade_pos_ok(G)) {
         llzs_set_error("fir_stream_fade_f32: bad arguments (block=%d channels=%d nblk=%d P=%d R=%d head=%d n_out=%ld fade %d of %d)",
                        block, channels, nblk, P, R, head, n_out, fade_done, fade_blocks);
         return LLZ_ERR_ARG;

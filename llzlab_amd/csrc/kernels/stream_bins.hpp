@@ -3,7 +3,9 @@
 // bitrev(i), position 0 packs DC and Nyquist), its product step, the loads and stores of neighbouring bins, the two split
 // steps between the B-point complex transform (part_fft.hpp) and that half-spectrum -- called by all three files, so that a
 // block of the fade kernel that does not fade, and one path of the matrix form, give the stream convolver's values -- and
-// the launch preamble of their five launchers: block size, dispatch over the seven sizes, K4f's geometry and argument check.
+// the launch preamble of their launchers: block size, dispatch over the seven sizes, K4f's geometry and argument check, and the
+// position of a launch within a fade (fade_pos and its check, the one place that holds the limit of 4096 blocks on the device
+// side) for fir_stream_fade.hip and fir_matrix_fade.hip.
 #pragma once
 #include "common.hpp"
 #include "part_fft.hpp"
@@ -103,6 +105,18 @@ struct stream_geom {
     long n_out;                 // samples per channel to store: <= nblk B
     long in_pitch, out_pitch;
 };
+
+// where a launch of a fade kernel stands in the fade (fir_stream_fade.hip, fir_matrix_fade.hip derive their geometries from
+// it): the launch's block 0 is block fade_done of the fade's fade_blocks; blocks from fade_blocks on run the new taps alone
+struct fade_pos {
+    int fade_done, fade_blocks;
+};
+
+// fade_blocks B <= 2^24, so that a sample's index within the fade is exact in float; a launch starts inside the fade
+bool fade_pos_ok(const fade_pos &F)
+{
+    return F.fade_blocks >= 1 && F.fade_blocks <= 4096 && F.fade_done >= 0 && F.fade_done < F.fade_blocks;
+}
 
 // G and the buffers of a K4f launch within the kernels' index ranges and the grid limits; in: null only for a flush
 bool stream_launch_ok(const stream_geom &G, bool log2ok, int block, int channels, bool buffers, const float *in)
