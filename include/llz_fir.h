@@ -96,6 +96,11 @@ void          llz_fir_filter_mc_uninit(unsigned long handle);
  * (used in place, asynchronous on the handle's stream) or host memory (staged through the GPU, synchronous).
  * frame_len must equal the init frame_len. Returns frame_len, or a negative LLZ_ERR_* code. */
 int llz_fir_filter_mc(unsigned long handle, const float *in, float *out, int frame_len);
+/* the same call on rows of larger buffers: channel c is in + c * in_pitch and out + c * out_pitch (pitches in floats, at least
+ * frame_len).  Device memory only, used in place; the spans may not overlap.  Planes cut from a larger tensor keep the row
+ * alignment they had, which the 1024-point overlap-save form uses: rows whose bases and pitches are multiples of 32 KB take its
+ * aligned walk whatever frame_len is. */
+int llz_fir_filter_mc_pitched(unsigned long handle, const float *in, float *out, int frame_len, long in_pitch, long out_pitch);
 /* out: planar [channels][flt_len-1]; returns flt_len-1 */
 int llz_fir_filter_mc_flush(unsigned long handle, float *out);
 int llz_fir_filter_mc_flt_len(unsigned long handle);

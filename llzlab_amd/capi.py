@@ -133,6 +133,7 @@ def lib():
     sig("llz_fir_filter_mc_bandstop_init", ul, i, i, i, d, d, i)
     sig("llz_fir_filter_mc_uninit", None, ul)
     sig("llz_fir_filter_mc", i, ul, vp, vp, i)
+    sig("llz_fir_filter_mc_pitched", i, ul, vp, vp, i, lng, lng)
     sig("llz_fir_filter_mc_flush", i, ul, vp)
     sig("llz_fir_filter_mc_flt_len", i, ul)
     sig("llz_fir_filter_mc_algo", i, ul)

@@ -571,6 +571,36 @@ static int firm_process(firm_t *f, const float *in, float *out, int frame_len)
     return rc == LLZ_OK ? frame_len : rc;
 }
 
+/* rows of larger device buffers: the launch of firm_process with the caller's pitches, nothing staged */
+int llz_fir_filter_mc_pitched(unsigned long handle, const float *in, float *out, int frame_len, long in_pitch, long out_pitch)
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM) || !in || !out) {
+        llzs_set_error("llz_fir_filter_mc_pitched: bad handle or NULL buffer");
+        return LLZ_ERR_ARG;
+    }
+    firm_t *f = (firm_t *)handle;
+    if (frame_len != f->frame_len || in_pitch < frame_len || out_pitch < frame_len) {
+        llzs_set_error("llz_fir_filter_mc_pitched: frame_len %d != init frame_len %d, or a pitch (%ld, %ld) below it", frame_len,
+                       f->frame_len, in_pitch, out_pitch);
+        return LLZ_ERR_ARG;
+    }
+    const int prev = llzs_device_enter(f->device);
+    const size_t in_bytes = sizeof(float) * ((size_t)(f->channels - 1) * (size_t)in_pitch + (size_t)frame_len);
+    const size_t out_bytes = sizeof(float) * ((size_t)(f->channels - 1) * (size_t)out_pitch + (size_t)frame_len);
+    const int in_dev = llzs_is_device_ptr(in), out_dev = llzs_is_device_ptr(out);
+    int rc = LLZ_OK;
+    if (in_dev != 1 || out_dev != 1) {
+        if (in_dev >= 0 && out_dev >= 0) llzs_set_error("llz_fir_filter_mc_pitched: in and out must be device memory");
+        rc = LLZ_ERR_ARG;
+    } else if (llz_refuse_device_overlap("llz_fir_filter_mc_pitched", "in", in, in_bytes, in_dev, "out", out, out_bytes, out_dev)) {
+        rc = LLZ_ERR_ARG;
+    } else {
+        rc = firm_launch(f, in, out, frame_len, in_pitch, out_pitch, f->algo);
+    }
+    llzs_device_leave(prev);
+    return rc == LLZ_OK ? frame_len : rc;
+}
+
 int llz_fir_filter_mc_flush(unsigned long handle, float *out)
 {
     if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM) || !out) {

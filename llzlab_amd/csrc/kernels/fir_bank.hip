@@ -1,6 +1,6 @@
 // fir_bank.hip -- K4c: the 1024-point overlap-save FIR with a tap set PER CHANNEL (llz_fir_bank_mc).
 //
-// The walk is fir_ols.hip's k_fir_ols_chain_f32, step for step (ols_walk.hpp): a half-wave owns a job of 1536 new samples,
+// The walk is fir_ols.hip's segment walk (k_fir_ols_seg_f32), step for step (ols_walk.hpp): a half-wave owns a job of 1536 new samples,
 // walks a segment of up to 16 jobs of one channel with the 256-sample overlap carried in registers, and requests the next
 // job -- across segment boundaries the first job and the halo of its NEXT segment -- before it transforms the current one:
 // every input sample is requested once, a half-wave instruction moves 128 contiguous bytes.  What differs is where the

@@ -1,5 +1,6 @@
 // fir_ols.hip -- K4 / K4b: overlap-save FIR with register FFTs that never leave the CU.
-//   k_fir_ols_chain_f32      up to 257 taps   1024-point transforms, a half-wave per job (described first, below)
+//   k_fir_ols_chain_f32      up to 257 taps   1024-point transforms, a half-wave per job (described first, below;
+//   k_fir_ols_seg_f32                         the super-block walk and the segment walk)
 //   k_fir_ols2k_chain_f32<O> up to 1025 taps  2048-point transforms, a whole wave per job (one radix-2 step over the half-waves)
 //   k_fir_ols4k_f32<O>       up to 3073 taps  4096-point transforms, a whole wave per job (two radix-2 steps)
 //   k_fir_ols8k_f32<O>       up to 6145 taps  8192-point transforms, a pair of waves per job (one more radix-2 step, across the pair)
@@ -13,17 +14,35 @@
 // Overlap-save costs ~46 vector lane-operations per sample and is HBM-bound.
 //
 // Mapping to CDNA4 (wave64):
-//   * job = one channel x 1536 new samples.  Two consecutive 1024-sample blocks (each: 256 overlap + 768 new) are
+//   * job = one channel x 1536 new samples.  Two 1024-sample blocks (each: 256 overlap + 768 new) are
 //     the real and imaginary part of ONE complex 1024-point transform -- the filter is real, so
 //     IFFT(FFT(xa + j xb) H) = ya + j yb and nothing has to be untangled.
 //   * a half-wave (32 lanes) owns a job: 1024 = 32 x 32, every lane keeps 32 complex values in registers.  A
 //     transform is two passes of 32-point in-register FFTs (fft32.hpp) with one 32 x 32 transpose through LDS
 //     between them (row pitch 33 floats).  Forward leaves bins digit-reversed in the register index, which is
 //     free (register renaming), so FFT -> multiply by H -> IFFT needs no permutation pass at all.
-//   * a half-wave walks a SEGMENT of up to 16 consecutive jobs of one channel and carries the 256-sample overlap in
-//     registers from job to job, so every input sample is requested from memory exactly once; the next job's samples
-//     are requested (into registers) before the current job is transformed, across segment boundaries as well
-//     (k_fir_ols_chain_f32: the last job of a segment requests the first job and the halo of the half-wave's next segment).
+//   * the walk, large batches of 32 KB-aligned rows (the headline; k_fir_ols_chain_f32, geometry in ols_superblock.h): a half-wave
+//     owns a SUPER-BLOCK of 16384 consecutive samples of one channel (64 KB, aligned to 64 KB) as two 32 KB regions walked
+//     side by side -- the real part of a transform is a block of region 0, the imaginary part the same block of region 1,
+//     so the half-wave's requests alternate between two 32 KB-aligned runs exactly 32 KB apart.  One 256-sample overlap per
+//     sub-stream is carried in registers from job to job; a region is 10 2/3 blocks of 768 new samples, so the 11th job of a
+//     super-block is short (16 requested rows; its window ends at the region's end).  The next job's samples are requested
+//     (into registers) before the current job is transformed, across super-blocks as well: the short job requests job 0 and
+//     both halos of the half-wave's next super-block.  Region 1's halo is the tail of region 0: 2 KB per 64 KB are requested
+//     twice, and 11 transforms do the work of 10 2/3.
+//   * the walk, everything else (k_fir_ols_seg_f32; fir_bank.hip walks the same way): a half-wave walks a SEGMENT of up to 16
+//     consecutive jobs of one channel -- a job is two CONSECUTIVE blocks, 1536 new samples -- with one carried overlap and the
+//     same chain across segments; every input sample is requested exactly once.  Small batches take the segment length that
+//     fills the machine (ols_plan_of), which 64 KB units cannot.
+//     Why two walks: how fast this memory system streams depends on the length and the alignment of the run a half-wave reads
+//     before it jumps (profiles/r02/ubench_walk_pairs.txt, ubench_walk_substreams.txt: two sub-streams exactly 32 KB apart copy
+//     7..11 % faster than one 96 KB run, sub-streams at any distance that is no multiple of 16 KB slower than both).  Segments
+//     are 96 KB at a 96 KB stride: never aligned, and no whole number of 6 KB jobs makes 32 KB.  The copy stand-in of both
+//     shapes (tools/ubench/ols_io.hip sb, profiles/r04/ubench_ols_io_superblock.txt): 5.80 against 5.57 TB/s; the kernel:
+//     6.28 against 6.40 ms on the headline, same box, alternating (profiles/r04/ab_ols_superblock.txt).
+//   * known and deliberately left alone: in the compiled job loop an s_waitcnt vmcnt(0) follows the prefetch requests directly,
+//     before the transform's first instruction, so a wave does not overlap its own prefetch with its own transform; the other
+//     wave of the SIMD does.  A third wave to hide that wait changed nothing (profiles/r02/ab_ols_no_prefetch_three_waves.txt).
 //   * HBM access shape: one dword per lane, a half-wave instruction moves 128 contiguous bytes of its job.  Wider shapes
 //     were built and measured and do not pay (profiles/r02/): a copy kernel in exactly this walk structure runs at the same
 //     rate with 4, 8 or 16 bytes per lane (6.04 / 6.02 / 6.02 ms for 32 GiB), and an 8-byte form of this kernel (512
@@ -31,7 +50,8 @@
 //     cda1552) was 7 % slower: the 96 extra vector instructions per job pair cost more than the shorter request stream saves.
 //   * per workgroup (4 waves): LDS = 8 KB inter-pass twiddles W_1024^(a*b) + 8 KB filter spectrum + 8 x 4.1 KB
 //     transpose buffers = 49 KB; two workgroups per CU (the prefetch registers allow two waves per SIMD).
-// HBM traffic: 4 B read + 4 B written per sample, nothing re-read (PMC: profiles/pmc_traffic.json).
+// HBM traffic: 4 B read + 4 B written per sample; the super-block walk's halo re-reads measure +0.4 % (PMC:
+// profiles/pmc_traffic.json, profiles/r04/rocprof_headline_before_after.txt).
 // The steps of the 1024-point walk (geometry, request, assemble, transform, store) and the launch plan live in ols_walk.hpp:
 // fir_bank.hip walks the same way with a spectrum per channel.
 #include <stdlib.h>
@@ -64,6 +84,7 @@ __device__ __forceinline__ ols_smem ols_tables(char *smem, const float2 *__restr
     return m;
 }
 
+// The segment walk (small batches, rows or pitches that are not 32 KB-aligned; fir_bank.hip walks the same way).
 // A half-wave runs one segment after the other (grid stride over segment pairs), with the prefetch carried ACROSS segments: the
 // last job of a segment requests the first job and the halo of the half-wave's NEXT segment, so every load is used and no
 // segment start waits on memory (a first form requested past the segment's end and discarded the data: 1/16 of the input
@@ -71,7 +92,7 @@ __device__ __forceinline__ ols_smem ols_tables(char *smem, const float2 *__restr
 // channels x 63 taps).  Both halves of a wave step through their segments together (a segment that is short at the end of a
 // channel idles its tail).
 __global__ void __launch_bounds__(OLS_THREADS, 2)
-k_fir_ols_chain_f32(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ hist,
+k_fir_ols_seg_f32(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ hist,
                     const float2 *__restrict__ hfreq, const float2 *__restrict__ twid, ols_geom G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -133,6 +154,82 @@ k_fir_ols_chain_f32(const float *__restrict__ in, float *__restrict__ out, const
         cur[1] = nxt[1];
 #pragma unroll
         for (int i = 0; i < 8; i++) halo[i] = halo_n[i];
+    }
+}
+
+// The headline form: the SUPER-BLOCK walk (ols_superblock.h).  A half-wave owns 16384 consecutive samples of a channel, 64 KB
+// aligned to 64 KB, as two 32 KB regions walked side by side: the real part of a transform is a block of region 0, the imaginary
+// part the same block of region 1 (the two blocks packed into one complex transform can come from anywhere), so the half-wave's
+// request stream is two sub-streams exactly 32 KB apart, each a 32 KB-aligned run of 32 KB -- the shape the walk-copy
+// micro-benchmarks single out (profiles/r02/ubench_walk_substreams.txt, profiles/r04/ubench_ols_io_superblock.txt); the segment
+// walk's runs are 96 KB at a 96 KB stride, never aligned.  11 jobs per super-block: ten full ones in one loop (8 carried + 24
+// requested rows per sub-stream), then the short one, peeled (8 carried + 16 requested rows, 16 stored: a region is 10 2/3 blocks).  Two
+// carried overlaps, one per sub-stream.  The chain across units is the segment walk's: the short job requests job 0 and both
+// halos of the half-wave's next super-block; both halves of a wave step together; a ragged last super-block of a row runs all
+// 11 jobs on clamped requests and bounded stores (a dead region 1 is an all-zero imaginary part).  The launcher takes this
+// form only where rows and pitches keep the regions 32 KB-aligned and the batch fills the machine (ols_sb_applies).
+__global__ void __launch_bounds__(OLS_THREADS, 2)
+k_fir_ols_chain_f32(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ hist,
+                    const float2 *__restrict__ hfreq, const float2 *__restrict__ twid, ols_geom G /* a segment = a super-block */)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ols_smem S = ols_tables(smem, hfreq, twid);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l5 = lane & 31;
+    const ols_lane g = ols_lane_of(lane);
+    const long halves_total = (long)gridDim.x * OLS_WAVES * 2;
+    const long first = ((long)blockIdx.x * OLS_WAVES + wave) * 2;
+
+    ols_seg cur[2] = {ols_locate(first, G), ols_locate(first + 1, G)};           // j0 = the super-block's index in its channel
+    float halo[16];
+    ols_raw raw;
+    {
+        const float *const row[2] = {in + (size_t)cur[0].c * G.in_pitch, in + (size_t)cur[1].c * G.in_pitch};
+        const ols_seg own = g.half ? cur[1] : cur[0];
+        ols_sb_load_halo(halo, g.half ? row[1] : row[0], hist ? hist + (size_t)own.c * G.keep : nullptr, own.j0 * OLS_SB_UNIT,
+                         g.col, G.keep, G.n, own.live);
+        const int s0[2] = {cur[0].j0 * OLS_SB_UNIT, cur[1].j0 * OLS_SB_UNIT};
+        const bool lv[2] = {cur[0].live, cur[1].live};
+        ols_sb_load<24>(raw, row, s0, lv, lv[0] && lv[1] && ols_sb_whole(s0[0], G.n) && ols_sb_whole(s0[1], G.n), g, G.n);
+    }
+    for (long sp = first; sp < G.total_segs; sp += halves_total) {
+        const ols_seg nxt[2] = {ols_locate(sp + halves_total, G), ols_locate(sp + halves_total + 1, G)};
+        const float *const row[2] = {in + (size_t)cur[0].c * G.in_pitch, in + (size_t)cur[1].c * G.in_pitch};
+        float *const orow[2] = {out + (size_t)cur[0].c * G.out_pitch, out + (size_t)cur[1].c * G.out_pitch};
+        const int s[2] = {cur[0].j0 * OLS_SB_UNIT, cur[1].j0 * OLS_SB_UNIT};
+        const bool live[2] = {cur[0].live, cur[1].live};
+        const bool whole = live[0] && live[1] && ols_sb_whole(s[0], G.n) && ols_sb_whole(s[1], G.n);   // wave-uniform
+
+#pragma unroll 1
+        for (int jj = 0; jj < OLS_SB_FULL_JOBS; jj++) {
+            cf v[32], u[32];
+            ols_sb_assemble_full(v, halo, raw);
+            // the next job of this super-block pair: a full one, or -- after job 9 -- the short one's 16 rows
+            const int sn[2] = {s[0] + ols_sb_request(jj + 1), s[1] + ols_sb_request(jj + 1)};
+            if (jj + 1 < OLS_SB_FULL_JOBS) ols_sb_load<24>(raw, row, sn, live, whole, g, G.n);
+            else ols_sb_load<16>(raw, row, sn, live, whole, g, G.n);
+            ols_filter(v, u, S.buf, S.tw, S.h, l5, g.col);
+            const int w[2] = {s[0] + ols_sb_window(jj), s[1] + ols_sb_window(jj)};
+            ols_sb_store<8>(u, orow, w, live, whole, g, G.n);
+        }
+        {
+            cf v[32], u[32];
+            ols_sb_assemble_short(v, halo, raw);
+            // job 0 and both halos of the half-wave's next super-block (an idle half requests nothing it uses)
+            const float *const nrow[2] = {in + (size_t)nxt[0].c * G.in_pitch, in + (size_t)nxt[1].c * G.in_pitch};
+            const ols_seg nown = g.half ? nxt[1] : nxt[0];
+            const int sn[2] = {nxt[0].j0 * OLS_SB_UNIT, nxt[1].j0 * OLS_SB_UNIT};
+            const bool ln[2] = {nxt[0].live, nxt[1].live};
+            ols_sb_load<24>(raw, nrow, sn, ln, ln[0] && ln[1] && ols_sb_whole(sn[0], G.n) && ols_sb_whole(sn[1], G.n), g, G.n);
+            ols_sb_load_halo(halo, g.half ? nrow[1] : nrow[0], hist ? hist + (size_t)nown.c * G.keep : nullptr, g.half ? sn[1] : sn[0],
+                             g.col, G.keep, G.n, nown.live);
+            ols_filter(v, u, S.buf, S.tw, S.h, l5, g.col);
+            const int w[2] = {s[0] + ols_sb_window(OLS_SB_FULL_JOBS), s[1] + ols_sb_window(OLS_SB_FULL_JOBS)};
+            ols_sb_store<16>(u, orow, w, live, whole, g, G.n);
+        }
+        cur[0] = nxt[0];
+        cur[1] = nxt[1];
     }
 }
 
@@ -815,7 +912,7 @@ const ols_rung OLS_RUNGS[] = {
     // two workgroups per CU: 49 KB of LDS and ~240 registers per lane
     {1024, 1, "k_fir_ols_f32", OLS_THREADS, 2 * OLS_WAVES, 2, true, 1.0,
      2 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float), false, false,
-     1, {OLS_OVERLAP}, {kfn(k_fir_ols_chain_f32)}},
+     1, {OLS_OVERLAP}, {kfn(k_fir_ols_seg_f32)}},
     {2048, 2, "k_fir_ols2k_chain_f32", OLS_THREADS, OLS_WAVES, 2, false, 1.0,
      4 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float), true, false,
      2, {512, 1024}, {kfn(k_fir_ols2k_chain_f32<512>), kfn(k_fir_ols2k_chain_f32<1024>)}},
@@ -834,6 +931,28 @@ const ols_rung OLS_RUNGS[] = {
      {kfn(k_fir_ols8k_f32<1536>), kfn(k_fir_ols8k_f32<2304>), kfn(k_fir_ols8k_f32<2560>), kfn(k_fir_ols8k_f32<3072>),
       kfn(k_fir_ols8k_f32<3584>), kfn(k_fir_ols8k_f32<4096>), kfn(k_fir_ols8k_f32<5120>), kfn(k_fir_ols8k_f32<6144>)}},
 };
+
+// The super-block walk is taken where it can be aligned and can fill the machine: row bases and pitches that are multiples of
+// 32 KB, and a batch large by the test that keeps the segment walk at its full segment length (small batches -- BASELINE config
+// 2 -- quantise badly into 64 KB units).  The ols_superblock tune: unset = this choice, 1 = also on small batches (never without
+// the alignment), 0 = the segment walk.  An ols_seg_len tune asks for the segment walk as well.
+bool ols_sb_applies(const ols_plan &p, const float *in, const float *out, long in_pitch, long out_pitch, int n)
+{
+    const int t = llzs_tune(LLZS_TUNE_OLS_SUPERBLOCK);
+    if (t == 0 || !ols_sb_aligned(in, out, in_pitch, out_pitch) || n > INT32_MAX - 2 * OLS_SB_UNIT) return false;
+    return t == 1 || (p.large && llzs_tune(LLZS_TUNE_OLS_SEG_LEN) < 0);
+}
+
+// a "segment" of the geometry becomes a super-block: one per ols_locate, numbered channel-major
+void ols_sb_plan(ols_plan &p, int channels, int n)
+{
+    ols_geom &G = p.G;
+    G.seg_len = 1;
+    G.jobs_per_channel = G.segs_per_channel = ols_sb_units_per_channel(n);
+    G.total_segs = ols_sb_total(channels, n);
+    p.blocks = (G.total_segs + 2 * OLS_WAVES - 1) / (2 * OLS_WAVES);
+    if (p.blocks > p.max_blocks) p.blocks = p.max_blocks;
+}
 
 } // namespace
 
@@ -862,11 +981,25 @@ extern "C" int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float 
     if (r->w4k) args[k++] = &w4;
     args[k] = &p.G;
     const void *kernel = r->kernel[p.instance];
+    if (r->nfft == 1024 && ols_sb_applies(p, in, out, in_pitch, out_pitch, n)) {
+        ols_sb_plan(p, channels, n);
+        kernel = kfn(k_fir_ols_chain_f32);
+    }
     if (r->lds_bytes > 64 * 1024)
         LLZ_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
     (void)hipLaunchKernel(kernel, dim3((unsigned)p.blocks), dim3(r->threads), args, r->lds_bytes, as_stream(stream));
     LLZ_LAUNCH_CHECK(r->name);
     return LLZ_OK;
+}
+
+extern "C" int llzs_fir_ols_superblock(const float *in, const float *out, int channels, int n, long in_pitch, long out_pitch,
+                                       int flt_len)
+{
+    const ols_rung &r = OLS_RUNGS[0];
+    if (channels <= 0 || n <= 0 || in_pitch < n || out_pitch < n || flt_len < r.min_taps || flt_len - 1 > r.overlap[r.count - 1])
+        return 0;
+    const ols_plan p = ols_plan_of(r, channels, n, in_pitch, out_pitch, flt_len);
+    return ols_sb_applies(p, in, out, in_pitch, out_pitch, n) ? 1 : 0;
 }
 
 #ifdef O8K_TRACE

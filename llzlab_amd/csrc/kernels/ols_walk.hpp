@@ -4,6 +4,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft32.hpp"
+#include "ols_superblock.h"
 
 namespace {
 
@@ -178,6 +179,87 @@ __device__ __forceinline__ void ols_assemble(cf (&v)[32], float (&halo)[8], cons
     }
 }
 
+// ---- the super-block walk (ols_superblock.h has the geometry; fir_ols.hip's k_fir_ols_chain_f32 walks it) ----
+
+// request ROWS rows of both sub-streams of the wave's two super-blocks: half h takes rows from sample s[h] of region 0 and
+// from OLS_SB_REGION further on, the requests alternating between the two places.  whole (wave-uniform): both super-blocks lie
+// inside their rows.
+template <int ROWS>
+__device__ __forceinline__ void ols_sb_load(ols_raw &raw, const float *const (&row)[2], const int (&s)[2], const bool (&live)[2],
+                                            bool whole, const ols_lane &g, int n)
+{
+    const float *r = g.half ? row[1] : row[0];
+    const int so = g.half ? s[1] : s[0];
+    const bool lv = g.half ? live[1] : live[0];
+    if (whole) {
+#pragma unroll
+        for (int i = 0; i < ROWS; i++) {
+            raw.a[i] = __builtin_nontemporal_load(&r[so + OLS_SB_ROW * i + g.col]);
+            raw.b[i] = __builtin_nontemporal_load(&r[so + OLS_SB_REGION + OLS_SB_ROW * i + g.col]);
+        }
+    } else {
+        // a ragged last super-block (region 1 short or absent) or an idle half
+#pragma unroll
+        for (int i = 0; i < ROWS; i++) {
+            const int ia = so + OLS_SB_ROW * i + g.col;
+            const ols_sb_ref ra = ols_sb_sample(ia, n, lv), rb = ols_sb_sample(ia + OLS_SB_REGION, n, lv);
+            const float xa = r[ra.addr], xb = r[rb.addr];
+            raw.a[i] = ra.use ? xa : 0.f;
+            raw.b[i] = rb.use ? xb : 0.f;
+        }
+    }
+}
+
+// the 256 samples in front of both regions of the super-block at sample s: halo[0..7] region 0's (the row, or the history /
+// zeros at s == 0), halo[8..15] region 1's (the tail of region 0)
+__device__ __forceinline__ void ols_sb_load_halo(float (&halo)[16], const float *row, const float *hrow, int s, int col, int keep,
+                                                 int n, bool live)
+{
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int idx = s - OLS_SB_HALO + OLS_SB_ROW * i + col;
+        const ols_sb_href ha = ols_sb_halo_sample(idx, n, keep, live, hrow != nullptr);
+        const ols_sb_href hb = ols_sb_halo_sample(idx + OLS_SB_REGION, n, keep, live, false);
+        float va = 0.f, vb = 0.f;
+        if (ha.src == OLS_SB_FROM_ROW) va = row[ha.addr];
+        else if (ha.src == OLS_SB_FROM_HIST) va = hrow[ha.addr];
+        if (hb.src == OLS_SB_FROM_ROW) vb = row[hb.addr];
+        halo[i] = va;
+        halo[8 + i] = vb;
+    }
+}
+
+// keep the rows >= CARRY of both blocks; w[h] = the first sample of half h's block of region 0 (region 1's is OLS_SB_REGION on)
+template <int CARRY>
+__device__ __forceinline__ void ols_sb_store(const cf (&u)[32], float *const (&orow)[2], const int (&w)[2], const bool (&live)[2],
+                                             bool whole, const ols_lane &g, int n)
+{
+    const bool lv = g.half ? live[1] : live[0];
+    if (!lv) return;
+    float *o = g.half ? orow[1] : orow[0];
+    const int oa = (g.half ? w[1] : w[0]) + g.col;        // + 32*n1
+    const int ob = oa + OLS_SB_REGION;
+    if (whole) {
+#pragma unroll
+        for (int r = 0; r < 32; r++) {
+            const int n1 = brev5(r);
+            if (n1 >= CARRY) {
+                __builtin_nontemporal_store(u[r].x, &o[oa + OLS_SB_ROW * n1]);
+                __builtin_nontemporal_store(u[r].y, &o[ob + OLS_SB_ROW * n1]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 32; r++) {
+            const int n1 = brev5(r);
+            if (n1 >= CARRY) {
+                if (oa + OLS_SB_ROW * n1 < n) o[oa + OLS_SB_ROW * n1] = u[r].x;
+                if (ob + OLS_SB_ROW * n1 < n) o[ob + OLS_SB_ROW * n1] = u[r].y;
+            }
+        }
+    }
+}
+
 // ---- launch plan (host) ----
 
 // one overlap-save size: how its segments map onto workgroups, and the kernel instance built for each overlap
@@ -200,7 +282,8 @@ template <typename K> static const void *kfn(K k) { return reinterpret_cast<cons
 
 struct ols_plan {
     int instance;               // index into the rung's overlaps
-    long blocks;
+    long blocks, max_blocks;    // workgroups launched; one resident set
+    bool large;                 // the batch fills the machine with full-length segments
     ols_geom G;
 };
 
@@ -226,7 +309,9 @@ static ols_plan ols_plan_of(const ols_rung &r, int channels, int n, long in_pitc
     // with the full length, so they take the length that minimises the cost in rounds.  Large batches keep the full length:
     // on 4096 channels a shorter segment measured 2.6 % slower (1024 points).
     int seg_len = OLS_SEG;
-    if ((long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels < 4 * slots) {
+    p.max_blocks = max_blocks;
+    p.large = (long)((G.jobs_per_channel + OLS_SEG - 1) / OLS_SEG) * channels >= 4 * slots;
+    if (!p.large) {
         double best = 1e300;
         for (int sl = OLS_SEG; sl >= 1; sl--) {
             const long segs = (long)((G.jobs_per_channel + sl - 1) / sl) * channels;

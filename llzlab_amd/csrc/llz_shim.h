@@ -60,6 +60,8 @@ enum {
                                      * measured against and dropped: fir_bank.hip) instead of a half-wave's own LDS image */
     LLZS_TUNE_PART_NFFT,            /* partitioned overlap-save: transform points (1024, 2048, 4096, 8192), read at init */
     LLZS_TUNE_PART_SCRATCH_MB,      /* ... cap of the spectra scratch in MiB (1 .. 1024; the library's own: 1024), read at init and per call */
+    LLZS_TUNE_OLS_SUPERBLOCK,       /* 1024-point overlap-save on large batches with 32 KB-aligned rows: 1 = the super-block walk
+                                     * on small batches too (never without the alignment), 0 = the segment walk */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -114,6 +116,9 @@ typedef struct {
 } llzs_ols_tables;
 int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float *in, float *out, const float *hist, int channels,
                      int n, long in_pitch, long out_pitch, int flt_len, void *stream);
+/* 1 when the 1024-point call of this shape takes the super-block walk (k_fir_ols_chain_f32), 0 for the segment walk: the
+ * launcher's own decision under the tunes set now, for tests and measurement tools; nothing is launched */
+int llzs_fir_ols_superblock(const float *in, const float *out, int channels, int n, long in_pitch, long out_pitch, int flt_len);
 /* 1024-point overlap-save with a spectrum per channel (fir_bank.hip), 1..257 taps: hbank = [channels][LLZS_BANK_PITCH] complex
  * floats, row c = bins 0..512 of DFT_1024(taps of channel c) / 1024 (the taps are real: the kernel mirrors the rest), the
  * row's tail unused; twid as above */
