@@ -24,6 +24,8 @@ OVERLAP_HIGH, OVERLAP_LOW = 0, 1      # llz_asmodel.h: 3/4 and 1/2 overlap
 MDCT_ORIGIN, MDCT_FFT, MDCT_FFT4 = 0, 1, 2
 MDCT_SINE, MDCT_KBD = 0, 1
 PCM_F32, PCM_I16, PCM_I16_FAST = 0, 1, 2
+CSD_RUN = 32                          # llz_spectral.h: LLZ_CSD_RUN
+SPEC_PXX, SPEC_PYY, SPEC_CSD, SPEC_COHERENCE, SPEC_TF = 0, 1, 2, 3, 4
 
 _lib = None
 
@@ -251,6 +253,16 @@ def lib():
     sig("llz_crosscorr_fast_mc_uninit", None, ul)
     sig("llz_crosscorr_fast_mc", i, ul, vp, vp, vp, i, i)
     sig("llz_crosscorr_fast_mc_set_stream", i, ul, vp)
+    # llz_spectral.h
+    sig("llz_csd_mc_init", ul, i, i, C.POINTER(C.c_int), i, i, i)
+    sig("llz_csd_mc_uninit", None, ul)
+    sig("llz_csd_mc_set_stream", i, ul, vp)
+    sig("llz_csd_mc_update", lng, ul, vp, lng)
+    sig("llz_csd_mc_frames", lng, ul)
+    sig("llz_csd_mc_read", i, ul, i, vp)
+    sig("llz_csd_mc_read_raw", i, ul, vp)
+    sig("llz_csd_mc_reset", i, ul)
+    sig("llz_csd_mc_plan", i, ul, lng, C.POINTER(C.c_int))
     sig("llz_levinson", None, dp, i, dp, dp, dp)
     sig("llz_levinson1", None, dp, i, dp, dp, dp)
     sig("llz_atlvs", i, dp, i, dp, dp, dp, dp)

@@ -62,6 +62,7 @@ enum {
     LLZS_TUNE_PART_SCRATCH_MB,      /* ... cap of the spectra scratch in MiB (1 .. 1024; the library's own: 1024), read at init and per call */
     LLZS_TUNE_OLS_SUPERBLOCK,       /* 1024-point overlap-save on large batches with 32 KB-aligned rows: 1 = the super-block walk
                                      * on small batches too (never without the alignment), 0 = the segment walk */
+    LLZS_TUNE_CSD_SCRATCH_KB,       /* llz_csd_mc: cap of the run-partial scratch in KiB (the library's own: 256 MiB), read per call */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -379,6 +380,27 @@ int llzs_acf_power(float *z, int frames, int n, int F, void *stream);
 int llzs_acf_extract(const float *z, float *r, int frames, int p, int F, void *stream);
 /* the same five steps fused in LDS (acf_fft.hip): one read of the frames, p+1 floats written per frame */
 int llzs_acf_fused_f32(const float *x, float *r, int frames, int n, int p, int size, const float *cs, void *stream);
+
+/* ---- Welch cross-spectra (csd.hip; include/llz_spectral.h) ----
+ * Frames are counted from the handle's last reset; frame f covers samples [(f - hops0) hop, (f - hops0) hop + fft_len) of the
+ * call's x ([channels][x_pitch]), negative indices in hist ([channels][fft_len - hop], the samples in front of the call; may be
+ * NULL when hop == fft_len), hops0 = the hops taken before the call.  The call holds frames [f_lo, f_hi); run r = frames
+ * [32 r, 32 r + 32).  One launch walks the runs [r0, r0 + nruns) of every pair: a run that began before f_lo starts from
+ * carry_in ([2][pairs][bins][4] floats: Sxx, Syy, Re Sxy, Im Sxy, then the compensation terms of these compensated float32
+ * sums), a run that ends behind f_hi goes to carry_out, ANOTHER buffer of that layout (both can happen in one launch, in work
+ * items that nothing orders), a finished run's sums go to scratch slot (r - r0) of [nruns][pairs][bins][4] floats.  pair_xy:
+ * [pairs][2] channel indices, checked by the caller.
+ * w: fft_len window floats; cs: cos then sin of 2 pi i / fft_len.  fft_len 64..4096, hop fft_len, fft_len / 2 or fft_len / 4. */
+int llzs_csd_form(int fft_len);         /* 1: the register form serves this size under the tunes set now, 0: the staged form */
+int llzs_csd_runs_f32(const float *x, const float *hist, const float *w, const float *cs, const int *pair_xy, float *scratch,
+                      const float *carry_in, float *carry_out, int pairs, int fft_len, int hop, long x_pitch, long hops0, long f_lo, long f_hi, long r0,
+                      int nruns, void *stream);
+/* acc ([pairs][bins][4] doubles) += the first nfin slots of scratch, in slot order */
+int llzs_csd_fold_f64(const float *scratch, double *acc, int pairs, int bins, int nfin, void *stream);
+/* the read-outs from acc + the sums in carry (its first [pairs][bins][4]; NULL: no run is open), in double, rounded once: what 0..4 = LLZ_SPEC_PXX .. LLZ_SPEC_TF
+ * into out ([pairs][bins] floats, CSD and TF [pairs][bins][2]), ku = frames x sum w^2; what 5: the four sums into raw */
+int llzs_csd_read_f64(const double *acc, const float *carry, int pairs, int bins, int what, double ku, float *out, double *raw,
+                      void *stream);
 
 /* ---- linear prediction (lpc.hip) ---- */
 /* LPC of frames x n float32 (0 <= p <= 32): the correlation of llzs_autocorr_mc_f32 (the same bits; on x*win when win is not

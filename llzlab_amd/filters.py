@@ -848,6 +848,84 @@ class CrosscorrFastMC:
     __del__ = close
 
 
+# ------------------------------------------------------------------------------------------ Welch cross-spectra
+class CsdMC:
+    """llz_csd_mc_*: the averaged cross-spectra of channel pairs (include/llz_spectral.h).  pairs_xy: [(x, y), ...] channel
+    indices; update(x) takes planar [channels, n] float32 (n a multiple of hop; a device tensor or a numpy array) and returns
+    the frames summed so far.  The read-outs fill `out` when given (device or host) or return a new numpy array: psd_x, psd_y,
+    coherence [pairs, bins] float32; csd, transfer [pairs, bins, 2] float32 (re, im); raw [pairs, bins, 4] float64 (Sxx, Syy,
+    Re Sxy, Im Sxy).  PSD and CSD are two-sided values over bins 0 .. fft_len / 2."""
+
+    def __init__(self, channels, pairs_xy, fft_len, hop, win=HAMMING, stream=None):
+        self._L = capi.lib()
+        table = np.ascontiguousarray(pairs_xy, dtype=np.int32).reshape(-1, 2)
+        self.channels, self.pairs, self.fft_len, self.hop = channels, len(table), fft_len, hop
+        self.bins = fft_len // 2 + 1
+        self.handle = check_handle(self._L.llz_csd_mc_init(channels, self.pairs, table.ctypes.data_as(C.POINTER(C.c_int)),
+                                                           fft_len, hop, win), "llz_csd_mc_init")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_csd_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_csd_mc_set_stream")
+
+    def update(self, x):
+        size = x.numel() if hasattr(x, "numel") else x.size
+        n, rem = divmod(size, self.channels)
+        if rem:
+            raise LlzError(f"llz_csd_mc_update: {size} samples do not divide into {self.channels} channels")
+        return check(self._L.llz_csd_mc_update(self.handle, _typed(x, "float32", size, "x"), n), "llz_csd_mc_update")
+
+    def frames(self):
+        return check(self._L.llz_csd_mc_frames(self.handle), "llz_csd_mc_frames")
+
+    def _read(self, what, width, out):
+        shape = (self.pairs, self.bins) + ((width,) if width > 1 else ())
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        check(self._L.llz_csd_mc_read(self.handle, what, _typed(out, "float32", self.pairs * self.bins * width, "out")),
+              "llz_csd_mc_read")
+        return out
+
+    def psd_x(self, out=None):
+        return self._read(capi.SPEC_PXX, 1, out)
+
+    def psd_y(self, out=None):
+        return self._read(capi.SPEC_PYY, 1, out)
+
+    def csd(self, out=None):
+        return self._read(capi.SPEC_CSD, 2, out)
+
+    def coherence(self, out=None):
+        return self._read(capi.SPEC_COHERENCE, 1, out)
+
+    def transfer(self, out=None):
+        return self._read(capi.SPEC_TF, 2, out)
+
+    def raw(self, out=None):
+        if out is None:
+            out = np.empty((self.pairs, self.bins, 4), dtype=np.float64)
+        check(self._L.llz_csd_mc_read_raw(self.handle, _typed(out, "float64", self.pairs * self.bins * 4, "out")),
+              "llz_csd_mc_read_raw")
+        return out
+
+    def reset(self):
+        check(self._L.llz_csd_mc_reset(self.handle), "llz_csd_mc_reset")
+
+    def plan(self, n):
+        """what update() of n samples per channel would run now: {"form": 0 staged / 1 register, "run", "runs_per_walk", "walks"}"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_csd_mc_plan(self.handle, n, out), "llz_csd_mc_plan")
+        return dict(zip(("form", "run", "runs_per_walk", "walks"), (int(v) for v in out)))
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_csd_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ linear prediction
 LEVINSON_ORDER_MAX = 64
 
