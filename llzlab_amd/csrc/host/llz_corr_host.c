@@ -46,7 +46,8 @@ double llz_corr_cof(double *a, double *b, int len)
 }
 
 typedef struct {
-    int tag, n, fft_len;
+    llz_head_t head;            /* no device memory of its own: the llz_fft handle's */
+    int n, fft_len;
     unsigned long h_fft;
     double *b1, *b2;
 } acf1_t;
@@ -68,9 +69,9 @@ unsigned long llz_autocorr_fast_init(int n)
         llzs_set_error("llz_autocorr_fast_init: n=%d (1..2048)", n);
         return LLZ_BAD_HANDLE;
     }
-    acf1_t *f = (acf1_t *)calloc(1, sizeof(*f));
+    acf1_t *f = (acf1_t *)llz_handle_new(sizeof(*f), LLZ_TAG_ACF1, 0);
     if (!f) return LLZ_BAD_HANDLE;
-    f->tag = LLZ_TAG_ACF1; f->n = n; f->fft_len = acf_fft_len(n);
+    f->n = n; f->fft_len = acf_fft_len(n);
     f->h_fft = llz_fft_init(f->fft_len);
     f->b1 = (double *)calloc(2 * (size_t)f->fft_len, sizeof(double));
     f->b2 = (double *)calloc(2 * (size_t)f->fft_len, sizeof(double));
@@ -84,21 +85,21 @@ unsigned long llz_autocorr_fast_init(int n)
 
 void llz_autocorr_fast_uninit(unsigned long handle)
 {
-    if (!LLZ_HANDLE_OK(handle, acf1_t, LLZ_TAG_ACF1)) return;
-    acf1_t *f = (acf1_t *)handle;
+    acf1_t *f = (acf1_t *)llz_handle(handle, LLZ_TAG_ACF1, NULL);
+    if (!f) return;
     llz_fft_uninit(f->h_fft);
     free(f->b1); free(f->b2);
-    f->tag = 0;
+    f->head.tag = 0;
     free(f);
 }
 
 void llz_autocorr_fast(unsigned long handle, double *x, int n, int p, double *r)
 {
-    if (!LLZ_HANDLE_OK(handle, acf1_t, LLZ_TAG_ACF1) || !x || !r || n < 1 || p < 0) {
+    acf1_t *f = (acf1_t *)llz_handle(handle, LLZ_TAG_ACF1, NULL);
+    if (!f || !x || !r || n < 1 || p < 0) {
         llzs_set_error("llz_autocorr_fast: bad handle or arguments");
         return;
     }
-    acf1_t *f = (acf1_t *)handle;
     if (n > f->fft_len / 2 || p >= f->fft_len) {
         llzs_set_error("llz_autocorr_fast: n=%d / p=%d do not fit fft_len %d", n, p, f->fft_len);
         return;
@@ -123,40 +124,10 @@ int llz_autocorr_mc(const float *x, float *r, int frames, int n, int p, void *st
         return LLZ_ERR_ARG;
     }
     const size_t xb = sizeof(float) * (size_t)frames * n, rb = sizeof(float) * (size_t)frames * (p + 1);
-    const int x_dev = llzs_is_device_ptr(x), r_dev = llzs_is_device_ptr(r);
-    if (x_dev < 0 || r_dev < 0) return LLZ_ERR_ARG;               /* device memory of a GPU that is not current */
-    if (llz_refuse_device_overlap("llz_autocorr_mc", "x", x, xb, x_dev, "r", r, rb, r_dev)) return LLZ_ERR_ARG;
-    float *d_x = (float *)x, *d_r = r;
-    int rc = LLZ_OK;
-    if (!x_dev) {
-        d_x = (float *)llzs_malloc(xb);
-        rc = d_x ? llzs_h2d(d_x, x, xb, stream) : LLZ_ERR_NOMEM;
-    }
-    if (rc == LLZ_OK && !r_dev) {
-        d_r = (float *)llzs_malloc(rb);
-        if (!d_r) rc = LLZ_ERR_NOMEM;
-    }
-    if (rc == LLZ_OK) rc = llzs_autocorr_mc_f32(d_x, d_r, frames, n, p, stream);
-    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, stream);
-    if (!x_dev) { llzs_sync(stream); llzs_free(d_x); }
-    if (!r_dev) llzs_free(d_r);
-    return rc;
-}
-
-/* a caller's float buffer for a kernel: device memory is used where it lies, host memory goes through a device copy (inputs
- * are uploaded); *d is the pointer to launch with.  corr_unstage frees what corr_stage allocated. */
-static int corr_stage(const float *user, size_t bytes, int dev, int upload, float **d, void *stream)
-{
-    *d = (float *)user;
-    if (dev) return LLZ_OK;
-    *d = (float *)llzs_malloc(bytes);
-    if (!*d) return LLZ_ERR_NOMEM;
-    return upload ? llzs_h2d(*d, user, bytes, stream) : LLZ_OK;
-}
-
-static void corr_unstage(const float *user, float *d)
-{
-    if (d && d != user) llzs_free(d);
+    llz_bind_t b[2] = {{"x", x, xb, LLZ_BIND_IN, NULL, 0, 0}, {"r", r, rb, LLZ_BIND_OUT, NULL, 0, 0}};
+    int rc = llz_bind("llz_autocorr_mc", b, 2, stream);
+    if (rc == LLZ_OK) rc = llzs_autocorr_mc_f32((const float *)b[0].dev, (float *)b[1].dev, frames, n, p, stream);
+    return llz_bind_finish(b, 2, stream, rc);
 }
 
 int llz_crosscorr_mc(const float *x, const float *y, float *r, int frames, int n, int p, int two_sided, void *stream)
@@ -168,25 +139,13 @@ int llz_crosscorr_mc(const float *x, const float *y, float *r, int frames, int n
     }
     const size_t xb = sizeof(float) * (size_t)frames * n;
     const size_t rb = sizeof(float) * (size_t)frames * (two_sided ? 2 * (size_t)p + 1 : (size_t)p + 1);
-    const int x_dev = llzs_is_device_ptr(x), y_dev = llzs_is_device_ptr(y), r_dev = llzs_is_device_ptr(r);
-    if (x_dev < 0 || y_dev < 0 || r_dev < 0) return LLZ_ERR_ARG;  /* device memory of a GPU that is not current */
-    if (llz_refuse_device_overlap("llz_crosscorr_mc", "x", x, xb, x_dev, "r", r, rb, r_dev) ||
-        llz_refuse_device_overlap("llz_crosscorr_mc", "y", y, xb, y_dev, "r", r, rb, r_dev))
-        return LLZ_ERR_ARG;
-    float *d_x = NULL, *d_y = NULL, *d_r = NULL;
-    int rc = corr_stage(x, xb, x_dev, 1, &d_x, stream);
-    if (rc == LLZ_OK) {
-        if (y == x) d_y = d_x;                                      /* one row: one copy, and the one-row kernels */
-        else rc = corr_stage(y, xb, y_dev, 1, &d_y, stream);
-    }
-    if (rc == LLZ_OK) rc = corr_stage(r, rb, r_dev, 0, &d_r, stream);
-    if (rc == LLZ_OK) rc = llzs_crosscorr_mc_f32(d_x, d_y, d_r, frames, n, p, two_sided, stream);
-    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, stream);
-    if (!x_dev || !y_dev) llzs_sync(stream);                       /* the kernels are done with the copies */
-    if (y != x) corr_unstage(y, d_y);
-    corr_unstage(x, d_x);
-    corr_unstage(r, d_r);
-    return rc;
+    llz_bind_t b[3] = {{"x", x, xb, LLZ_BIND_IN, NULL, 0, 0}, {"y", y, xb, LLZ_BIND_IN, NULL, 0, 0},
+                       {"r", r, rb, LLZ_BIND_OUT, NULL, 0, 0}};
+    int rc = llz_bind("llz_crosscorr_mc", b, 3, stream);
+    if (rc == LLZ_OK)
+        rc = llzs_crosscorr_mc_f32((const float *)b[0].dev, (const float *)b[1].dev, (float *)b[2].dev, frames, n, p, two_sided,
+                                   stream);
+    return llz_bind_finish(b, 3, stream, rc);
 }
 
 int llz_corr_cof_mc(const float *a, const float *b, float *c, int frames, int n, void *stream)
@@ -196,40 +155,26 @@ int llz_corr_cof_mc(const float *a, const float *b, float *c, int frames, int n,
         return LLZ_ERR_ARG;
     }
     const size_t ab = sizeof(float) * (size_t)frames * n, cb = sizeof(float) * (size_t)frames;
-    const int a_dev = llzs_is_device_ptr(a), b_dev = llzs_is_device_ptr(b), c_dev = llzs_is_device_ptr(c);
-    if (a_dev < 0 || b_dev < 0 || c_dev < 0) return LLZ_ERR_ARG;
-    if (llz_refuse_device_overlap("llz_corr_cof_mc", "a", a, ab, a_dev, "c", c, cb, c_dev) ||
-        llz_refuse_device_overlap("llz_corr_cof_mc", "b", b, ab, b_dev, "c", c, cb, c_dev))
-        return LLZ_ERR_ARG;
-    float *d_a = NULL, *d_b = NULL, *d_c = NULL;
-    int rc = corr_stage(a, ab, a_dev, 1, &d_a, stream);
-    if (rc == LLZ_OK) {
-        if (b == a) d_b = d_a;
-        else rc = corr_stage(b, ab, b_dev, 1, &d_b, stream);
-    }
-    if (rc == LLZ_OK) rc = corr_stage(c, cb, c_dev, 0, &d_c, stream);
-    if (rc == LLZ_OK) rc = llzs_corr_cof_mc_f32(d_a, d_b, d_c, frames, n, stream);
-    if (rc == LLZ_OK && !c_dev) rc = llzs_d2h(c, d_c, cb, stream);
-    if (!a_dev || !b_dev) llzs_sync(stream);
-    if (b != a) corr_unstage(b, d_b);
-    corr_unstage(a, d_a);
-    corr_unstage(c, d_c);
-    return rc;
+    llz_bind_t v[3] = {{"a", a, ab, LLZ_BIND_IN, NULL, 0, 0}, {"b", b, ab, LLZ_BIND_IN, NULL, 0, 0},
+                       {"c", c, cb, LLZ_BIND_OUT, NULL, 0, 0}};
+    int rc = llz_bind("llz_corr_cof_mc", v, 3, stream);
+    if (rc == LLZ_OK) rc = llzs_corr_cof_mc_f32((const float *)v[0].dev, (const float *)v[1].dev, (float *)v[2].dev, frames, n, stream);
+    return llz_bind_finish(v, 3, stream, rc);
 }
 
 typedef struct {
-    int tag, device, frames, n, fft_len;
+    llz_head_t head;
+    int frames, n, fft_len;
     float *d_cs;            /* fft_len cos then fft_len sin */
-    void *stream;
     llz_stage_t st_in, st_out;
 } acfm_t;
 
-static void acfm_destroy(acfm_t *f)
+static void acfm_destroy(void *p)
 {
-    if (!f) return;
+    acfm_t *f = (acfm_t *)p;
     llzs_free(f->d_cs);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
-    f->tag = 0;
+    f->head.tag = 0;
     free(f);
 }
 
@@ -239,67 +184,45 @@ unsigned long llz_autocorr_fast_mc_init(int frames, int n)
         llzs_set_error("llz_autocorr_fast_mc_init: frames %d n %d (4..2048)", frames, n);
         return LLZ_BAD_HANDLE;
     }
-    acfm_t *f = (acfm_t *)calloc(1, sizeof(*f));
+    acfm_t *f = (acfm_t *)llz_handle_new(sizeof(*f), LLZ_TAG_ACFM, 1);
     if (!f) return LLZ_BAD_HANDLE;
-    f->tag = LLZ_TAG_ACFM; f->device = llzs_device_get(); f->frames = frames; f->n = n; f->fft_len = acf_fft_len(n);
-    const int F = f->fft_len;
-    float *cs = (float *)malloc(sizeof(float) * 2 * (size_t)F);
-    int rc = cs ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) {
-        for (int i = 0; i < F; i++) {
-            const double ang = (double)(2 * M_PI * i) / F;
-            cs[i] = (float)cos(ang);
-            cs[F + i] = (float)sin(ang);
-        }
-        f->d_cs = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)F);
-        rc = f->d_cs ? llzs_h2d(f->d_cs, cs, sizeof(float) * 2 * (size_t)F, NULL) : LLZ_ERR_NOMEM;
-    }
-    free(cs);
-    if (rc != LLZ_OK) {
+    f->frames = frames; f->n = n; f->fft_len = acf_fft_len(n);
+    f->d_cs = llz_host_cs_f32(f->fft_len);
+    if (!f->d_cs) {
         acfm_destroy(f);
         return LLZ_BAD_HANDLE;
     }
     return (unsigned long)f;
 }
 
-void llz_autocorr_fast_mc_uninit(unsigned long handle)
-{
-    if (LLZ_HANDLE_OK(handle, acfm_t, LLZ_TAG_ACFM)) {
-        const int prev = llzs_device_enter(((acfm_t *)handle)->device);
-        llzs_sync(((acfm_t *)handle)->stream);
-        acfm_destroy((acfm_t *)handle);
-        llzs_device_leave(prev);
-    }
-}
+void llz_autocorr_fast_mc_uninit(unsigned long handle) { llz_handle_retire(handle, LLZ_TAG_ACFM, acfm_destroy); }
 
 int llz_autocorr_fast_mc_set_stream(unsigned long handle, void *stream)
 {
-    if (!LLZ_HANDLE_OK(handle, acfm_t, LLZ_TAG_ACFM)) return LLZ_ERR_ARG;
-    ((acfm_t *)handle)->stream = stream;
-    return LLZ_OK;
+    return llz_handle_set_stream(handle, LLZ_TAG_ACFM, "llz_autocorr_fast_mc_set_stream", stream);
 }
 
 int llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p)
 {
-    if (!LLZ_HANDLE_OK(handle, acfm_t, LLZ_TAG_ACFM) || !x || !r || p < 0) {
+    acfm_t *f = (acfm_t *)llz_handle(handle, LLZ_TAG_ACFM, NULL);
+    if (!f || !x || !r || p < 0) {
         llzs_set_error("llz_autocorr_fast_mc: bad handle or arguments");
         return LLZ_ERR_ARG;
     }
-    acfm_t *f = (acfm_t *)handle;
     if (p >= f->fft_len) {
         llzs_set_error("llz_autocorr_fast_mc: p=%d >= fft_len %d", p, f->fft_len);
         return LLZ_ERR_ARG;
     }
     const size_t xb = sizeof(float) * (size_t)f->frames * f->n, rb = sizeof(float) * (size_t)f->frames * (p + 1);
-    const int prev = llzs_device_enter(f->device);
+    const int prev = llzs_device_enter(f->head.device);
     const int x_dev = llzs_is_device_ptr(x), r_dev = llzs_is_device_ptr(r);
     int rc = (x_dev < 0 || r_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;     /* a buffer of another GPU: refused, message set */
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_autocorr_fast_mc", "x", x, xb, x_dev, "r", r, rb, r_dev);
-    const float *d_x = llz_stage_in(&f->st_in, x, xb, x_dev, f->stream, &rc);
+    const float *d_x = llz_stage_in(&f->st_in, x, xb, x_dev, f->head.stream, &rc);
     float *d_r = llz_stage_out(&f->st_out, r, rb, r_dev, &rc);
     /* pack -> FFT -> |X|^2 (first n bins) -> IFFT -> 2 Re, fused in LDS */
-    if (rc == LLZ_OK) rc = llzs_acf_fused_f32(d_x, d_r, f->frames, f->n, p, f->fft_len, f->d_cs, f->stream);
-    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->stream);
+    if (rc == LLZ_OK) rc = llzs_acf_fused_f32(d_x, d_r, f->frames, f->n, p, f->fft_len, f->d_cs, f->head.stream);
+    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->head.stream);
     llzs_device_leave(prev);
     return rc;
 }
@@ -309,20 +232,20 @@ int llz_autocorr_fast_mc(unsigned long handle, const float *x, float *r, int p)
 #define XCF_SCRATCH_BYTES ((size_t)256 << 20)      /* spectra scratch: at most this much, walked in slabs of frames */
 
 typedef struct {
-    int tag, device, frames, n, fft_len, slab;      /* slab: frames per walk of the scratch */
+    llz_head_t head;
+    int frames, n, fft_len, slab;                   /* slab: frames per walk of the scratch */
     float *d_cs;            /* fft_len cos then fft_len sin */
     float *d_z;             /* slab x fft_len complex */
-    void *stream;
     llz_stage_t st_x, st_y, st_out;
 } xcfm_t;
 
-static void xcfm_destroy(xcfm_t *f)
+static void xcfm_destroy(void *p)
 {
-    if (!f) return;
+    xcfm_t *f = (xcfm_t *)p;
     llzs_free(f->d_cs);
     llzs_free(f->d_z);
     llz_stage_release(&f->st_x); llz_stage_release(&f->st_y); llz_stage_release(&f->st_out);
-    f->tag = 0;
+    f->head.tag = 0;
     free(f);
 }
 
@@ -332,62 +255,31 @@ unsigned long llz_crosscorr_fast_mc_init(int frames, int n)
         llzs_set_error("llz_crosscorr_fast_mc_init: frames %d n %d (frames >= 1, n in 4..2048)", frames, n);
         return LLZ_BAD_HANDLE;
     }
-    xcfm_t *f = (xcfm_t *)calloc(1, sizeof(*f));
+    xcfm_t *f = (xcfm_t *)llz_handle_new(sizeof(*f), LLZ_TAG_XCFM, 1);
     if (!f) return LLZ_BAD_HANDLE;
-    f->tag = LLZ_TAG_XCFM; f->device = llzs_device_get(); f->frames = frames; f->n = n; f->fft_len = acf_fft_len(n);
-    const int F = f->fft_len;
-    const size_t per_frame = sizeof(float) * 2 * (size_t)F;
+    f->frames = frames; f->n = n; f->fft_len = acf_fft_len(n);
+    const size_t per_frame = sizeof(float) * 2 * (size_t)f->fft_len;
     f->slab = (size_t)frames * per_frame <= XCF_SCRATCH_BYTES ? frames : (int)(XCF_SCRATCH_BYTES / per_frame);
-    float *cs = (float *)malloc(sizeof(float) * 2 * (size_t)F);
-    int rc = cs ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK) {
-        for (int i = 0; i < F; i++) {
-            const double ang = (double)(2 * M_PI * i) / F;
-            cs[i] = (float)cos(ang);
-            cs[F + i] = (float)sin(ang);
-        }
-        f->d_cs = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)F);
-        rc = f->d_cs ? llzs_h2d(f->d_cs, cs, sizeof(float) * 2 * (size_t)F, NULL) : LLZ_ERR_NOMEM;
-    }
-    free(cs);
-    if (rc == LLZ_OK) {
-        f->d_z = (float *)llzs_malloc((size_t)f->slab * per_frame);
-        if (!f->d_z) rc = LLZ_ERR_NOMEM;
-    }
-    if (rc != LLZ_OK) {
+    f->d_cs = llz_host_cs_f32(f->fft_len);
+    if (f->d_cs) f->d_z = (float *)llzs_malloc((size_t)f->slab * per_frame);
+    if (!f->d_z) {
         xcfm_destroy(f);
         return LLZ_BAD_HANDLE;
     }
     return (unsigned long)f;
 }
 
-void llz_crosscorr_fast_mc_uninit(unsigned long handle)
-{
-    if (LLZ_HANDLE_OK(handle, xcfm_t, LLZ_TAG_XCFM)) {
-        const int prev = llzs_device_enter(((xcfm_t *)handle)->device);
-        llzs_sync(((xcfm_t *)handle)->stream);
-        xcfm_destroy((xcfm_t *)handle);
-        llzs_device_leave(prev);
-    }
-}
+void llz_crosscorr_fast_mc_uninit(unsigned long handle) { llz_handle_retire(handle, LLZ_TAG_XCFM, xcfm_destroy); }
 
 int llz_crosscorr_fast_mc_set_stream(unsigned long handle, void *stream)
 {
-    if (!LLZ_HANDLE_OK(handle, xcfm_t, LLZ_TAG_XCFM)) {
-        llzs_set_error("llz_crosscorr_fast_mc_set_stream: not a llz_crosscorr_fast_mc_init handle");
-        return LLZ_ERR_ARG;
-    }
-    ((xcfm_t *)handle)->stream = stream;
-    return LLZ_OK;
+    return llz_handle_set_stream(handle, LLZ_TAG_XCFM, "llz_crosscorr_fast_mc_set_stream", stream);
 }
 
 int llz_crosscorr_fast_mc(unsigned long handle, const float *x, const float *y, float *r, int p, int two_sided)
 {
-    if (!LLZ_HANDLE_OK(handle, xcfm_t, LLZ_TAG_XCFM)) {
-        llzs_set_error("llz_crosscorr_fast_mc: not a llz_crosscorr_fast_mc_init handle");
-        return LLZ_ERR_ARG;
-    }
-    xcfm_t *f = (xcfm_t *)handle;
+    xcfm_t *f = (xcfm_t *)llz_handle(handle, LLZ_TAG_XCFM, "llz_crosscorr_fast_mc");
+    if (!f) return LLZ_ERR_ARG;
     if (!x || !y || !r || p < 0 || p >= f->n || (two_sided != 0 && two_sided != 1)) {
         llzs_set_error("llz_crosscorr_fast_mc: x %p y %p r %p p %d two_sided %d (0 <= p < n = %d, two_sided 0 or 1)",
                        (const void *)x, (const void *)y, (void *)r, p, two_sided, f->n);
@@ -395,25 +287,25 @@ int llz_crosscorr_fast_mc(unsigned long handle, const float *x, const float *y, 
     }
     const int width = two_sided ? 2 * p + 1 : p + 1, F = f->fft_len;
     const size_t xb = sizeof(float) * (size_t)f->frames * f->n, rb = sizeof(float) * (size_t)f->frames * width;
-    const int prev = llzs_device_enter(f->device);
+    const int prev = llzs_device_enter(f->head.device);
     const int x_dev = llzs_is_device_ptr(x), y_dev = llzs_is_device_ptr(y), r_dev = llzs_is_device_ptr(r);
     int rc = (x_dev < 0 || y_dev < 0 || r_dev < 0) ? LLZ_ERR_ARG : LLZ_OK;   /* a buffer of another GPU: refused, message set */
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_crosscorr_fast_mc", "x", x, xb, x_dev, "r", r, rb, r_dev);
     if (rc == LLZ_OK) rc = llz_refuse_device_overlap("llz_crosscorr_fast_mc", "y", y, xb, y_dev, "r", r, rb, r_dev);
-    const float *d_x = llz_stage_in(&f->st_x, x, xb, x_dev, f->stream, &rc);
+    const float *d_x = llz_stage_in(&f->st_x, x, xb, x_dev, f->head.stream, &rc);
     /* an autocorrelation from host memory (y == x) is staged once */
-    const float *d_y = y == x ? d_x : llz_stage_in(&f->st_y, y, xb, y_dev, f->stream, &rc);
+    const float *d_y = y == x ? d_x : llz_stage_in(&f->st_y, y, xb, y_dev, f->head.stream, &rc);
     float *d_r = llz_stage_out(&f->st_out, r, rb, r_dev, &rc);
     /* per slab of frames: pack -> FFT -> conj(X) Y -> IFFT -> lags; the launches of a slab follow the previous slab's on the stream */
     for (int f0 = 0; rc == LLZ_OK && f0 < f->frames; f0 += f->slab) {
         const int cnt = f->frames - f0 < f->slab ? f->frames - f0 : f->slab;
-        rc = llzs_xcf_pack(d_x + (size_t)f0 * f->n, d_y + (size_t)f0 * f->n, f->d_z, cnt, f->n, F, f->stream);
-        if (rc == LLZ_OK) rc = llzs_fft_f32(f->d_z, cnt, F, f->d_cs, 0, f->stream);
-        if (rc == LLZ_OK) rc = llzs_xcf_product(f->d_z, cnt, F, f->stream);
-        if (rc == LLZ_OK) rc = llzs_fft_f32(f->d_z, cnt, F, f->d_cs, 1, f->stream);
-        if (rc == LLZ_OK) rc = llzs_xcf_extract(f->d_z, d_r + (size_t)f0 * width, cnt, p, two_sided, F, f->stream);
+        rc = llzs_xcf_pack(d_x + (size_t)f0 * f->n, d_y + (size_t)f0 * f->n, f->d_z, cnt, f->n, F, f->head.stream);
+        if (rc == LLZ_OK) rc = llzs_fft_f32(f->d_z, cnt, F, f->d_cs, 0, f->head.stream);
+        if (rc == LLZ_OK) rc = llzs_xcf_product(f->d_z, cnt, F, f->head.stream);
+        if (rc == LLZ_OK) rc = llzs_fft_f32(f->d_z, cnt, F, f->d_cs, 1, f->head.stream);
+        if (rc == LLZ_OK) rc = llzs_xcf_extract(f->d_z, d_r + (size_t)f0 * width, cnt, p, two_sided, F, f->head.stream);
     }
-    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->stream);
+    if (rc == LLZ_OK && !r_dev) rc = llzs_d2h(r, d_r, rb, f->head.stream);
     llzs_device_leave(prev);
     return rc;
 }

@@ -89,23 +89,13 @@ static double sinc_norm(double x)
     return sin(M_PI * fmod(x, 2.0)) / (M_PI * x);
 }
 
-static int fill_window(double *w, int n, win_t win)
-{
-    switch (win) {
-    case HAMMING:  llz_hamming(w, n);  return 0;
-    case BLACKMAN: llz_blackman(w, n); return 0;
-    case KAISER:   llz_kaiser(w, n);   return 0;
-    }
-    return -1;
-}
-
 int llz_host_design(int kind, double **out, int n, double fc1, double fc2, win_t win)
 {
     if (n < 1) return -1;
     if (kind != LLZ_KIND_LPF && (n & 1) == 0) n += 1;          /* llz_fir.c:305-307 */
     double *w = (double *)malloc(sizeof(double) * (size_t)n);
     double *h = (double *)malloc(sizeof(double) * (size_t)n);
-    if (!w || !h || fill_window(w, n, win) != 0) {
+    if (!w || !h || !llz_host_window(w, n, win)) {
         free(w); free(h);
         return -1;
     }

@@ -26,8 +26,52 @@ enum {
 /* one frame of a llz_mdct_init() handle between two device buffers of doubles (llz_mdct_host.c; used by the frame handles
  * of llz_asmodel_host.c): forward N samples -> N/2 coefficients, inverse the other way; d_src != d_dst */
 int llz_host_mdct_on_device(unsigned long handle, const double *d_src, double *d_dst, int inverse);
-/* cos then sin of 2 pi i / size, i < size, as llz_fft_init builds them (llz_fft.c:222-229), uploaded; NULL on failure */
-double *llz_host_fft_table_f64(int size);
+
+/* ---- the head of a handle (llz_util.c) ----
+ * The handles of the transform and analysis family start with this head, so one lookup, one set_stream and one retire serve
+ * them all.  device: the device the handle's buffers live on, bound by every call; stream: NULL for the handles without one. */
+typedef struct {
+    int tag, device;
+    void *stream;
+} llz_head_t;
+/* a zeroed handle of `size` bytes with its tag set and (on_device) the current device taken; NULL when out of host memory.  An
+ * init that fails calls its destroy on the partly built handle: every destroy takes a handle with any of its members still zero */
+void *llz_handle_new(size_t size, int tag, int on_device);
+/* the handle, or NULL -- with the message "<who>: bad handle" when who is not NULL */
+void *llz_handle(unsigned long handle, int tag, const char *who);
+int   llz_handle_set_stream(unsigned long handle, int tag, const char *who, void *stream);
+/* the uninit of a handle: its device entered, its stream synchronised, destroy(handle), the device left; nothing on a bad handle */
+void  llz_handle_retire(unsigned long handle, int tag, void (*destroy)(void *));
+
+/* ---- llz_tables.c: the window, twiddle and MDCT tables of the transform and analysis family ----
+ * Every builder returns DEVICE memory (llzs_malloc, filled through llzs_h2d on the default stream) or NULL; the values come from
+ * libm in the reference's own expressions and operation order, so that a table is the reference's to the last bit. */
+
+/* Hamming / Blackman / Kaiser (llz_fir.c:61-158) by win_t; 0: unknown window, nothing written */
+int llz_host_window(double *w, int n, win_t win_type);
+/* a device copy of `bytes` of host memory; of `count` doubles rounded to float; `bytes` of zeros */
+void  *llz_host_upload(const void *host, size_t bytes);
+float *llz_host_upload_f32(const double *host, size_t count);
+void  *llz_host_zeros(size_t bytes);
+/* cos then sin of 2 pi i / size, i < size, as llz_fft_init builds them (llz_fft.c:222-229): in double, rounded to float once,
+ * and in Q15 as llz_fft_fixed_init does (llz_fft_fixed.c:243-247) */
+double *llz_host_cs_f64(int size);
+float  *llz_host_cs_f32(int size);
+short  *llz_host_cs_q15(int size);
+/* LLZ_FIX15 of the reference (llz_fft_fixed.h:42-66): v * 2^15 rounded half away from zero, saturated to int32, clipped to
+ * +-32767 */
+short llz_host_q15(double v);
+/* the twiddle steps of the MDCT's FFT forms: step = one of these for the N-point form; the N/4-point form (quarter) has one
+ * table for all four.  A table is `count` (cos, sin) pairs of the reference's angle of (step, k, length), in double or Q15 */
+enum { LLZ_ROT_FWD_PRE = 0, LLZ_ROT_FWD_POST = 1, LLZ_ROT_INV_PRE = 2, LLZ_ROT_INV_POST = 3 };
+double *llz_host_mdct_rot_f64(int quarter, int step, int count, int length);
+short  *llz_host_mdct_rot_q15(int quarter, int step, int count, int length);
+/* the cosine kernels of the defining sums: *fwd = [N/2][N], *inv = [N][N/2], in double or Q15; LLZ_OK or LLZ_ERR_NOMEM (what
+ * was built stays in *fwd / *inv for the handle's destroy) */
+int llz_host_mdct_sums_f64(int N, double **fwd, double **inv);
+int llz_host_mdct_sums_q15(int N, short **fwd, short **inv);
+/* the float pre-twiddles of the N/4-point form: cos and sin of -2 pi (k + 1/8) / N, k < N / 4 (llz_mdct.c:459-462) */
+int llz_host_mdct_pretwiddles_f32(int N, float **tc, float **ts);
 
 /* ---- llz_spectra.c: the tables of the frequency-domain FIR forms ---- */
 
@@ -77,12 +121,10 @@ int llz_refuse_device_overlap(const char *who, const char *in_name, const void *
  * bytes per lane and take their rows on a 16-byte boundary; the headers ask no more of a caller's pointer than its element's
  * alignment.  llz_in_place() is 1 for device memory (dev as llzs_is_device_ptr() answered) such a kernel may use where it
  * lies; everything else -- host memory, and device memory at a lesser alignment -- goes through the handle's staging buffer
- * with llz_stage_load() / llz_stage_store() (a copy from / to host memory waits for the stream, one between device buffers
- * is ordered on it). */
+ * with the llz_vec_stage_* calls below (a copy from / to host memory waits for the stream, one between device buffers is
+ * ordered on it). */
 enum { LLZ_VEC_ALIGN = 16 };
 int llz_in_place(const void *p, int dev);
-int llz_stage_load(void *d_stage, const void *user, size_t bytes, int user_dev, void *stream);
-int llz_stage_store(void *user, const void *d_stage, size_t bytes, int user_dev, void *stream);
 
 /* staging buffers for callers that hand over host memory */
 typedef struct {
@@ -102,6 +144,33 @@ void  llz_stage_release(llz_stage_t *s);
  * the copy's error. */
 const void *llz_stage_in(llz_stage_t *s, const void *user, size_t bytes, int user_dev, void *stream, int *rc);
 void *llz_stage_out(llz_stage_t *s, void *user, size_t bytes, int user_dev, int *rc);
+
+/* The same three steps under the 16-byte rule above: memory that llz_in_place() accepts is used where it lies, everything else
+ * goes through s with a copy from host or device memory (llz_vec_stage_in), is reserved (llz_vec_stage_out), and is copied back
+ * when d, the pointer the kernel wrote, is not the caller's (llz_vec_stage_back).  All three chain on *rc. */
+const void *llz_vec_stage_in(llz_stage_t *s, const void *user, size_t bytes, int user_dev, void *stream, int *rc);
+void *llz_vec_stage_out(llz_stage_t *s, void *user, size_t bytes, int user_dev, int *rc);
+void  llz_vec_stage_back(void *user, const void *d, size_t bytes, int user_dev, void *stream, int *rc);
+
+/* The staged call of the one-shot entry points, which have no handle to keep a stage in.  A call declares its buffers in the
+ * order its kernel takes them: name, pointer, bytes, input or output (a NULL pointer or no bytes: an optional buffer that is
+ * absent; LLZ_BIND_SCRATCH: the library's own, filled in by llz_bind_scratch).  llz_bind classifies them all (memory of another
+ * GPU: LLZ_ERR_ARG), refuses a device overlap of each input with each output through llz_refuse_device_overlap before anything
+ * is staged, then, in declaration order, uploads host inputs (an input whose pointer is an earlier input's shares its copy) and
+ * reserves host outputs; dev is what to launch with.  llz_bind_finish(rc of the launch) downloads the staged outputs in
+ * declaration order, synchronises the stream once if anything was staged, frees, and returns the first error. */
+enum { LLZ_BIND_IN = 0, LLZ_BIND_OUT = 1, LLZ_BIND_SCRATCH = 2 };
+typedef struct {
+    const char *name;
+    const void *user;
+    size_t bytes;
+    int kind;
+    void *dev;                  /* filled in by llz_bind */
+    int on_dev, staged;
+} llz_bind_t;
+int   llz_bind(const char *who, llz_bind_t *b, int count, void *stream);
+void *llz_bind_scratch(llz_bind_t *b, size_t bytes, int *rc);     /* chains on *rc; freed by llz_bind_finish */
+int   llz_bind_finish(llz_bind_t *b, int count, void *stream, int rc);
 
 /* ---- llz_fade.c: the crossfade state of the delay-line convolvers (llz_fir_xfade_stream_mc, llz_fir_xfade_matrix_mc) ---- */
 

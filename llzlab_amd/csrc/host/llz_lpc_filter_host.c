@@ -17,32 +17,30 @@
 #define LLZ_TAG_LPCF 0x4c5a5046
 
 typedef struct {
-    int tag;                    /* LLZ_TAG_LPCF */
-    int device;                 /* the device the handle's buffers live on: every call binds it */
+    llz_head_t head;
     int channels, frame_len, p;
     int cur;                    /* which half of d_hist holds the residual's history in front of the next call */
     float *d_hist;              /* [2][channels][LLZ_LEVINSON_ORDER_MAX]: [c][i] = x(-1 - i), i < p */
     double *d_ys;               /* [channels][LLZ_LEVINSON_ORDER_MAX]: [c][i] = the unrounded y(-1 - i), i < p */
-    void *stream;
     llz_stage_t st_in, st_cof, st_out;   /* only for callers passing host memory */
 } lpcf_t;
 
 static size_t lpcf_hist_count(const lpcf_t *f) { return (size_t)f->channels * LLZ_LEVINSON_ORDER_MAX; }
 
-static void lpcf_destroy(lpcf_t *f)
+static void lpcf_destroy(void *p)
 {
-    if (!f) return;
+    lpcf_t *f = (lpcf_t *)p;
     llzs_free(f->d_hist); llzs_free(f->d_ys);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_cof); llz_stage_release(&f->st_out);
-    f->tag = 0;
+    f->head.tag = 0;
     free(f);
 }
 
 /* zeros in both delay lines, ordered on the handle's stream */
 static int lpcf_clear(lpcf_t *f)
 {
-    int rc = llzs_memset(f->d_hist, 0, sizeof(float) * 2 * lpcf_hist_count(f), f->stream);
-    if (rc == LLZ_OK) rc = llzs_memset(f->d_ys, 0, sizeof(double) * lpcf_hist_count(f), f->stream);
+    int rc = llzs_memset(f->d_hist, 0, sizeof(float) * 2 * lpcf_hist_count(f), f->head.stream);
+    if (rc == LLZ_OK) rc = llzs_memset(f->d_ys, 0, sizeof(double) * lpcf_hist_count(f), f->head.stream);
     f->cur = 0;
     return rc;
 }
@@ -63,13 +61,11 @@ unsigned long llz_lpc_filter_mc_init(int channels, int frame_len, int p)
                        who, frame_len, p);
         return LLZ_BAD_HANDLE;
     }
-    lpcf_t *f = (lpcf_t *)calloc(1, sizeof(*f));
+    lpcf_t *f = (lpcf_t *)llz_handle_new(sizeof(*f), LLZ_TAG_LPCF, 1);
     if (!f) {
         llzs_set_error("%s: no host memory for the handle", who);
         return LLZ_BAD_HANDLE;
     }
-    f->tag = LLZ_TAG_LPCF;
-    f->device = llzs_device_get();
     f->channels = channels; f->frame_len = frame_len; f->p = p;
     const size_t hb = sizeof(float) * 2 * lpcf_hist_count(f), yb = sizeof(double) * lpcf_hist_count(f);
     f->d_hist = (float *)llzs_malloc(hb);
@@ -88,35 +84,18 @@ unsigned long llz_lpc_filter_mc_init(int channels, int frame_len, int p)
     return (unsigned long)f;
 }
 
-void llz_lpc_filter_mc_uninit(unsigned long handle)
-{
-    if (LLZ_HANDLE_OK(handle, lpcf_t, LLZ_TAG_LPCF)) {
-        lpcf_t *f = (lpcf_t *)handle;
-        const int prev = llzs_device_enter(f->device);
-        llzs_sync(f->stream);
-        lpcf_destroy(f);
-        llzs_device_leave(prev);
-    }
-}
+void llz_lpc_filter_mc_uninit(unsigned long handle) { llz_handle_retire(handle, LLZ_TAG_LPCF, lpcf_destroy); }
 
 int llz_lpc_filter_mc_set_stream(unsigned long handle, void *stream)
 {
-    if (!LLZ_HANDLE_OK(handle, lpcf_t, LLZ_TAG_LPCF)) {
-        llzs_set_error("llz_lpc_filter_mc_set_stream: bad handle");
-        return LLZ_ERR_ARG;
-    }
-    ((lpcf_t *)handle)->stream = stream;
-    return LLZ_OK;
+    return llz_handle_set_stream(handle, LLZ_TAG_LPCF, "llz_lpc_filter_mc_set_stream", stream);
 }
 
 int llz_lpc_filter_mc_reset(unsigned long handle)
 {
-    if (!LLZ_HANDLE_OK(handle, lpcf_t, LLZ_TAG_LPCF)) {
-        llzs_set_error("llz_lpc_filter_mc_reset: bad handle");
-        return LLZ_ERR_ARG;
-    }
-    lpcf_t *f = (lpcf_t *)handle;
-    const int prev = llzs_device_enter(f->device);
+    lpcf_t *f = (lpcf_t *)llz_handle(handle, LLZ_TAG_LPCF, "llz_lpc_filter_mc_reset");
+    if (!f) return LLZ_ERR_ARG;
+    const int prev = llzs_device_enter(f->head.device);
     const int rc = lpcf_clear(f);
     llzs_device_leave(prev);
     return rc;
@@ -135,29 +114,26 @@ static int lpcf_run(lpcf_t *f, const char *who, int synth, const char *in_name, 
         llz_refuse_device_overlap(who, "acof", acof, cbytes, cof_dev, out_name, out, bytes, out_dev))
         return LLZ_ERR_ARG;
     int rc = LLZ_OK;
-    const float *d_in = llz_stage_in(&f->st_in, in, bytes, in_dev, f->stream, &rc);
-    const float *d_cof = llz_stage_in(&f->st_cof, acof, cbytes, cof_dev, f->stream, &rc);
+    const float *d_in = llz_stage_in(&f->st_in, in, bytes, in_dev, f->head.stream, &rc);
+    const float *d_cof = llz_stage_in(&f->st_cof, acof, cbytes, cof_dev, f->head.stream, &rc);
     float *d_out = llz_stage_out(&f->st_out, out, bytes, out_dev, &rc);
     if (rc == LLZ_OK && synth)
-        rc = llzs_lpc_synth_f32(d_in, d_cof, d_out, f->d_ys, f->channels, frames, f->frame_len, f->p, f->stream);
+        rc = llzs_lpc_synth_f32(d_in, d_cof, d_out, f->d_ys, f->channels, frames, f->frame_len, f->p, f->head.stream);
     if (rc == LLZ_OK && !synth) {
         const float *h_in = f->d_hist + (size_t)f->cur * lpcf_hist_count(f);
         float *h_out = f->d_hist + (size_t)(1 - f->cur) * lpcf_hist_count(f);
-        rc = llzs_lpc_residual_f32(d_in, d_cof, d_out, h_in, h_out, f->channels, frames, f->frame_len, f->p, f->stream);
+        rc = llzs_lpc_residual_f32(d_in, d_cof, d_out, h_in, h_out, f->channels, frames, f->frame_len, f->p, f->head.stream);
         if (rc == LLZ_OK) f->cur = 1 - f->cur;
     }
-    if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
+    if (rc == LLZ_OK && !out_dev) rc = llzs_d2h(out, d_out, bytes, f->head.stream);
     return rc == LLZ_OK ? frames : rc;
 }
 
 static int lpcf_call(const char *who, int synth, unsigned long handle, const char *in_name, const float *in, const float *acof,
                      const char *out_name, float *out, int frames)
 {
-    if (!LLZ_HANDLE_OK(handle, lpcf_t, LLZ_TAG_LPCF)) {
-        llzs_set_error("%s: bad handle", who);
-        return LLZ_ERR_ARG;
-    }
-    lpcf_t *f = (lpcf_t *)handle;
+    lpcf_t *f = (lpcf_t *)llz_handle(handle, LLZ_TAG_LPCF, who);
+    if (!f) return LLZ_ERR_ARG;
     if (!in || !acof || !out) {
         llzs_set_error("%s: NULL buffer (%s, acof and %s are all needed)", who, in_name, out_name);
         return LLZ_ERR_ARG;
@@ -171,7 +147,7 @@ static int lpcf_call(const char *who, int synth, unsigned long handle, const cha
                        f->channels);
         return LLZ_ERR_RANGE;
     }
-    const int prev = llzs_device_enter(f->device);       /* the handle's device, whatever the caller has current */
+    const int prev = llzs_device_enter(f->head.device);       /* the handle's device, whatever the caller has current */
     const int rc = lpcf_run(f, who, synth, in_name, in, acof, out_name, out, frames);
     llzs_device_leave(prev);
     return rc;

@@ -8,7 +8,6 @@
  */
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 #include "../../../include/llz_levinson.h"
 #include "../../../include/llz_lpc.h"
 #include "llz_host.h"
@@ -120,7 +119,8 @@ int llz_atlvs(double *r, int n, double *b, double *x, double *kcof, double *err)
 #define LLZ_TAG_LPC1 0x4c5a4c31
 
 typedef struct {
-    int tag, p;
+    llz_head_t head;                                     /* device -1, no stream: the calls run where the caller is */
+    int p;
     double *r, *acof, *kcof, err;                        /* llz_lpc.c:19-27: the state that outlives a call */
     double *d_r;
     llz_stage_t st_x;
@@ -128,11 +128,10 @@ typedef struct {
 
 static void lpc1_destroy(lpc1_t *f)
 {
-    if (!f) return;
     llzs_free(f->d_r);
     llz_stage_release(&f->st_x);
     free(f->r); free(f->acof); free(f->kcof);
-    f->tag = 0;
+    f->head.tag = 0;
     free(f);
 }
 
@@ -142,9 +141,9 @@ unsigned long llz_lpc_init(int p)
         llzs_set_error("llz_lpc_init: p=%d (0 <= p <= %d)", p, LLZ_LEVINSON_ORDER_MAX);
         return LLZ_BAD_HANDLE;
     }
-    lpc1_t *f = (lpc1_t *)calloc(1, sizeof(*f));
+    lpc1_t *f = (lpc1_t *)llz_handle_new(sizeof(*f), LLZ_TAG_LPC1, 0);
     if (!f) return LLZ_BAD_HANDLE;
-    f->tag = LLZ_TAG_LPC1; f->p = p;
+    f->p = p;
     f->r = (double *)calloc((size_t)p + 1, sizeof(double));         /* zeroed, as llz_lpc.c:38-43 */
     f->acof = (double *)calloc((size_t)p + 1, sizeof(double));
     f->kcof = (double *)calloc((size_t)p + 1, sizeof(double));
@@ -158,16 +157,17 @@ unsigned long llz_lpc_init(int p)
 
 void llz_lpc_uninit(unsigned long handle)
 {
-    if (LLZ_HANDLE_OK(handle, lpc1_t, LLZ_TAG_LPC1)) lpc1_destroy((lpc1_t *)handle);
+    lpc1_t *f = (lpc1_t *)llz_handle(handle, LLZ_TAG_LPC1, NULL);
+    if (f) lpc1_destroy(f);
 }
 
 double llz_lpc(unsigned long handle, double *x, int x_len, double *lpc_cof, double *kcof, double *err)
 {
-    if (!LLZ_HANDLE_OK(handle, lpc1_t, LLZ_TAG_LPC1) || !x || !lpc_cof || !kcof || !err || x_len < 1) {
+    lpc1_t *f = (lpc1_t *)llz_handle(handle, LLZ_TAG_LPC1, NULL);
+    if (!f || !x || !lpc_cof || !kcof || !err || x_len < 1) {
         llzs_set_error("llz_lpc: bad handle or arguments (x_len=%d)", x_len);
         return 0.0;
     }
-    lpc1_t *f = (lpc1_t *)handle;
     const int p = f->p;
     /* llz_autocorr (llz_corr.c:33-42) on the device in its own summation order, into the handle's r */
     const size_t xb = sizeof(double) * (size_t)x_len, rb = sizeof(double) * ((size_t)p + 1);
@@ -186,26 +186,6 @@ double llz_lpc(unsigned long handle, double *x, int x_len, double *lpc_cof, doub
 
 /* ---- Part 2: batch extension ---- */
 
-/* a caller buffer on the device: used in place, or a device copy (inputs uploaded, outputs downloaded afterwards) */
-typedef struct {
-    void *user, *dev;
-    size_t bytes;
-    int staged;
-} lpc_buf;
-
-static int lpc_bind(lpc_buf *b, const void *user, size_t bytes, int input, void *stream)
-{
-    b->user = (void *)user; b->dev = NULL; b->bytes = bytes; b->staged = 0;
-    if (!user || !bytes) return LLZ_OK;
-    const int dev = llzs_is_device_ptr(user);
-    if (dev < 0) return LLZ_ERR_ARG;                     /* memory of another GPU: refused, message set */
-    if (dev) { b->dev = (void *)user; return LLZ_OK; }
-    b->dev = llzs_malloc(bytes);
-    if (!b->dev) return LLZ_ERR_NOMEM;
-    b->staged = 1;
-    return input ? llzs_h2d(b->dev, user, bytes, stream) : LLZ_OK;
-}
-
 int llz_lpc_mc(const float *x, const float *win, float *acof, float *kcof, float *err, float *gain, float *r,
                int frames, int n, int p, void *stream)
 {
@@ -216,54 +196,31 @@ int llz_lpc_mc(const float *x, const float *win, float *acof, float *kcof, float
     }
     const size_t F = (size_t)frames, P1 = (size_t)p + 1, fb = sizeof(float);
     enum { BX, BW, BA, BK, BE, BG, BR, BXW, BRS, NB };
-    lpc_buf b[NB];
-    memset(b, 0, sizeof(b));
+    llz_bind_t b[NB] = {{"x", x, fb * F * n, LLZ_BIND_IN, NULL, 0, 0}, {"win", win, fb * n, LLZ_BIND_IN, NULL, 0, 0},
+                        {"acof", acof, fb * F * P1, LLZ_BIND_OUT, NULL, 0, 0}, {"kcof", kcof, fb * F * p, LLZ_BIND_OUT, NULL, 0, 0},
+                        {"err", err, fb * F, LLZ_BIND_OUT, NULL, 0, 0}, {"gain", gain, fb * F, LLZ_BIND_OUT, NULL, 0, 0},
+                        {"r", r, fb * F * P1, LLZ_BIND_OUT, NULL, 0, 0},
+                        {"x * win", NULL, 0, LLZ_BIND_SCRATCH, NULL, 0, 0}, {"r", NULL, 0, LLZ_BIND_SCRATCH, NULL, 0, 0}};
     const int split = p > 32 || llzs_tune(LLZS_TUNE_LPC_SPLIT) == 1;
-    /* no output may overlap x on the device: checked for all of them before anything is staged */
-    const struct { const char *name; const float *ptr; size_t bytes; } outs[5] = {
-        {"acof", acof, fb * F * P1}, {"kcof", p ? kcof : NULL, fb * F * p}, {"err", err, fb * F}, {"gain", gain, fb * F},
-        {"r", r, fb * F * P1}};
-    const int x_dev = llzs_is_device_ptr(x);
-    for (int i = 0; i < 5 && x_dev == 1; i++)
-        if (outs[i].ptr && llz_refuse_device_overlap("llz_lpc_mc", "x", x, fb * F * n, x_dev, outs[i].name, outs[i].ptr,
-                                                     outs[i].bytes, llzs_is_device_ptr(outs[i].ptr)))
-            return LLZ_ERR_ARG;
-    int rc = lpc_bind(&b[BX], x, fb * F * n, 1, stream);
-    if (rc == LLZ_OK) rc = lpc_bind(&b[BW], win, fb * n, 1, stream);
-    if (rc == LLZ_OK) rc = lpc_bind(&b[BA], acof, fb * F * P1, 0, stream);
-    if (rc == LLZ_OK) rc = lpc_bind(&b[BK], p ? kcof : NULL, fb * F * p, 0, stream);
-    if (rc == LLZ_OK) rc = lpc_bind(&b[BE], err, fb * F, 0, stream);
-    if (rc == LLZ_OK) rc = lpc_bind(&b[BG], gain, fb * F, 0, stream);
-    if (rc == LLZ_OK) rc = lpc_bind(&b[BR], r, fb * F * P1, 0, stream);
-    if (rc == LLZ_OK) {
-        if (!split) {
-            rc = llzs_lpc_fused_f32((const float *)b[BX].dev, (const float *)b[BW].dev, (float *)b[BA].dev,
-                                    (float *)b[BK].dev, (float *)b[BE].dev, (float *)b[BG].dev, (float *)b[BR].dev,
-                                    frames, n, p, stream);
-        } else {
-            /* llz_autocorr_mc's kernel (on x*win when a window is given), then the recursion */
-            const float *xin = (const float *)b[BX].dev;
-            float *rr = (float *)b[BR].dev;
-            if (b[BW].dev) {
-                b[BXW].dev = llzs_malloc(fb * F * n);
-                rc = b[BXW].dev ? llzs_window_f32(xin, (const float *)b[BW].dev, (float *)b[BXW].dev, frames, n, stream)
-                                : LLZ_ERR_NOMEM;
-                xin = (const float *)b[BXW].dev;
-            }
-            if (rc == LLZ_OK && !rr) {
-                rr = (float *)(b[BRS].dev = llzs_malloc(fb * F * P1));
-                if (!rr) rc = LLZ_ERR_NOMEM;
-            }
-            if (rc == LLZ_OK) rc = llzs_autocorr_mc_f32(xin, rr, frames, n, p, stream);
-            if (rc == LLZ_OK)
-                rc = llzs_levinson_f32(rr, (float *)b[BA].dev, (float *)b[BK].dev, (float *)b[BE].dev,
-                                       (float *)b[BG].dev, frames, n, p, stream);
+    int rc = llz_bind("llz_lpc_mc", b, NB, stream);
+    if (rc == LLZ_OK) b[BRS].staged = 1;    /* a call has always returned synchronised: llz_bind_finish waits even where nothing was staged */
+    if (rc == LLZ_OK && !split) {
+        rc = llzs_lpc_fused_f32((const float *)b[BX].dev, (const float *)b[BW].dev, (float *)b[BA].dev, (float *)b[BK].dev,
+                                (float *)b[BE].dev, (float *)b[BG].dev, (float *)b[BR].dev, frames, n, p, stream);
+    } else if (rc == LLZ_OK) {
+        /* llz_autocorr_mc's kernel (on x*win when a window is given), then the recursion */
+        const float *xin = (const float *)b[BX].dev;
+        float *rr = (float *)b[BR].dev;
+        if (b[BW].dev) {
+            float *xw = (float *)llz_bind_scratch(&b[BXW], fb * F * n, &rc);
+            if (xw) rc = llzs_window_f32(xin, (const float *)b[BW].dev, xw, frames, n, stream);
+            xin = xw;
         }
+        if (!rr) rr = (float *)llz_bind_scratch(&b[BRS], fb * F * P1, &rc);
+        if (rc == LLZ_OK) rc = llzs_autocorr_mc_f32(xin, rr, frames, n, p, stream);
+        if (rc == LLZ_OK)
+            rc = llzs_levinson_f32(rr, (float *)b[BA].dev, (float *)b[BK].dev, (float *)b[BE].dev, (float *)b[BG].dev, frames, n,
+                                   p, stream);
     }
-    for (int i = BA; i <= BR && rc == LLZ_OK; i++)
-        if (b[i].staged) rc = llzs_d2h(b[i].user, b[i].dev, b[i].bytes, stream);
-    llzs_sync(stream);                                   /* nothing in flight reads the buffers freed below */
-    for (int i = 0; i < NB; i++)
-        if (b[i].staged || i >= BXW) llzs_free(b[i].dev);
-    return rc;
+    return llz_bind_finish(b, NB, stream, rc);
 }

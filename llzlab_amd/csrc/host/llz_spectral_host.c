@@ -3,7 +3,6 @@
  * twiddle tables, the pair table, the history ping-pong, the run grid with its carried float32 partial, the double
  * accumulators, and the walk of the partial scratch in slabs of runs.
  */
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../../include/llz_spectral.h"
@@ -14,7 +13,8 @@
 #define CSD_READ_RAW 5
 
 typedef struct {
-    int tag, device, channels, pairs, fft_len, hop, bins, keep;
+    llz_head_t head;
+    int channels, pairs, fft_len, hop, bins, keep;
     long hops;                      /* hops of every channel's stream taken since the last reset */
     double u;                       /* sum of the squared float32 window values */
     float *d_w, *d_cs;
@@ -28,7 +28,6 @@ typedef struct {
                                      * while frames % LLZ_CSD_RUN != 0 */
     int cur_carry;
     llz_stage_t st_x, st_out, st_scratch;
-    void *stream;
 } csdm_t;
 
 static long csd_frames_at(const csdm_t *f, long hops)
@@ -39,33 +38,23 @@ static long csd_frames_at(const csdm_t *f, long hops)
 
 static size_t csd_cell_bytes(const csdm_t *f, size_t elem) { return elem * 4 * (size_t)f->pairs * (size_t)f->bins; }
 
-static void csdm_destroy(csdm_t *f)
+static void csdm_destroy(void *p)
 {
-    if (!f) return;
+    csdm_t *f = (csdm_t *)p;
     llzs_free(f->d_w); llzs_free(f->d_cs); llzs_free(f->d_pairs);
     llzs_free(f->d_hist[0]); llzs_free(f->d_hist[1]); llzs_free(f->d_acc); llzs_free(f->d_carry[0]); llzs_free(f->d_carry[1]);
     llz_stage_release(&f->st_x); llz_stage_release(&f->st_out); llz_stage_release(&f->st_scratch);
-    f->tag = 0;
+    f->head.tag = 0;
     free(f);
-}
-
-static int csd_window(double *w, int n, win_t win_type)
-{
-    switch (win_type) {
-    case HAMMING: llz_hamming(w, n); return 1;
-    case BLACKMAN: llz_blackman(w, n); return 1;
-    case KAISER: llz_kaiser(w, n); return 1;
-    default: return 0;
-    }
 }
 
 static int csd_clear(csdm_t *f)
 {
-    int rc = llzs_memset(f->d_acc, 0, csd_cell_bytes(f, sizeof(double)), f->stream);
+    int rc = llzs_memset(f->d_acc, 0, csd_cell_bytes(f, sizeof(double)), f->head.stream);
     for (int k = 0; k < 2 && rc == LLZ_OK; k++)
-        rc = llzs_memset(f->d_carry[k], 0, 2 * csd_cell_bytes(f, sizeof(float)), f->stream);
+        rc = llzs_memset(f->d_carry[k], 0, 2 * csd_cell_bytes(f, sizeof(float)), f->head.stream);
     for (int k = 0; k < 2 && rc == LLZ_OK && f->keep; k++)
-        rc = llzs_memset(f->d_hist[k], 0, sizeof(float) * (size_t)f->channels * (size_t)f->keep, f->stream);
+        rc = llzs_memset(f->d_hist[k], 0, sizeof(float) * (size_t)f->channels * (size_t)f->keep, f->head.stream);
     if (rc == LLZ_OK) f->hops = 0;
     return rc;
 }
@@ -92,28 +81,21 @@ unsigned long llz_csd_mc_init(int channels, int pairs, const int *pair_xy, int f
                            channels - 1);
             return LLZ_BAD_HANDLE;
         }
-    csdm_t *f = (csdm_t *)calloc(1, sizeof(*f));
     double *w = (double *)malloc(sizeof(double) * (size_t)N);
-    float *tab = (float *)malloc(sizeof(float) * 3 * (size_t)N);
-    int rc = (f && w && tab) ? LLZ_OK : LLZ_ERR_NOMEM;
-    if (rc == LLZ_OK && !csd_window(w, N, win_type)) {
+    if (w && !llz_host_window(w, N, win_type)) {
         llzs_set_error("llz_csd_mc_init: unknown window %d", (int)win_type);
-        rc = LLZ_ERR_ARG;
+        free(w);
+        return LLZ_BAD_HANDLE;
     }
-    if (rc == LLZ_OK) {
-        f->tag = LLZ_TAG_CSDM; f->device = llzs_device_get(); f->channels = channels; f->pairs = pairs;
+    csdm_t *f = w ? (csdm_t *)llz_handle_new(sizeof(*f), LLZ_TAG_CSDM, 1) : NULL;
+    if (f) {
+        f->channels = channels; f->pairs = pairs;
         f->fft_len = N; f->hop = hop; f->bins = N / 2 + 1; f->keep = N - hop;
-        for (int i = 0; i < N; i++) {
-            const double ang = (double)(2 * M_PI * i) / N;          /* the table of llz_stft_mc_init */
-            tab[i] = (float)w[i];
-            tab[N + i] = (float)cos(ang);
-            tab[2 * N + i] = (float)sin(ang);
-            f->u += (double)tab[i] * (double)tab[i];
-        }
+        for (int i = 0; i < N; i++) f->u += (double)(float)w[i] * (double)(float)w[i];
         const size_t hist = sizeof(float) * (size_t)channels * (size_t)f->keep;
-        f->d_w = (float *)llzs_malloc(sizeof(float) * (size_t)N);
-        f->d_cs = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)N);
-        f->d_pairs = (int *)llzs_malloc(sizeof(int) * 2 * (size_t)pairs);
+        f->d_w = llz_host_upload_f32(w, (size_t)N);
+        f->d_cs = llz_host_cs_f32(N);
+        f->d_pairs = (int *)llz_host_upload(pair_xy, sizeof(int) * 2 * (size_t)pairs);
         f->d_acc = (double *)llzs_malloc(csd_cell_bytes(f, sizeof(double)));
         f->d_carry[0] = (float *)llzs_malloc(2 * csd_cell_bytes(f, sizeof(float)));
         f->d_carry[1] = (float *)llzs_malloc(2 * csd_cell_bytes(f, sizeof(float)));
@@ -121,48 +103,30 @@ unsigned long llz_csd_mc_init(int channels, int pairs, const int *pair_xy, int f
             f->d_hist[0] = (float *)llzs_malloc(hist);
             f->d_hist[1] = (float *)llzs_malloc(hist);
         }
+        int rc = LLZ_OK;
         if (!f->d_w || !f->d_cs || !f->d_pairs || !f->d_acc || !f->d_carry[0] || !f->d_carry[1] || (f->keep && (!f->d_hist[0] || !f->d_hist[1]))) {
             rc = LLZ_ERR_NOMEM;
             llzs_set_error("llz_csd_mc_init: device allocation failed (channels %d pairs %d fft_len %d: %zu bytes of sums, "
                            "2 x %zu bytes of history)", channels, pairs, N, csd_cell_bytes(f, sizeof(double) + 4 * sizeof(float)), hist);
         }
-        if (rc == LLZ_OK) rc = llzs_h2d(f->d_w, tab, sizeof(float) * (size_t)N, NULL);
-        if (rc == LLZ_OK) rc = llzs_h2d(f->d_cs, tab + N, sizeof(float) * 2 * (size_t)N, NULL);
-        if (rc == LLZ_OK) rc = llzs_h2d(f->d_pairs, pair_xy, sizeof(int) * 2 * (size_t)pairs, NULL);
         if (rc == LLZ_OK) rc = csd_clear(f);
         if (rc == LLZ_OK) rc = llzs_sync(NULL);
+        if (rc != LLZ_OK) {
+            csdm_destroy(f);
+            f = NULL;
+        }
     }
-    free(w); free(tab);
-    if (rc != LLZ_OK) {
-        if (f && f->tag) csdm_destroy(f); else free(f);
-        return LLZ_BAD_HANDLE;
-    }
-    return (unsigned long)f;
+    free(w);
+    return f ? (unsigned long)f : LLZ_BAD_HANDLE;
 }
 
-void llz_csd_mc_uninit(unsigned long handle)
-{
-    if (LLZ_HANDLE_OK(handle, csdm_t, LLZ_TAG_CSDM)) {
-        const int prev = llzs_device_enter(((csdm_t *)handle)->device);
-        llzs_sync(((csdm_t *)handle)->stream);
-        csdm_destroy((csdm_t *)handle);
-        llzs_device_leave(prev);
-    }
-}
+void llz_csd_mc_uninit(unsigned long handle) { llz_handle_retire(handle, LLZ_TAG_CSDM, csdm_destroy); }
 
-static csdm_t *csd_handle(unsigned long handle, const char *who)
-{
-    if (LLZ_HANDLE_OK(handle, csdm_t, LLZ_TAG_CSDM)) return (csdm_t *)handle;
-    llzs_set_error("%s: bad handle (not a llz_csd_mc_init handle)", who);
-    return NULL;
-}
+static csdm_t *csd_handle(unsigned long handle, const char *who) { return (csdm_t *)llz_handle(handle, LLZ_TAG_CSDM, who); }
 
 int llz_csd_mc_set_stream(unsigned long handle, void *stream)
 {
-    csdm_t *f = csd_handle(handle, "llz_csd_mc_set_stream");
-    if (!f) return LLZ_ERR_ARG;
-    f->stream = stream;
-    return LLZ_OK;
+    return llz_handle_set_stream(handle, LLZ_TAG_CSDM, "llz_csd_mc_set_stream", stream);
 }
 
 long llz_csd_mc_frames(unsigned long handle)
@@ -222,10 +186,10 @@ long llz_csd_mc_update(unsigned long handle, const float *x, long n)
     }
     if (csd_span(f, "llz_csd_mc_update", n, &f_lo, &f_hi) != LLZ_OK) return LLZ_ERR_ARG;
     const size_t xb = sizeof(float) * (size_t)f->channels * (size_t)n;
-    const int prev = llzs_device_enter(f->device);
+    const int prev = llzs_device_enter(f->head.device);
     const int x_dev = llzs_is_device_ptr(x);
     int rc = x_dev < 0 ? LLZ_ERR_ARG : LLZ_OK;                     /* a buffer of another GPU: refused, message set */
-    const float *d_x = (const float *)llz_stage_in(&f->st_x, x, xb, x_dev, f->stream, &rc);
+    const float *d_x = (const float *)llz_stage_in(&f->st_x, x, xb, x_dev, f->head.stream, &rc);
     if (rc == LLZ_OK && f_hi > f_lo) {
         const long r_lo = f_lo / LLZ_CSD_RUN, r_hi = (f_hi - 1) / LLZ_CSD_RUN, per = csd_runs_per_walk(f);
         const long most = r_hi - r_lo + 1 < per ? r_hi - r_lo + 1 : per;
@@ -242,19 +206,19 @@ long llz_csd_mc_update(unsigned long handle, const float *x, long n)
             if (nfin > nruns) nfin = nruns;
             rc = llzs_csd_runs_f32(d_x, f->d_hist[f->cur], f->d_w, f->d_cs, f->d_pairs, scratch, f->d_carry[f->cur_carry],
                                    f->d_carry[f->cur_carry ^ 1], f->pairs, f->fft_len, f->hop, n, f->hops, f_lo, f_hi, r0,
-                                   (int)nruns, f->stream);
-            if (rc == LLZ_OK && nfin > 0) rc = llzs_csd_fold_f64(scratch, f->d_acc, f->pairs, f->bins, (int)nfin, f->stream);
+                                   (int)nruns, f->head.stream);
+            if (rc == LLZ_OK && nfin > 0) rc = llzs_csd_fold_f64(scratch, f->d_acc, f->pairs, f->bins, (int)nfin, f->head.stream);
         }
         /* the call left a run open: its partial is in the other buffer (a call without a frame keeps the open run where it is) */
         if (rc == LLZ_OK && f_hi % LLZ_CSD_RUN) f->cur_carry ^= 1;
     }
     /* history for the next call: the last fft_len - hop samples of concat(history, x) */
     if (rc == LLZ_OK && f->keep) {
-        rc = llzs_fir_tail_f32(d_x, f->d_hist[f->cur], f->d_hist[f->cur ^ 1], f->channels, n, n, f->keep + 1, f->stream);
+        rc = llzs_fir_tail_f32(d_x, f->d_hist[f->cur], f->d_hist[f->cur ^ 1], f->channels, n, n, f->keep + 1, f->head.stream);
         if (rc == LLZ_OK) f->cur ^= 1;
     }
     if (rc == LLZ_OK) f->hops += n / f->hop;
-    if (rc == LLZ_OK && !x_dev) rc = llzs_sync(f->stream);         /* the stage may be reused by the next call */
+    if (rc == LLZ_OK && !x_dev) rc = llzs_sync(f->head.stream);         /* the stage may be reused by the next call */
     llzs_device_leave(prev);
     return rc == LLZ_OK ? csd_frames_at(f, f->hops) : rc;
 }
@@ -270,15 +234,15 @@ static int csd_read(csdm_t *f, const char *who, int what, void *out, size_t byte
         llzs_set_error("%s: no frame yet (%ld of the first %d samples have arrived)", who, f->hops * f->hop, f->fft_len);
         return LLZ_ERR_ARG;
     }
-    const int prev = llzs_device_enter(f->device);
+    const int prev = llzs_device_enter(f->head.device);
     const int o_dev = llzs_is_device_ptr(out);
     int rc = o_dev < 0 ? LLZ_ERR_ARG : LLZ_OK;
     void *d_out = llz_stage_out(&f->st_out, out, bytes, o_dev, &rc);
     if (rc == LLZ_OK)
         rc = llzs_csd_read_f64(f->d_acc, K % LLZ_CSD_RUN ? f->d_carry[f->cur_carry] : NULL, f->pairs, f->bins, what, (double)K * f->u,
                                what == CSD_READ_RAW ? NULL : (float *)d_out, what == CSD_READ_RAW ? (double *)d_out : NULL,
-                               f->stream);
-    if (rc == LLZ_OK && !o_dev) rc = llzs_d2h(out, d_out, bytes, f->stream);
+                               f->head.stream);
+    if (rc == LLZ_OK && !o_dev) rc = llzs_d2h(out, d_out, bytes, f->head.stream);
     llzs_device_leave(prev);
     return rc;
 }
@@ -306,7 +270,7 @@ int llz_csd_mc_reset(unsigned long handle)
 {
     csdm_t *f = csd_handle(handle, "llz_csd_mc_reset");
     if (!f) return LLZ_ERR_ARG;
-    const int prev = llzs_device_enter(f->device);
+    const int prev = llzs_device_enter(f->head.device);
     const int rc = csd_clear(f);
     llzs_device_leave(prev);
     return rc;
