@@ -18,7 +18,7 @@ enum {
     LLZ_TAG_FIR1 = 0x4c5a4631, LLZ_TAG_FIRM = 0x4c5a464d, LLZ_TAG_IIR1 = 0x4c5a4931, LLZ_TAG_IIRM = 0x4c5a494d,
     LLZ_TAG_RS1 = 0x4c5a5231, LLZ_TAG_RSM = 0x4c5a524d, LLZ_TAG_FFT1 = 0x4c5a5431, LLZ_TAG_FFTB = 0x4c5a5442,
     LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942, LLZ_TAG_FIRS = 0x4c5a4653,
-    LLZ_TAG_FIRX = 0x4c5a4658
+    LLZ_TAG_FIRX = 0x4c5a4658, LLZ_TAG_ADPT = 0x4c5a4144
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))
@@ -90,6 +90,9 @@ void llz_host_part_spectra(float *dst, const float *taps, int flt_len, int N, co
  * 1 / (2 N).  Entry i > 0 is bin bitrev(i) (over log2 block bits); entry 0 packs the two real bins: (DC, Nyquist).  cs:
  * llz_host_cs_table(cs, N); z: 2 N doubles of work space */
 void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int block, const double *cs, double *z);
+/* the way back (llz_adapt_mc_get_taps): the first `count` <= block samples of the real sequence whose packed row (layout and
+ * 1 / (2 N) as above) is `row`, by an N-point transform in double, each rounded to float once; cs, z as above */
+void llz_host_stream_taps(float *taps, int count, const float *row, int block, const double *cs, double *z);
 /* the device table of both delay-line forms uploaded through llzs_h2d_table: [block / 2] complex W_block^m, then [block] complex
  * W_N^bitrev(i); d_tw: 2 (block / 2 + block) floats */
 int  llz_host_stream_twiddles(float *d_tw, int block);

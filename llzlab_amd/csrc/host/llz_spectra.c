@@ -1,6 +1,7 @@
 /* llz_spectra.c -- the host side of the frequency-domain FIR forms (llz_fir_host.c parts 2 to 4, llz_fir_stream_host.c,
- * llz_fir_matrix_host.c): the quadrant-exact cos / sin table, the double-precision transform of a tap partition, the two packings
- * of its bins, the twiddles of the delay-line forms, the chunked upload of tap rows and the double -> float copy of caller taps.
+ * llz_fir_matrix_host.c, llz_adapt_host.c): the quadrant-exact cos / sin table, the double-precision transform of a tap partition,
+ * the two packings of its bins and the way back from a packed row to taps, the twiddles of the delay-line forms, the chunked
+ * upload of tap rows and the double -> float copy of caller taps.
  * Shared and per-row handles build their spectra here, so equal taps give equal float32 entries (tests/fir_tables_driver.c). */
 #include <math.h>
 #include <stdlib.h>
@@ -23,16 +24,10 @@ static int spectra_bitrev(int i, int bits)
     return r;
 }
 
-/* z = DFT_N(taps[p B .. p B + B), zero-padded), B = N / 2, by radix-2 decimation in frequency in double, in place and left in
- * that transform's output order: entry e is bin bitrev_N(e) */
-static void spectra_partition(double *z, const float *taps, int flt_len, int p, int N, const double *cs)
+/* z = DFT_N(z) by radix-2 decimation in frequency in double, in place and left in that transform's output order: entry e is bin
+ * bitrev_N(e) */
+static void spectra_dif(double *z, int N, const double *cs)
 {
-    const int B = N / 2;
-    for (int i = 0; i < N; i++) {
-        const long t = (long)p * B + i;
-        z[2 * i] = (i < B && t < flt_len) ? (double)taps[t] : 0.0;
-        z[2 * i + 1] = 0.0;
-    }
     for (int span = N; span >= 2; span /= 2) {
         const int half = span / 2, step = N / span;
         for (int base = 0; base < N; base += span)
@@ -44,6 +39,19 @@ static void spectra_partition(double *z, const float *taps, int flt_len, int p, 
                 b[0] = dr * wr - di * wi; b[1] = dr * wi + di * wr;
             }
     }
+}
+
+/* z = DFT_N(taps[p B .. p B + B), zero-padded), B = N / 2, by radix-2 decimation in frequency in double, in place and left in
+ * that transform's output order: entry e is bin bitrev_N(e) */
+static void spectra_partition(double *z, const float *taps, int flt_len, int p, int N, const double *cs)
+{
+    const int B = N / 2;
+    for (int i = 0; i < N; i++) {
+        const long t = (long)p * B + i;
+        z[2 * i] = (i < B && t < flt_len) ? (double)taps[t] : 0.0;
+        z[2 * i + 1] = 0.0;
+    }
+    spectra_dif(z, N, cs);
 }
 
 /* Row p = the whole transform / N, rounded to float once: the device's forward transform leaves its bins in the same order, and
@@ -74,6 +82,25 @@ void llz_host_stream_spectra(float *dst, const float *taps, int flt_len, int blo
             row[2 * i + 1] = (float)(z[4 * i + 1] * scale);
         }
     }
+}
+
+/* The way back from one packed row (llz_adapt_mc_get_taps): the row holds Z_k / (2 N), k = 0 .. block, of a real sequence's
+ * N-point spectrum Z, so sample t = (1 / N) sum_k Z_k e^(+2 pi j k t / N) = 2 Re DFT_N(conj(row), mirrored to all N bins)[t].
+ * The first `count` samples, rounded to float once. */
+void llz_host_stream_taps(float *taps, int count, const float *row, int block, const double *cs, double *z)
+{
+    const int N = 2 * block;
+    int bits = 0;
+    while ((1 << bits) < block) bits++;
+    z[0] = (double)row[0]; z[1] = 0.0;
+    z[2 * block] = (double)row[1]; z[2 * block + 1] = 0.0;
+    for (int i = 1; i < block; i++) {
+        const int k = spectra_bitrev(i, bits);
+        z[2 * k] = (double)row[2 * i]; z[2 * k + 1] = -(double)row[2 * i + 1];
+        z[2 * (N - k)] = (double)row[2 * i]; z[2 * (N - k) + 1] = (double)row[2 * i + 1];
+    }
+    spectra_dif(z, N, cs);
+    for (int t = 0; t < count; t++) taps[t] = (float)(2.0 * z[2 * spectra_bitrev(t, bits + 1)]);
 }
 
 /* the transform's twiddles W_block^m, m < block / 2, then the split twiddles by position: W_N^bitrev(i), i < block */

@@ -63,6 +63,8 @@ enum {
     LLZS_TUNE_OLS_SUPERBLOCK,       /* 1024-point overlap-save on large batches with 32 KB-aligned rows: 1 = the super-block walk
                                      * on small batches too (never without the alignment), 0 = the segment walk */
     LLZS_TUNE_CSD_SCRATCH_KB,       /* llz_csd_mc: cap of the run-partial scratch in KiB (the library's own: 256 MiB), read per call */
+    LLZS_TUNE_ADAPT_PPW,            /* llz_adapt_mc: partitions per workgroup of the weight update (1..64), read per call; no bit
+                                     * of the result depends on it */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -221,6 +223,21 @@ int llzs_fir_matrix_mac_fade_f32(int block, const float *hspec, const float *hsp
 int llzs_fir_matrix_inv_fade_f32(int block, const float *ypart, const float *ypart_new, const unsigned char *ofade,
                                  const float *tw, float *out, int outputs, int nblk, int j0, int groups, long n_out,
                                  long out_pitch, int fade_done, int fade_blocks, void *stream);
+/* the partitioned frequency-domain NLMS adaptive filter (fir_adapt.hip; include/llz_adapt.h), block = 64 .. 2048: two launches
+ * per block, ordered by the stream.  w = [channels][P][block] complex, the weights' packed spectra laid out and scaled as
+ * llz_host_stream_spectra builds them; tw, ring ([channels][R][block] complex), prev as llzs_fir_stream_f32's; g = [channels]
+ * [block] complex scratch; mu = [channels] step sizes on the device, 0 = the channel is frozen; x, d, e, y = [channels][pitch],
+ * y may be NULL.
+ * filter: block j of the call's nblk: its spectrum into ring slot `slot` (prev updated by block nblk - 1), y = the filter's
+ *         output with the bits of llzs_fir_stream_f32 for these spectra, e = d - y, and for the channels with mu != 0 g = mu E /
+ *         (D + delta), D the power of the P spectra the product walked.
+ * update: w_p += conj(X_(j-p)) g under the gradient constraint (samples from min(block, flt_len - p block) on zeroed), every p,
+ *         every channel with mu != 0; the same block and slot as the filter launch in front of it. */
+int llzs_fir_adapt_filter_f32(int block, int flt_len, const float *w, const float *tw, float *ring, float *prev, float *g,
+                              const float *mu, float delta, const float *x, const float *d, float *e, float *y, int channels,
+                              int nblk, int j, long pitch, int P, int R, int slot, void *stream);
+int llzs_fir_adapt_update_f32(int block, int flt_len, float *w, const float *tw, const float *ring, const float *g,
+                              const float *mu, int channels, int P, int R, int slot, void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

@@ -314,6 +314,72 @@ class FirStreamMC:
     __del__ = close
 
 
+class AdaptMC:
+    """channels x frame_len float32, planar, frame_len = k x block: llz_adapt_mc_*, the partitioned frequency-domain NLMS
+    adaptive filter (include/llz_adapt.h) -- the stream convolver's delay line with an error, a normalised gradient and a
+    constrained weight update per block.  The weights start at zero; mu is every channel's step size (0 = frozen), delta the
+    regularisation of the power (None: 1e-3 x block).  frame_len defaults to block and is the longest call."""
+
+    def __init__(self, channels, block, flt_len, frame_len=None, mu=0.5, delta=None, stream=None):
+        self._L = capi.lib()
+        frame_len = block if frame_len is None else frame_len
+        delta = 1e-3 * block if delta is None else delta
+        self.handle = check_handle(self._L.llz_adapt_mc_init(channels, block, frame_len, flt_len, mu, delta), "llz_adapt_mc_init")
+        self.channels, self.block, self.frame_len, self.flt_len = channels, block, frame_len, flt_len
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_adapt_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_adapt_mc_set_stream")
+
+    def plan(self):
+        """(N = 2 block, partitions P, ring slots R, blocks per call k)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_adapt_mc_plan(self.handle, out), "llz_adapt_mc_plan")
+        return tuple(out)
+
+    def process(self, x, d, e, y=None):
+        """x (reference), d (desired), e (error, written), y (filter output, written when given): [channels, n] float32 with n
+        a multiple of block up to frame_len (torch device tensors or numpy).  Returns e."""
+        n = (x.numel() if hasattr(x, "numel") else x.size) // self.channels
+        count = self.channels * n
+        check(self._L.llz_adapt_mc(self.handle, _typed(x, "float32", count, "AdaptMC.process x"),
+                                   _typed(d, "float32", count, "AdaptMC.process d"),
+                                   _typed(e, "float32", count, "AdaptMC.process e"),
+                                   None if y is None else _typed(y, "float32", count, "AdaptMC.process y"), n), "llz_adapt_mc")
+        return e
+
+    def set_step(self, first, mu):
+        """step sizes of channels first .. first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
+        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float32)
+        check(self._L.llz_adapt_mc_set_step(self.handle, first, mu.shape[0], mu.ctypes.data), "llz_adapt_mc_set_step")
+
+    def set_taps(self, first, taps):
+        """replace the weights of channels first .. first + count - 1; taps: [count, flt_len], or [flt_len] for one channel"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps = taps[None, :] if taps.ndim == 1 else taps
+        if taps.ndim != 2 or taps.shape[1] != self.flt_len:
+            raise LlzError(f"AdaptMC.set_taps: taps must be [count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_adapt_mc_set_taps(self.handle, first, taps.shape[0], taps.ctypes.data), "llz_adapt_mc_set_taps")
+
+    def get_taps(self, first=0, count=None):
+        """the weights of channels first .. first + count - 1 (default: all from first) as [count, flt_len] float32"""
+        count = self.channels - first if count is None else count
+        taps = np.empty((max(count, 0), self.flt_len), dtype=np.float32)
+        check(self._L.llz_adapt_mc_get_taps(self.handle, first, count, taps.ctypes.data), "llz_adapt_mc_get_taps")
+        return taps
+
+    def reset(self, clear_taps=False):
+        check(self._L.llz_adapt_mc_reset(self.handle, 1 if clear_taps else 0), "llz_adapt_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_adapt_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 class FirMatrixMC:
     """[inputs, frame_len] -> [outputs, frame_len] float32, planar, frame_len = k x block: llz_fir_matrix_mc_*, the stream
     convolver with a filter per path, y_o = sum_i x_i * h[o, i].  taps: [outputs, inputs, flt_len]; a path whose taps are all
