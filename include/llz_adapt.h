@@ -3,7 +3,8 @@
  * frequency-domain NLMS filter (PBFDAF, also called MDF) that TRACKS a response while the signals run -- echo, feedback and
  * crosstalk cancellation per microphone, online identification of a room or cabinet, keeping the taps of a llz_fir_stream_mc or
  * llz_fir_matrix_mc handle up to date from a reference x and a microphone signal d.  The reference has no counterpart; the
- * checker is a float64 model written from the definition below (tests/adapt_checks.py).
+ * checker is a float64 model written from the definition below (tests/adapt_checks.py).  One reference per channel: where an
+ * output hears several references at once, llz_adapt_matrix_mc (llz_adapt_matrix.h) is the form to use.
  *
  * It is the stream convolver of llz_fir.h part 5 -- the same block, partitions, ring of input spectra and kernel walk -- plus
  * an error, a normalised gradient and a constrained weight update on the same ring.

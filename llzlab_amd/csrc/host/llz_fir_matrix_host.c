@@ -20,8 +20,6 @@
 #define FIRX_MAX_BLOCK 4096
 #define FIRX_MAX_PORTS 4096                     /* inputs, outputs */
 #define FIRX_MAX_BLOCKS 65535                   /* blocks of a launch: a grid dimension */
-#define FIRX_WG_TARGET 1024                     /* workgroups of the product asked for before the sum over inputs stays whole */
-#define FIRX_MAX_GROUPS 32
 #define FIRX_SCRATCH_BYTES ((size_t)64 << 20)   /* the partial spectra of a flush beyond this go in several passes */
 
 typedef struct {
@@ -63,18 +61,6 @@ static void firx_destroy(firx_t *f)
     free(f->conn);
     f->tag = 0;
     free(f);
-}
-
-/* G and the inputs per group from (inputs, outputs, block) alone: as many groups as bring the product to FIRX_WG_TARGET
- * workgroups per block, FIRX_MAX_GROUPS at the most, of equal size but for a ragged last one */
-static void firx_groups(int inputs, int outputs, int block, int *G, int *gsize)
-{
-    const long rows = (long)outputs * (block >= 1024 ? block / 512 : 1);        /* workgroups of one group: outputs x bin tiles */
-    long cap = (FIRX_WG_TARGET + rows - 1) / rows;
-    if (cap > FIRX_MAX_GROUPS) cap = FIRX_MAX_GROUPS;
-    if (cap > inputs) cap = inputs;
-    *gsize = (int)((inputs + cap - 1) / cap);
-    *G = (inputs + *gsize - 1) / *gsize;
 }
 
 static int firx_row_connected(const float *taps, int flt_len)
@@ -156,7 +142,7 @@ unsigned long llz_fir_matrix_mc_init(int inputs, int outputs, int block, int fra
     f->k = frame_len / block;
     f->P = (flt_len + block - 1) / block;
     f->R = f->P + f->k - 1;
-    firx_groups(inputs, outputs, block, &f->G, &f->gsize);
+    llz_host_matrix_groups(inputs, outputs, block, &f->G, &f->gsize);
     const size_t paths = (size_t)outputs * (size_t)inputs;
     const size_t ybytes1 = sizeof(float) * 2 * (size_t)f->G * (size_t)outputs * (size_t)block;     /* one block's partials */
     const int nflush = (flt_len - 1 + block - 1) / block;

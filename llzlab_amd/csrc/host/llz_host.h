@@ -18,7 +18,7 @@ enum {
     LLZ_TAG_FIR1 = 0x4c5a4631, LLZ_TAG_FIRM = 0x4c5a464d, LLZ_TAG_IIR1 = 0x4c5a4931, LLZ_TAG_IIRM = 0x4c5a494d,
     LLZ_TAG_RS1 = 0x4c5a5231, LLZ_TAG_RSM = 0x4c5a524d, LLZ_TAG_FFT1 = 0x4c5a5431, LLZ_TAG_FFTB = 0x4c5a5442,
     LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942, LLZ_TAG_FIRS = 0x4c5a4653,
-    LLZ_TAG_FIRX = 0x4c5a4658, LLZ_TAG_ADPT = 0x4c5a4144
+    LLZ_TAG_FIRX = 0x4c5a4658, LLZ_TAG_ADPT = 0x4c5a4144, LLZ_TAG_ADPX = 0x4c5a4158
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))
@@ -103,6 +103,22 @@ int  llz_host_stream_twiddles(float *d_tw, int block);
  * `stream`, behind the calls already issued.  Out of host memory: LLZ_ERR_NOMEM and a message naming `who`. */
 int llz_host_load_spectra(const char *who, float *d_dst, size_t row, int count, const float *taps, int flt_len, int N, int packed,
                           int at_init, void *stream);
+
+/* The input groups of the matrix product (llzs_fir_matrix_mac_f32) for llz_fir_matrix_mc and llz_adapt_matrix_mc, which
+ * promises the former's summation order: G and the inputs per group from (inputs, outputs, block) alone -- as many groups as
+ * bring the product to LLZ_MATRIX_WG_TARGET workgroups per block, LLZ_MATRIX_MAX_GROUPS at the most, of equal size but for a
+ * ragged last one */
+#define LLZ_MATRIX_WG_TARGET 1024               /* workgroups of the product asked for before the sum over inputs stays whole */
+#define LLZ_MATRIX_MAX_GROUPS 32
+static inline void llz_host_matrix_groups(int inputs, int outputs, int block, int *G, int *gsize)
+{
+    const long rows = (long)outputs * (block >= 1024 ? block / 512 : 1);        /* workgroups of one group: outputs x bin tiles */
+    long cap = (LLZ_MATRIX_WG_TARGET + rows - 1) / rows;
+    if (cap > LLZ_MATRIX_MAX_GROUPS) cap = LLZ_MATRIX_MAX_GROUPS;
+    if (cap > inputs) cap = inputs;
+    *gsize = (int)((inputs + cap - 1) / cap);
+    *G = (inputs + *gsize - 1) / *gsize;
+}
 
 /* a malloc'ed float copy of `count` double taps; NULL, with a message naming `who`, when out of host memory */
 float *llz_host_taps_f32(const char *who, const double *taps, size_t count);

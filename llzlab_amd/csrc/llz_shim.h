@@ -63,7 +63,7 @@ enum {
     LLZS_TUNE_OLS_SUPERBLOCK,       /* 1024-point overlap-save on large batches with 32 KB-aligned rows: 1 = the super-block walk
                                      * on small batches too (never without the alignment), 0 = the segment walk */
     LLZS_TUNE_CSD_SCRATCH_KB,       /* llz_csd_mc: cap of the run-partial scratch in KiB (the library's own: 256 MiB), read per call */
-    LLZS_TUNE_ADAPT_PPW,            /* llz_adapt_mc: partitions per workgroup of the weight update (1..64), read per call; no bit
+    LLZS_TUNE_ADAPT_PPW,            /* llz_adapt_mc, llz_adapt_matrix_mc: partitions per workgroup of the weight update (1..64), read per call; no bit
                                      * of the result depends on it */
     LLZS_TUNE_COUNT
 };
@@ -238,6 +238,23 @@ int llzs_fir_adapt_filter_f32(int block, int flt_len, const float *w, const floa
                               int nblk, int j, long pitch, int P, int R, int slot, void *stream);
 int llzs_fir_adapt_update_f32(int block, int flt_len, float *w, const float *tw, const float *ring, const float *g,
                               const float *mu, int channels, int P, int R, int slot, void *stream);
+/* the multi-reference adaptive filter (fir_adapt_matrix.hip; include/llz_adapt_matrix.h), block = 64 .. 2048, on the matrix
+ * convolver's rings: behind llzs_fir_matrix_fwd_f32 of a call's nblk blocks one power launch, then per block
+ * llzs_fir_matrix_mac_f32 (nblk = 1, head = the block's slot, conn all ones), error and update, ordered by the stream.  w =
+ * [outputs][inputs][P][block] complex laid out and scaled as hspec; den = [nblk][block] pairs of floats; g = [outputs][block]
+ * complex scratch; mu = [outputs] step sizes on the device, 0 = the output is frozen; d, e, y = [outputs][pitch], y may be NULL.
+ * power:  den[j] = delta + sum_i sum_p |ring_i[(slot + j - p) mod R]|^2, i ascending, p ascending within i, for every block j of
+ *         the call; position 0 holds the DC and the Nyquist bin's denominators, every other position its own twice.
+ * error:  block j: the `groups` partials of ypart ([groups][outputs][block]) added ascending, y with the bits of
+ *         llzs_fir_matrix_inv_f32, e = d - y, and for the outputs with mu != 0 g = mu E / den (den: block j's row).
+ * update: w[o][i][p] += conj(X_(i, j-p)) g_o under the gradient constraint, every path and partition of every output with
+ *         mu != 0; slot = the block's ring slot.  The adapt_ppw override groups the partitions of a path; no bit depends on it. */
+int llzs_fir_adapt_matrix_power_f32(int block, int flt_len, const float *ring, float *den, float delta, int inputs, int nblk,
+                                    int P, int R, int slot, void *stream);
+int llzs_fir_adapt_matrix_error_f32(int block, const float *ypart, const float *tw, const float *den, float *g, const float *mu,
+                                    const float *d, float *e, float *y, int outputs, int groups, int j, long pitch, void *stream);
+int llzs_fir_adapt_matrix_update_f32(int block, int flt_len, float *w, const float *tw, const float *ring, const float *g,
+                                     const float *mu, int inputs, int outputs, int P, int R, int slot, void *stream);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

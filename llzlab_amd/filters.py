@@ -460,6 +460,81 @@ class FirMatrixMC:
     __del__ = close
 
 
+class AdaptMatrixMC:
+    """x [inputs, n], d / e / y [outputs, n] float32, planar, n a multiple of block up to frame_len: llz_adapt_matrix_mc_*, the
+    multi-reference frequency-domain NLMS adaptive filter (include/llz_adapt_matrix.h) -- the matrix convolver's delay lines with
+    a weight set per path (o, i), the error of output o driving all of its paths, normalised by the joint power of all
+    references.  The weights start at zero; mu is every output's step size (0 = frozen), delta the regularisation of the power
+    (None: 1e-3 x block x inputs).  frame_len defaults to block and is the longest call."""
+
+    def __init__(self, inputs, outputs, block, flt_len, frame_len=None, mu=0.5, delta=None, stream=None):
+        self._L = capi.lib()
+        frame_len = block if frame_len is None else frame_len
+        delta = 1e-3 * block * inputs if delta is None else delta
+        self.handle = check_handle(self._L.llz_adapt_matrix_mc_init(inputs, outputs, block, frame_len, flt_len, mu, delta),
+                                   "llz_adapt_matrix_mc_init")
+        self.inputs, self.outputs, self.block, self.frame_len, self.flt_len = inputs, outputs, block, frame_len, flt_len
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_adapt_matrix_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_adapt_matrix_mc_set_stream")
+
+    def plan(self):
+        """(N = 2 block, partitions P, ring slots R, blocks per call k, input groups G, inputs per group)"""
+        out = (C.c_int * 6)()
+        check(self._L.llz_adapt_matrix_mc_plan(self.handle, out), "llz_adapt_matrix_mc_plan")
+        return tuple(out)
+
+    def process(self, x, d, e, y=None):
+        """x (references): [inputs, n]; d (desired), e (error, written), y (filter output, written when given): [outputs, n]
+        float32 (torch device tensors or numpy).  Returns e."""
+        n = (x.numel() if hasattr(x, "numel") else x.size) // self.inputs
+        count = self.outputs * n
+        check(self._L.llz_adapt_matrix_mc(self.handle, _typed(x, "float32", self.inputs * n, "AdaptMatrixMC.process x"),
+                                          _typed(d, "float32", count, "AdaptMatrixMC.process d"),
+                                          _typed(e, "float32", count, "AdaptMatrixMC.process e"),
+                                          None if y is None else _typed(y, "float32", count, "AdaptMatrixMC.process y"), n),
+              "llz_adapt_matrix_mc")
+        return e
+
+    def set_step(self, out_first, mu):
+        """step sizes of outputs out_first .. out_first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
+        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float32)
+        check(self._L.llz_adapt_matrix_mc_set_step(self.handle, out_first, mu.shape[0], mu.ctypes.data),
+              "llz_adapt_matrix_mc_set_step")
+
+    def set_taps(self, out_first, in_first, taps):
+        """replace the weights of the paths [out_first, +out_count) x [in_first, +in_count); taps: [out_count, in_count,
+        flt_len], or [flt_len] for one path"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps = taps[None, None, :] if taps.ndim == 1 else taps
+        if taps.ndim != 3 or taps.shape[2] != self.flt_len:
+            raise LlzError(f"AdaptMatrixMC.set_taps: taps must be [out_count, in_count, flt_len = {self.flt_len}], got {taps.shape}")
+        check(self._L.llz_adapt_matrix_mc_set_taps(self.handle, out_first, taps.shape[0], in_first, taps.shape[1],
+                                                   taps.ctypes.data), "llz_adapt_matrix_mc_set_taps")
+
+    def get_taps(self, out_first=0, out_count=None, in_first=0, in_count=None):
+        """the weights of the paths [out_first, +out_count) x [in_first, +in_count) (default: all from the firsts) as
+        [out_count, in_count, flt_len] float32: what FirMatrixMC takes"""
+        out_count = self.outputs - out_first if out_count is None else out_count
+        in_count = self.inputs - in_first if in_count is None else in_count
+        taps = np.empty((max(out_count, 0), max(in_count, 0), self.flt_len), dtype=np.float32)
+        check(self._L.llz_adapt_matrix_mc_get_taps(self.handle, out_first, out_count, in_first, in_count, taps.ctypes.data),
+              "llz_adapt_matrix_mc_get_taps")
+        return taps
+
+    def reset(self, clear_taps=False):
+        check(self._L.llz_adapt_matrix_mc_reset(self.handle, 1 if clear_taps else 0), "llz_adapt_matrix_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_adapt_matrix_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
