@@ -238,6 +238,18 @@ def lib():
     sig("llz_resample_mc_set_stream", i, ul, vp)
     sig("llz_resample_mc_get_matrix", i, ul, vp, i)
     sig("llz_resample_mc_set_matrix", i, ul, vp, i)
+    # llz_asrc.h
+    sig("llz_asrc_mc_init", ul, i, i, i, i, d, d, i, d)
+    sig("llz_asrc_mc_uninit", None, ul)
+    sig("llz_asrc_mc_set_stream", i, ul, vp)
+    sig("llz_asrc_mc", lng, ul, vp, lng, vp, lng, ip)
+    sig("llz_asrc_mc_out_len", lng, ul, lng, ip)
+    sig("llz_asrc_mc_set_step", i, ul, i, i, dp, lng)
+    sig("llz_asrc_mc_get_step", i, ul, i, i, dp, C.POINTER(C.c_long))
+    sig("llz_asrc_mc_next_time", i, ul, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_uint))
+    sig("llz_asrc_mc_get_table", i, ul, vp, i)
+    sig("llz_asrc_mc_reset", i, ul)
+    sig("llz_asrc_mc_plan", i, ul, C.POINTER(C.c_int))
     # llz_fft.h / llz_fft_fixed.h
     sig("llz_fft_init", ul, i)
     sig("llz_fft_uninit", None, ul)

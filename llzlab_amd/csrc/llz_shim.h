@@ -65,6 +65,7 @@ enum {
     LLZS_TUNE_CSD_SCRATCH_KB,       /* llz_csd_mc: cap of the run-partial scratch in KiB (the library's own: 256 MiB), read per call */
     LLZS_TUNE_ADAPT_PPW,            /* llz_adapt_mc, llz_adapt_matrix_mc: partitions per workgroup of the weight update (1..64), read per call; no bit
                                      * of the result depends on it */
+    LLZS_TUNE_ASRC_TABLE_GLOBAL,    /* llz_asrc_mc: 1 = the table is read from global memory even where it fits the LDS form, read at init */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -375,6 +376,17 @@ int llzs_decimate_i16(const short *buf /* n hist + num_in */, short *out, const 
                       int num_out, double gain, void *stream);
 int llzs_interp_i16(const short *x /* num_in + K zero padded */, short *out, const double *p, int L, int K,
                     int num_in, double gain, void *stream);
+
+/* ---- arbitrary-ratio resampler (asrc.hip; include/llz_asrc.h) ----
+ * state: [channels] llz_asrc_state (llz_asrc_time.h) on the device, a channel's position, step and glide in front of the
+ * call; table: [phases + 1] rows of LLZ_ASRC_PITCH(T) floats; hist: [channels][T - 1], the samples in front of in
+ * ([channels][in_pitch], n_in >= 1 of them).  llzs_asrc_f32 stores output j < count_c of channel c, count_c the state's own
+ * count for n_in, to out[c][j] and nothing else; max_count: the largest count (>= 1), which sizes the grid; table_lds: 1 = the
+ * table is loaded into LDS (LLZ_ERR_RANGE beyond LLZ_ASRC_LDS_TABLE_BYTES), 0 = read through the caches; the same bits either
+ * way.  llzs_asrc_advance moves every channel's state behind the call. */
+int llzs_asrc_f32(const float *in, float *out, const float *hist, const float *table, const void *state, int channels,
+                  long n_in, long in_pitch, long out_pitch, int T, int phases, int table_lds, long max_count, void *stream);
+int llzs_asrc_advance(void *state, int channels, long n_in, int T, void *stream);
 
 /* ---- FFT ---- */
 /* float32 batch, in place; cs = size cos then size sin values (float). inverse: 0 forward, 1 inverse (divides by size) */

@@ -792,6 +792,87 @@ class ResampleMC:
     __del__ = close
 
 
+class AsrcMC:
+    """channels x n_in float32 -> a count of outputs per channel: llz_asrc_mc_*, the arbitrary-ratio resampler
+    (include/llz_asrc.h) -- a polyphase windowed-sinc table with linear interpolation between phases, time in 64-bit fixed
+    point, a step (input samples per output) per channel that may glide while the signals run.  frame_len is the longest
+    n_in; cutoff=None means min(1, 1 / step), times 0.9 when that is below 1."""
+
+    def __init__(self, channels, frame_len, step=1.0, taps=32, phases=512, cutoff=None, gain=1.0, win=KAISER, stream=None):
+        self._L = capi.lib()
+        if cutoff is None:
+            cutoff = min(1.0, 1.0 / step) if step > 0 else 1.0
+            cutoff = 0.9 * cutoff if cutoff < 1.0 else cutoff
+        self.handle = check_handle(self._L.llz_asrc_mc_init(channels, frame_len, taps, phases, cutoff, gain, win, step),
+                                   "llz_asrc_mc_init")
+        self.channels, self.frame_len, self.taps, self.phases, self.cutoff = channels, frame_len, taps, phases, cutoff
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_asrc_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_asrc_mc_set_stream")
+
+    def plan(self):
+        """(taps, phases, history samples kept per channel, table form: 0 = in LDS, 1 = read from global memory)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_asrc_mc_plan(self.handle, out), "llz_asrc_mc_plan")
+        return tuple(out)
+
+    def out_len(self, n_in):
+        """the counts [channels] the next call of n_in samples would deliver; the state does not move"""
+        counts = (C.c_int * self.channels)()
+        check(self._L.llz_asrc_mc_out_len(self.handle, n_in, counts), "llz_asrc_mc_out_len")
+        return np.array(counts, dtype=np.int64)
+
+    def process(self, x, out):
+        """x: [channels, n_in] float32, n_in <= frame_len (n_in = 0: an empty array); out: [channels, out_pitch] float32, row c
+        receives counts[c] outputs and is not written behind them (torch device tensors or numpy).  Returns counts."""
+        n_in = (x.numel() if hasattr(x, "numel") else x.size) // self.channels
+        out_pitch = (out.numel() if hasattr(out, "numel") else out.size) // self.channels
+        counts = (C.c_int * self.channels)()
+        check(self._L.llz_asrc_mc(self.handle, _typed(x, "float32", self.channels * n_in, "AsrcMC.process x") if n_in else None,
+                                  n_in, _typed(out, "float32", self.channels * out_pitch, "AsrcMC.process out"), out_pitch,
+                                  counts), "llz_asrc_mc")
+        return np.array(counts, dtype=np.int64)
+
+    def set_step(self, first, step, ramp=0):
+        """steps of channels first .. first + count - 1: [count] values in [1/16, 16] (or one number), reached over `ramp`
+        outputs (0: at once)"""
+        step = _f64(np.atleast_1d(step))
+        check(self._L.llz_asrc_mc_set_step(self.handle, first, step.shape[0], step.ctypes.data_as(_dp), ramp),
+              "llz_asrc_mc_set_step")
+
+    def get_step(self, first=0, count=None):
+        """(the step behind each channel's next output, the outputs its glide has left) of channels first .. first + count - 1"""
+        count = self.channels - first if count is None else count
+        step, left = np.zeros(max(count, 1)), (C.c_long * max(count, 1))()
+        check(self._L.llz_asrc_mc_get_step(self.handle, first, count, step.ctypes.data_as(_dp), left), "llz_asrc_mc_get_step")
+        return step, np.array(left, dtype=np.int64)
+
+    def next_time(self, first=0, count=None):
+        """the time of each channel's next output as (whole input samples, fraction in units of 2^-32), two int arrays"""
+        count = self.channels - first if count is None else count
+        whole, frac = (C.c_longlong * max(count, 1))(), (C.c_uint * max(count, 1))()
+        check(self._L.llz_asrc_mc_next_time(self.handle, first, count, whole, frac), "llz_asrc_mc_next_time")
+        return np.array(whole, dtype=np.int64), np.array(frac, dtype=np.int64)
+
+    def table(self):
+        """G of the definition: [phases + 1, taps] float32"""
+        g = np.empty((self.phases + 1, self.taps), dtype=np.float32)
+        check(self._L.llz_asrc_mc_get_table(self.handle, g.ctypes.data, g.size), "llz_asrc_mc_get_table")
+        return g
+
+    def reset(self):
+        check(self._L.llz_asrc_mc_reset(self.handle), "llz_asrc_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_asrc_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ FFT
 class Fft:
     """Reference API: complex128 host arrays, forward unscaled, inverse / N."""
