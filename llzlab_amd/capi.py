@@ -21,6 +21,7 @@ FIR_ALGO_OVERLAP_SAVE_4096 = 5
 FIR_ALGO_OVERLAP_SAVE_8192 = 6
 FIR_ALGO_PARTITIONED = 7
 OVERLAP_HIGH, OVERLAP_LOW = 0, 1      # llz_asmodel.h: 3/4 and 1/2 overlap
+PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1    # llz_pfb.h
 MDCT_ORIGIN, MDCT_FFT, MDCT_FFT4 = 0, 1, 2
 MDCT_SINE, MDCT_KBD = 0, 1
 PCM_F32, PCM_I16, PCM_I16_FAST = 0, 1, 2
@@ -321,6 +322,17 @@ def lib():
     sig("llz_stft_mc_set_stream", i, ul, vp)
     sig("llz_stft_mc_analysis", i, ul, vp, vp, vp, i)
     sig("llz_stft_mc_synthesis", i, ul, vp, vp, vp, i)
+    # llz_pfb.h
+    sig("llz_pfb_mc_init", ul, i, i, i, i, vp, vp, i)
+    sig("llz_pfb_mc_uninit", None, ul)
+    sig("llz_pfb_mc_bins", i, ul)
+    sig("llz_pfb_mc_delay", i, ul)
+    sig("llz_pfb_mc_set_stream", i, ul, vp)
+    sig("llz_pfb_mc_analysis", i, ul, vp, vp, vp, i)
+    sig("llz_pfb_mc_synthesis", i, ul, vp, vp, vp, i)
+    sig("llz_pfb_mc_reset", i, ul)
+    sig("llz_pfb_mc_frames", i, ul, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
+    sig("llz_pfb_mc_plan", i, ul, i, C.POINTER(C.c_int))
     sig("llz_iir_mc_init", ul, i, i, dp, i, dp)
     sig("llz_iir_mc_uninit", None, ul)
     sig("llz_iir_mc", i, ul, vp, vp, i)

@@ -66,6 +66,8 @@ enum {
     LLZS_TUNE_ADAPT_PPW,            /* llz_adapt_mc, llz_adapt_matrix_mc: partitions per workgroup of the weight update (1..64), read per call; no bit
                                      * of the result depends on it */
     LLZS_TUNE_ASRC_TABLE_GLOBAL,    /* llz_asrc_mc: 1 = the table is read from global memory even where it fits the LDS form, read at init */
+    LLZS_TUNE_PFB_GLOBAL,           /* llz_pfb_mc: 1 = the analysis fold reads its samples through the caches even where a run's span fits LDS,
+                                     * read per call; no bit of the result depends on it */
     LLZS_TUNE_COUNT
 };
 int llzs_tune(int id);                                   /* current override or -1 */
@@ -493,6 +495,22 @@ int llzs_stft_bins_large_f32(const float *z, float *re, float *im, int N, long g
 int llzs_stft_mirror_large_f32(const float *re, const float *im, float *z, int N, long g0, int count, void *stream);
 int llzs_stft_ola_large_f32(const float *z, float *x, const float *ola_old, float *ola_new, float *tail, const float *w,
                             int frames, int F, int N, long x_pitch, long g0, int count, float magic, void *stream);
+
+/* ---- polyphase DFT filter bank (pfb.hip; include/llz_pfb.h), float32, M bands, hop D, prototype length L = P M ----
+ * x planar [C][frames*D] (row pitch x_pitch), spectra [C][frames][M/2+1]; cs: cos then sin of 2*pi*i/M.  rot0, rstep: frame f
+ * of the call is rotated by (rot0 + f rstep) mod M (FRAME phase: 0, 0; TIME phase: (m + 1) D mod M of the call's first frame, D).
+ * analysis: hist [C][L-D], the samples in front of x; w: L floats.  Synthesis runs per chunk of `count` frames f0 .. f0+count-1
+ * of the call: inverse writes the real inverse transforms, rotation undone, to u = [C][count][M]; ola adds g[i] u[i mod M] onto
+ * the tail ([C][L-D], tail_old != tail_new), oldest frame first, count D samples to x (the chunk's first sample) and the rest to
+ * tail_new.  plan: out[0..3] = analysis form (0 LDS span, 1 through the caches), frames per workgroup, workgroups, LDS bytes;
+ * out[4..7] = synthesis form (1), frames per workgroup, workgroups and LDS bytes of inverse over a chunk of `chunk` frames. */
+int llzs_pfb_analysis_f32(const float *x, const float *hist, float *re, float *im, const float *w, const float *cs,
+                          int channels, int frames, int M, int D, int L, int rot0, int rstep, long x_pitch, void *stream);
+int llzs_pfb_inverse_f32(const float *re, const float *im, float *u, const float *cs, int channels, int frames, int f0,
+                         int count, int M, int D, int rot0, int rstep, void *stream);
+int llzs_pfb_ola_f32(const float *u, float *x, const float *tail_old, float *tail_new, const float *g, int channels, int count,
+                     int M, int D, int L, long x_pitch, void *stream);
+int llzs_pfb_plan(int channels, int frames, int chunk, int M, int D, int L, int *out);
 
 /* MDCT (llz_mdct.c): y[r] = sum_c x[c]*A[r][c] in ascending c, separately rounded multiply and add (device doubles) */
 int llzs_matvec_exact_f64(const double *A, const double *x, double *y, int rows, int cols, void *stream);

@@ -12,7 +12,7 @@ import numpy as np
 from . import capi
 from .capi import (BAD_HANDLE, BLACKMAN, FIR_ALGO_AUTO, FIR_ALGO_OVERLAP_SAVE, FIR_ALGO_OVERLAP_SAVE_2048, FIR_ALGO_OVERLAP_SAVE_4096, FIR_ALGO_OVERLAP_SAVE_8192, FIR_ALGO_PARTITIONED, FIR_ALGO_TIME,  # noqa: F401
                    FIR_ALGO_TIME_MFMA, HAMMING, KAISER,
-                   PCM_F32, PCM_I16, PCM_I16_FAST, LlzError, check, check_handle)
+                   PCM_F32, PCM_I16, PCM_I16_FAST, PFB_PHASE_FRAME, PFB_PHASE_TIME, LlzError, check, check_handle)
 
 
 def _ptr(buf):
@@ -1339,6 +1339,80 @@ class StftMC:
     def close(self):
         if getattr(self, "handle", 0):
             self._L.llz_stft_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
+def pfb_prototype(bands, taps_per_band, win=KAISER):
+    """A prototype for PfbMC: the windowed-sinc low-pass of llz_fir_lpf_cof with bands * taps_per_band taps and cutoff 1 / bands,
+    as float32, scaled so that the squares of every bands / 4-th tap sum to about 1 (w = g at a hop of bands / 4 then returns the
+    input at about unit gain).  A convenience: how well a prototype reconstructs is its own property."""
+    h = fir_design("lpf", bands * taps_per_band, 1.0 / bands, win=win)
+    return (h * np.sqrt((bands // 4) / np.sum(h * h))).astype(np.float32)
+
+
+class PfbMC:
+    """llz_pfb_mc_*: the uniform DFT polyphase filter bank (include/llz_pfb.h), many channels and frames per call, float32;
+    x [channels, frames*hop], re/im [channels, frames, bins]; w (and g, default w): [taps_per_band * bands] float32 prototypes,
+    index 0 on a frame's oldest sample.  The handle carries both streams' state between calls."""
+
+    def __init__(self, channels, bands, hop, taps_per_band, w, g=None, phase=PFB_PHASE_FRAME, stream=None):
+        self._L = capi.lib()
+        n = bands * taps_per_band
+        w = None if w is None else np.ascontiguousarray(w, dtype=np.float32)
+        g = None if g is None else np.ascontiguousarray(g, dtype=np.float32)
+        for name, a in (("w", w), ("g", g)):
+            if a is not None and n > 0 and a.size != n:
+                raise LlzError(f"PfbMC: {name} holds {a.size} values, taps_per_band * bands = {n}")
+        self.handle = check_handle(self._L.llz_pfb_mc_init(channels, bands, hop, taps_per_band,
+                                                           None if w is None else w.ctypes.data,
+                                                           None if g is None else g.ctypes.data, phase), "llz_pfb_mc_init")
+        self.channels, self.bands, self.hop, self.taps_per_band, self.phase = channels, bands, hop, taps_per_band, phase
+        self.bins = self._L.llz_pfb_mc_bins(self.handle)
+        self.delay = self._L.llz_pfb_mc_delay(self.handle)
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_pfb_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_pfb_mc_set_stream")
+
+    def _frames(self, x, re, im):
+        frames = re.shape[1] if len(re.shape) == 3 else 0
+        _typed(x, "float32", self.channels * frames * self.hop, "PfbMC x")
+        _typed(re, "float32", self.channels * frames * self.bins, "PfbMC re")
+        _typed(im, "float32", self.channels * frames * self.bins, "PfbMC im")
+        return frames
+
+    def analysis(self, x, re, im):
+        frames = self._frames(x, re, im)
+        check(self._L.llz_pfb_mc_analysis(self.handle, _ptr(x), _ptr(re), _ptr(im), frames), "llz_pfb_mc_analysis")
+        return re, im
+
+    def synthesis(self, re, im, x):
+        frames = self._frames(x, re, im)
+        check(self._L.llz_pfb_mc_synthesis(self.handle, _ptr(re), _ptr(im), _ptr(x), frames), "llz_pfb_mc_synthesis")
+        return x
+
+    def reset(self):
+        check(self._L.llz_pfb_mc_reset(self.handle), "llz_pfb_mc_reset")
+
+    def frames(self):
+        """(analysis, synthesis) frames taken since init or reset"""
+        a, s = C.c_longlong(), C.c_longlong()
+        check(self._L.llz_pfb_mc_frames(self.handle, C.byref(a), C.byref(s)), "llz_pfb_mc_frames")
+        return a.value, s.value
+
+    def plan(self, frames):
+        """what a call of `frames` frames launches, per direction: (form, frames per workgroup, workgroups, LDS bytes) of the
+        analysis (form 0: a run's span staged in LDS, 1: samples read through the caches) and of the synthesis' inverse transforms"""
+        out = (C.c_int * 8)()
+        check(self._L.llz_pfb_mc_plan(self.handle, frames, out), "llz_pfb_mc_plan")
+        return tuple(out[:4]), tuple(out[4:])
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_pfb_mc_uninit(self.handle)
             self.handle = 0
 
     __del__ = close
