@@ -192,6 +192,47 @@ int   llz_bind(const char *who, llz_bind_t *b, int count, void *stream);
 void *llz_bind_scratch(llz_bind_t *b, size_t bytes, int *rc);     /* chains on *rc; freed by llz_bind_finish */
 int   llz_bind_finish(llz_bind_t *b, int count, void *stream, int rc);
 
+/* ---- llz_adapt_core.c: what the adaptive handles share (llz_adapt_mc, llz_adapt_matrix_mc) ---- */
+
+/* the refusals of an init behind its channel or port counts, with a message naming `who`, 1 when refused: block (a power of two
+ * in 64..2048; 4096 has a message of its own), frame_len = k x block with k >= 1 (max_blocks != 0: k in 1..max_blocks), flt_len,
+ * mu in 0..2, delta finite and above 0 */
+int  llz_adapt_refuse(const char *who, int block, int frame_len, int max_blocks, int flt_len, float mu, float delta);
+
+/* the step sizes of `count` rows (channels, outputs): the device array the kernels read and its host copy, which tells a call
+ * whether anything adapts */
+typedef struct {
+    float *h_mu, *d_mu;         /* HOST and device [count] */
+    int count, adapting;        /* rows whose mu is not zero */
+} llz_adapt_steps_t;
+/* every row at mu.  Out of host memory: LLZ_ERR_NOMEM and a message.  Out of device memory: d_mu stays NULL and the answer is
+ * LLZ_OK, for the init's own message about its small device buffers */
+int  llz_adapt_steps_create(llz_adapt_steps_t *s, const char *who, int count, float mu);
+void llz_adapt_steps_destroy(llz_adapt_steps_t *s);
+/* rows [first, first + count) (inside the state: the caller checks) to mu[], uploaded on the stream; a mu outside 0..2 is
+ * refused with "<who>: mu <mu> of <noun> <row> outside 0..2" */
+int  llz_adapt_steps_set(llz_adapt_steps_t *s, const char *who, const char *noun, int first, int count, const float *mu,
+                         void *stream);
+
+/* get_taps: the flt_len taps of each of `count` neighbouring weight rows at d_w ([P][block] packed spectra each, as
+ * llz_host_load_spectra built them) into taps = [count][flt_len], through at most 8 MiB of host staging (one row at least) */
+int  llz_adapt_get_taps(const char *who, float *taps, const float *d_w, int count, int block, int flt_len, void *stream);
+
+/* the staged call: x of xbytes, d, e and y (may be NULL) of `bytes` each.  begin refuses in-place use and device overlap of an
+ * input with an output or of e with y, then x, d, e, y are where the launches read and write (the caller's device memory, or the
+ * stages); end(rc of the launches) copies e and y back to host memory and returns the first error */
+typedef struct {
+    llz_stage_t st_x, st_d, st_e, st_y;
+    const float *x, *d;
+    float *e, *y;
+    float *user_e, *user_y;     /* host memory to copy back to, or NULL */
+    size_t bytes;
+} llz_adapt_io_t;
+int  llz_adapt_io_begin(llz_adapt_io_t *io, const char *who, const float *x, size_t xbytes, const float *d, float *e, float *y,
+                        size_t bytes, void *stream);
+int  llz_adapt_io_end(llz_adapt_io_t *io, int rc, void *stream);
+void llz_adapt_io_release(llz_adapt_io_t *io);
+
 /* ---- llz_fade.c: the crossfade state of the delay-line convolvers (llz_fir_xfade_stream_mc, llz_fir_xfade_matrix_mc) ---- */
 
 #define LLZ_FADE_MAX_BLOCKS 4096        /* fade_blocks x block <= 2^24: a sample's index within the fade is exact in float */

@@ -31,16 +31,18 @@
 //     thirteenth.  Timed at 1024 channels against 1, 2 and 8 (the adapt_ppw override): within 5 %, 4 the fastest at 25248 taps.
 //   * Blocks 64 .. 2048: at 4096 a thread owns 16 bins, K4f is at 238 VGPRs there and this kernel carries the power sums on top.
 //   * All index arithmetic over channels x slots x bins is size_t / long.
+//   * The error tail behind the inverse transform, the update kernel (k_adapt_update<LOG2B, false>) and the launch preamble are
+//     adapt_steps.hpp's, shared with fir_adapt_matrix.hip (K4i).  This file keeps the front: the ring walk with the power sums.
 #include "common.hpp"
 #include "part_fft.hpp"
 #include "stream_bins.hpp"
+#include "adapt_steps.hpp"
 
 namespace {
 
-struct adapt_geom {
+struct adapt_filter_geom {
     int P, R, cur;              // partitions, ring slots, the slot this block's spectrum goes to
     int j, last;                // the block of the call; last != 0: the call's last block (the input block goes to prev)
-    int flt_len;
     long pitch;                 // row pitch of x, d, e and y
     float delta4;               // 4 delta: the regularisation against the doubled spectra's power
 };
@@ -50,7 +52,7 @@ template <int LOG2B>
 __global__ void __launch_bounds__(stream_threads(LOG2B))
 k_adapt_filter(const float *__restrict__ x, const float *__restrict__ d, float *__restrict__ e, float *__restrict__ y,
                const float2 *__restrict__ W, const float2 *__restrict__ tw, float2 *ring, float *prev, float2 *__restrict__ gs,
-               const float *__restrict__ mus, adapt_geom G)
+               const float *__restrict__ mus, adapt_filter_geom G)
 {
     constexpr int B = 1 << LOG2B, T = stream_threads(LOG2B), M = B / T, V = M >= 2 ? 2 : 1, NG = M / V;
     constexpr int U = M >= 8 ? 1 : 8 / M;                   // partitions in flight
@@ -146,138 +148,18 @@ k_adapt_filter(const float *__restrict__ x, const float *__restrict__ d, float *
 #pragma unroll
     for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &zz[g * V]);
     part_fft_dit_inv<LOG2B, T>(lds, tw, tid);
-    // y: the last B real samples; e = d - y; (0, e) is the image of the error's transform: the first half is read by nobody
-    // behind the inverse's barrier, lf[B + t] only by the thread that writes it here
-    for (int t = tid; t < B; t += T) {
-        const float yv = lf[B + t], ev = drow[t] - yv;
-        __builtin_nontemporal_store(ev, &e[row + t]);
-        if (y) __builtin_nontemporal_store(yv, &y[row + t]);
-        lf[t] = 0.f;
-        lf[B + t] = ev;
-        if (G.last) prow[t] = xrow[t];                      // the call's last block is the next call's previous block
-    }
-    if (mu == 0.f) return;                                  // frozen: the same for the whole workgroup
-
-    part_fft_dif<LOG2B, T>(lds, tw, tid);
-    float2 gv[M];
+    // the denominators of the V positions from pos[g] on: D' + 4 delta, the halves of the packed bin each by its own
+    auto den = [&](int g, float2 *dn) {
 #pragma unroll
-    for (int m = 0; m < M; m++) {
-        const int i = pos[m / V] + m % V;
-        const float2 a = lds[i];
-        float2 ee = split_fwd(a, lds[mirror<LOG2B>(i)], spl[i]);
-        const bool packed0 = m == 0 && first;
-        if (packed0) ee = split_fwd0(a);
-        const float dsum = pw[m].x + pw[m].y;
-        const float dx = (packed0 ? pw[m].x : dsum) + G.delta4, dy = (packed0 ? pw[m].y : dsum) + G.delta4;
-        gv[m] = float2{mu * ee.x / dx, mu * ee.y / dy};
-    }
-    float2 *gc = gs + (size_t)c * B;
-#pragma unroll
-    for (int g = 0; g < NG; g++) store_bins<V>(gc + pos[g], &gv[g * V]);
-}
-
-// K4h update: workgroup (c, q) -> channel c, partitions [q ppw, min(P, (q + 1) ppw))
-template <int LOG2B>
-__global__ void __launch_bounds__(stream_threads(LOG2B))
-k_adapt_update(float2 *__restrict__ W, const float2 *__restrict__ tw, const float2 *__restrict__ ring,
-               const float2 *__restrict__ gs, const float *__restrict__ mus, adapt_geom G, int ppw)
-{
-    constexpr int B = 1 << LOG2B, T = stream_threads(LOG2B), M = B / T, V = M >= 2 ? 2 : 1, NG = M / V;
-    __shared__ __align__(16) float2 lds[B];
-    float *lf = reinterpret_cast<float *>(lds);
-    const int tid = threadIdx.x, c = blockIdx.x;
-    if (mus[c] == 0.f) return;                              // frozen: W keeps its bits
-    const float2 *spl = tw + B / 2;
-    const float2 *rc = ring + (size_t)c * (size_t)G.R * B;
-    float2 *wc = W + (size_t)c * (size_t)G.P * B;
-    const float2 *gc = gs + (size_t)c * B;
-    constexpr float scale = 1.f / (16.f * (float)B * (float)B);        // 1 / (4 N^2)
-
-    int pos[NG];
-#pragma unroll
-    for (int g = 0; g < NG; g++) pos[g] = (tid + g * T) * V;
-    const bool first = tid == 0;
-    float2 gv[M];
-#pragma unroll
-    for (int g = 0; g < NG; g++) load_bins<V>(gc + pos[g], &gv[g * V]);
-
-    const int p0 = (int)blockIdx.y * ppw, p1 = p0 + ppw < G.P ? p0 + ppw : G.P;
-    for (int p = p0; p < p1; p++) {
-        int s = G.cur - p;
-        if (s < 0) s += G.R;
-        const float2 *xs = rc + (size_t)s * B;
-        float2 *wp = wc + (size_t)p * B;
-        float2 dw[M];
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            float2 xv[V];
-            load_bins<V>(xs + pos[g], xv);
-#pragma unroll
-            for (int v = 0; v < V; v++) {
-                const int m = g * V + v;
-                dw[m] = c_mul<true>(gv[m], xv[v]);          // G conj(X)
-                if (m == 0 && first) dw[m] = float2{xv[v].x * gv[m].x, xv[v].y * gv[m].y};
-            }
+        for (int v = 0; v < V; v++) {
+            const int m = g * V + v;
+            const bool packed0 = m == 0 && first;
+            const float dsum = pw[m].x + pw[m].y;
+            dn[v] = float2{(packed0 ? pw[m].x : dsum) + G.delta4, (packed0 ? pw[m].y : dsum) + G.delta4};
         }
-        // inverse split, inverse transform
-        __syncthreads();                                    // the partition before: every mirror read is done
-#pragma unroll
-        for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &dw[g * V]);
-        __syncthreads();
-        float2 zz[M];
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            const int i = pos[m / V] + m % V;
-            zz[m] = split_inv(dw[m], lds[mirror<LOG2B>(i)], spl[i]);
-            if (m == 0 && first) zz[m] = split_inv0(dw[m]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &zz[g * V]);
-        part_fft_dit_inv<LOG2B, T>(lds, tw, tid);
-        // the constraint: samples [0, lim) kept (and scaled), the rest zero
-        const long left = (long)G.flt_len - (long)p * B;
-        const int lim = left < B ? (int)left : B;
-        for (int t = tid; t < B; t += T) {
-            lf[t] = t < lim ? lf[t] * scale : 0.f;
-            lf[B + t] = 0.f;
-        }
-        part_fft_dif<LOG2B, T>(lds, tw, tid);
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            const int i = pos[m / V] + m % V;
-            const float2 a = lds[i];
-            dw[m] = split_fwd(a, lds[mirror<LOG2B>(i)], spl[i]);
-            if (m == 0 && first) dw[m] = split_fwd0(a);
-        }
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            float2 w[V];
-            load_bins<V>(wp + pos[g], w);
-#pragma unroll
-            for (int v = 0; v < V; v++) w[v] = c_add(w[v], dw[g * V + v]);
-            store_bins<V>(wp + pos[g], w);
-        }
-    }
-}
-
-// block = 2^*log2b, 64 .. 2048
-bool adapt_log2(int block, int *log2b) { return stream_log2(block, log2b) && *log2b <= 11; }
-
-#define ADAPT_DISPATCH(log2b, call)                                                                                              \
-    switch (log2b) {                                                                                                             \
-    case 6: call(6); break;                                                                                                      \
-    case 7: call(7); break;                                                                                                      \
-    case 8: call(8); break;                                                                                                      \
-    case 9: call(9); break;                                                                                                      \
-    case 10: call(10); break;                                                                                                    \
-    default: call(11); break;                                                                                                    \
-    }
-
-bool adapt_geom_ok(bool log2ok, int block, int flt_len, int channels, int P, int R, int slot)
-{
-    return log2ok && channels >= 1 && channels <= 65535 && flt_len >= 1 && flt_len <= LLZS_FIR_PART_MAX_TAPS &&
-           P == (flt_len + block - 1) / block && R >= P && slot >= 0 && slot < R;
+    };
+    // y, e = d - y, the call's last block handed over to prev, and where the channel adapts G = mu E / den
+    adapt_error_tail<LOG2B>(lds, tw, tid, pos, drow, e, y, row, G.last ? prow : nullptr, xrow, mu, gs + (size_t)c * B, den);
 }
 
 } // namespace
@@ -291,13 +173,14 @@ extern "C" int llzs_fir_adapt_filter_f32(int block, int flt_len, const float *w,
 {
     int log2b;
     const bool ok = adapt_log2(block, &log2b);
-    if (!adapt_geom_ok(ok, block, flt_len, channels, P, R, slot) || !(w && tw && ring && prev && g && mu && x && d && e) ||
-        nblk < 1 || j < 0 || j >= nblk || pitch < (long)nblk * block || !(delta > 0.f)) {
+    if (!adapt_geom_ok(ok, block, flt_len, P, R, slot) || channels < 1 || channels > 65535 ||
+        !(w && tw && ring && prev && g && mu && x && d && e) || nblk < 1 || j < 0 || j >= nblk || pitch < (long)nblk * block ||
+        !(delta > 0.f)) {
         llzs_set_error("fir_adapt_filter_f32: bad arguments (block=%d flt_len=%d channels=%d nblk=%d j=%d P=%d R=%d slot=%d)", block,
                        flt_len, channels, nblk, j, P, R, slot);
         return LLZ_ERR_ARG;
     }
-    const adapt_geom G = {P, R, slot, j, j == nblk - 1, flt_len, pitch, 4.f * delta};
+    const adapt_filter_geom G = {P, R, slot, j, j == nblk - 1, pitch, 4.f * delta};
     const float2 *W = reinterpret_cast<const float2 *>(w), *TW = reinterpret_cast<const float2 *>(tw);
     float2 *rg = reinterpret_cast<float2 *>(ring), *gs = reinterpret_cast<float2 *>(g);
     hipStream_t st = as_stream(stream);
@@ -317,20 +200,19 @@ extern "C" int llzs_fir_adapt_update_f32(int block, int flt_len, float *w, const
 {
     int log2b;
     const bool ok = adapt_log2(block, &log2b);
-    if (!adapt_geom_ok(ok, block, flt_len, channels, P, R, slot) || !(w && tw && ring && g && mu)) {
+    if (!adapt_geom_ok(ok, block, flt_len, P, R, slot) || channels < 1 || channels > 65535 || !(w && tw && ring && g && mu)) {
         llzs_set_error("fir_adapt_update_f32: bad arguments (block=%d flt_len=%d channels=%d P=%d R=%d slot=%d)", block, flt_len,
                        channels, P, R, slot);
         return LLZ_ERR_ARG;
     }
-    const adapt_geom G = {P, R, slot, 0, 0, flt_len, 0, 0.f};
-    const int tuned = llzs_tune(LLZS_TUNE_ADAPT_PPW);
-    const int ppw = tuned >= 1 ? (tuned < 64 ? tuned : 64) : (long)channels * P >= 4096 ? 4 : 1;
-    const dim3 grid((unsigned)channels, (unsigned)((P + ppw - 1) / ppw));
+    const adapt_update_geom G = {1, P, R, slot, flt_len};
+    const int ppw = adapt_ppw((long)channels * P), nq = (P + ppw - 1) / ppw;
+    const dim3 grid((unsigned)channels, (unsigned)nq);
     float2 *W = reinterpret_cast<float2 *>(w);
     const float2 *TW = reinterpret_cast<const float2 *>(tw), *rg = reinterpret_cast<const float2 *>(ring);
     const float2 *gs = reinterpret_cast<const float2 *>(g);
     hipStream_t st = as_stream(stream);
-#define UPDATE(L) hipLaunchKernelGGL((k_adapt_update<L>), grid, dim3(stream_threads(L)), 0, st, W, TW, rg, gs, mu, G, ppw)
+#define UPDATE(L) hipLaunchKernelGGL((k_adapt_update<L, false>), grid, dim3(stream_threads(L)), 0, st, W, TW, rg, gs, mu, G, ppw, nq)
     ADAPT_DISPATCH(log2b, UPDATE)
 #undef UPDATE
     LLZ_LAUNCH_CHECK("k_adapt_update");

@@ -8,11 +8,11 @@
 //           does not depend on W, so all k blocks go in one launch;
 // and per block j, ordered by the stream:
 //   llzs_fir_matrix_mac_f32 (K4g, unchanged) with one block and a connection table of ones: the G partial spectra of Y_o;
-//   error:  grid (output): the partials added g ascending, the inverse split and transform (K4g's inverse to the letter), y, e =
-//           d - y, and where mu_o != 0 E = the spectrum of (0_B, e), G_o = mu_o E / den[j] into an [outputs][B] scratch (K4h's
-//           filter tail to the letter);
-//   update: grid ((input, group of partitions), output): W_{o,i,p} += the constrained conj(X_{i,j-p}) G_o, K4h's update loop to
-//           the letter on input i's ring and path (o, i)'s weights.
+//   error:  grid (output): the partials added g ascending, the inverse split and transform (K4g's inverse to the letter), then
+//           the tail K4h's filter runs (adapt_steps.hpp, adapt_error_tail): y, e = d - y, and where mu_o != 0 E = the spectrum
+//           of (0_B, e), G_o = mu_o E / den[j] into an [outputs][B] scratch;
+//   update: grid ((input, group of partitions), output): W_{o,i,p} += the constrained conj(X_{i,j-p}) G_o: the kernel K4h
+//           launches (adapt_steps.hpp, k_adapt_update) on input i's ring and path (o, i)'s weights.
 // With one input the chains are K4h's: e, y and W have llz_adapt_mc's bits.  Frozen (every mu zero) y has llz_fir_matrix_mc's.
 //
 // Choices, with their reasons:
@@ -31,23 +31,27 @@
 #include "common.hpp"
 #include "part_fft.hpp"
 #include "stream_bins.hpp"
+#include "adapt_steps.hpp"
 
 namespace {
 
-struct adaptx_geom {
-    int inputs, outputs, P, R;
-    int cur;                    // the ring slot of the block (power: of block 0 of the launch)
-    int j;                      // the block of the call
-    int groups;                 // input groups of the partial spectra
-    int flt_len;
-    long pitch;                 // row pitch of d, e and y
+struct adaptx_power_geom {
+    int inputs, P, R;
+    int cur;                    // the ring slot of block 0 of the launch
     float delta4;               // 4 delta: the regularisation against the doubled spectra's power
+};
+
+struct adaptx_error_geom {
+    int outputs;
+    int groups;                 // input groups of the partial spectra
+    int j;                      // the block of the call
+    long pitch;                 // row pitch of d, e and y
 };
 
 // power: workgroup (j, tile) -> block j of the call, bins [tile T, (tile + 1) T).  den: [nblk][B] (dx, dy)
 template <int LOG2B>
 __global__ void __launch_bounds__(stream_threads(LOG2B))
-k_adaptx_power(const float2 *__restrict__ ring, float2 *__restrict__ den, adaptx_geom G)
+k_adaptx_power(const float2 *__restrict__ ring, float2 *__restrict__ den, adaptx_power_geom G)
 {
     constexpr int B = 1 << LOG2B, T = stream_threads(LOG2B), U = 16;     // slots in flight
     const int pos = (int)blockIdx.y * T + (int)threadIdx.x, j = blockIdx.x;
@@ -98,17 +102,15 @@ template <int LOG2B>
 __global__ void __launch_bounds__(stream_threads(LOG2B))
 k_adaptx_error(const float2 *__restrict__ Y, const float2 *__restrict__ tw, const float *__restrict__ d, float *__restrict__ e,
                float *__restrict__ y, const float2 *__restrict__ den, float2 *__restrict__ gs, const float *__restrict__ mus,
-               adaptx_geom G)
+               adaptx_error_geom G)
 {
     constexpr int B = 1 << LOG2B, T = stream_threads(LOG2B), M = B / T, V = M >= 2 ? 2 : 1, NG = M / V;
     __shared__ __align__(16) float2 lds[B];
-    float *lf = reinterpret_cast<float *>(lds);
     const int tid = threadIdx.x, o = blockIdx.x;
     const float2 *spl = tw + B / 2;
     const size_t gstride = (size_t)G.outputs * B;
     const float2 *y0 = Y + (size_t)o * B;
     const size_t row = (size_t)o * (size_t)G.pitch + (size_t)G.j * B;
-    const float *drow = d + row;
     const float mu = mus[o];
     int pos[NG];
 #pragma unroll
@@ -139,140 +141,13 @@ k_adaptx_error(const float2 *__restrict__ Y, const float2 *__restrict__ tw, cons
 #pragma unroll
     for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &zz[g * V]);
     part_fft_dit_inv<LOG2B, T>(lds, tw, tid);
-    // y: the last B real samples; e = d - y; (0, e) is the image of the error's transform
-    for (int t = tid; t < B; t += T) {
-        const float yv = lf[B + t], ev = drow[t] - yv;
-        __builtin_nontemporal_store(ev, &e[row + t]);
-        if (y) __builtin_nontemporal_store(yv, &y[row + t]);
-        lf[t] = 0.f;
-        lf[B + t] = ev;
-    }
-    if (mu == 0.f) return;                                  // frozen: the same for the whole workgroup
-
-    part_fft_dif<LOG2B, T>(lds, tw, tid);
-    float2 gv[M];
-#pragma unroll
-    for (int g = 0; g < NG; g++) {
-        float2 dn[V];
-        load_bins<V>(den + pos[g], dn);
-#pragma unroll
-        for (int v = 0; v < V; v++) {
-            const int m = g * V + v, i = pos[g] + v;
-            const float2 a = lds[i];
-            float2 ee = split_fwd(a, lds[mirror<LOG2B>(i)], spl[i]);
-            if (m == 0 && first) ee = split_fwd0(a);
-            gv[m] = float2{mu * ee.x / dn[v].x, mu * ee.y / dn[v].y};
-        }
-    }
-    float2 *gc = gs + (size_t)o * B;
-#pragma unroll
-    for (int g = 0; g < NG; g++) store_bins<V>(gc + pos[g], &gv[g * V]);
+    // y, e = d - y, and where the output adapts G = mu E / den: the denominators of a position come from the block's den row
+    adapt_error_tail<LOG2B>(lds, tw, tid, pos, d + row, e, y, row, nullptr, nullptr, mu, gs + (size_t)o * B,
+                            [&](int g, float2 *dn) { load_bins<V>(den + pos[g], dn); });
 }
 
-// update: workgroup (i nq + q, o) -> path (o, i), partitions [q ppw, min(P, (q + 1) ppw)).  W: [outputs][inputs][P][B]
-template <int LOG2B>
-__global__ void __launch_bounds__(stream_threads(LOG2B))
-k_adaptx_update(float2 *__restrict__ W, const float2 *__restrict__ tw, const float2 *__restrict__ ring,
-                const float2 *__restrict__ gs, const float *__restrict__ mus, adaptx_geom G, int ppw, int nq)
-{
-    constexpr int B = 1 << LOG2B, T = stream_threads(LOG2B), M = B / T, V = M >= 2 ? 2 : 1, NG = M / V;
-    __shared__ __align__(16) float2 lds[B];
-    float *lf = reinterpret_cast<float *>(lds);
-    const int tid = threadIdx.x, o = blockIdx.y;
-    const int i = (int)(blockIdx.x / (unsigned)nq), q = (int)(blockIdx.x % (unsigned)nq);
-    if (mus[o] == 0.f) return;                              // frozen: W keeps its bits
-    const float2 *spl = tw + B / 2;
-    const float2 *rc = ring + (size_t)i * (size_t)G.R * B;
-    float2 *wc = W + ((size_t)o * (size_t)G.inputs + (size_t)i) * (size_t)G.P * B;
-    const float2 *gc = gs + (size_t)o * B;
-    constexpr float scale = 1.f / (16.f * (float)B * (float)B);        // 1 / (4 N^2)
-
-    int pos[NG];
-#pragma unroll
-    for (int g = 0; g < NG; g++) pos[g] = (tid + g * T) * V;
-    const bool first = tid == 0;
-    float2 gv[M];
-#pragma unroll
-    for (int g = 0; g < NG; g++) load_bins<V>(gc + pos[g], &gv[g * V]);
-
-    const int p0 = q * ppw, p1 = p0 + ppw < G.P ? p0 + ppw : G.P;
-    for (int p = p0; p < p1; p++) {
-        int s = G.cur - p;
-        if (s < 0) s += G.R;
-        const float2 *xs = rc + (size_t)s * B;
-        float2 *wp = wc + (size_t)p * B;
-        float2 dw[M];
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            float2 xv[V];
-            load_bins<V>(xs + pos[g], xv);
-#pragma unroll
-            for (int v = 0; v < V; v++) {
-                const int m = g * V + v;
-                dw[m] = c_mul<true>(gv[m], xv[v]);          // G conj(X)
-                if (m == 0 && first) dw[m] = float2{xv[v].x * gv[m].x, xv[v].y * gv[m].y};
-            }
-        }
-        // inverse split, inverse transform
-        __syncthreads();                                    // the partition before: every mirror read is done
-#pragma unroll
-        for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &dw[g * V]);
-        __syncthreads();
-        float2 zz[M];
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            const int k = pos[m / V] + m % V;
-            zz[m] = split_inv(dw[m], lds[mirror<LOG2B>(k)], spl[k]);
-            if (m == 0 && first) zz[m] = split_inv0(dw[m]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < NG; g++) store_bins<V>(lds + pos[g], &zz[g * V]);
-        part_fft_dit_inv<LOG2B, T>(lds, tw, tid);
-        // the constraint: samples [0, lim) kept (and scaled), the rest zero
-        const long left = (long)G.flt_len - (long)p * B;
-        const int lim = left < B ? (int)left : B;
-        for (int t = tid; t < B; t += T) {
-            lf[t] = t < lim ? lf[t] * scale : 0.f;
-            lf[B + t] = 0.f;
-        }
-        part_fft_dif<LOG2B, T>(lds, tw, tid);
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            const int k = pos[m / V] + m % V;
-            const float2 a = lds[k];
-            dw[m] = split_fwd(a, lds[mirror<LOG2B>(k)], spl[k]);
-            if (m == 0 && first) dw[m] = split_fwd0(a);
-        }
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            float2 w[V];
-            load_bins<V>(wp + pos[g], w);
-#pragma unroll
-            for (int v = 0; v < V; v++) w[v] = c_add(w[v], dw[g * V + v]);
-            store_bins<V>(wp + pos[g], w);
-        }
-    }
-}
-
-// block = 2^*log2b, 64 .. 2048
-bool adaptx_log2(int block, int *log2b) { return stream_log2(block, log2b) && *log2b <= 11; }
-
-#define ADAPTX_DISPATCH(log2b, call)                                                                                             \
-    switch (log2b) {                                                                                                             \
-    case 6: call(6); break;                                                                                                      \
-    case 7: call(7); break;                                                                                                      \
-    case 8: call(8); break;                                                                                                      \
-    case 9: call(9); break;                                                                                                      \
-    case 10: call(10); break;                                                                                                    \
-    default: call(11); break;                                                                                                    \
-    }
-
-bool adaptx_geom_ok(bool log2ok, int block, int flt_len, int inputs, int outputs, int P, int R, int slot)
-{
-    return log2ok && inputs >= 1 && inputs <= 4096 && outputs >= 1 && outputs <= 4096 && flt_len >= 1 &&
-           flt_len <= LLZS_FIR_PART_MAX_TAPS && P == (flt_len + block - 1) / block && R >= P && slot >= 0 && slot < R;
-}
+// inputs and outputs: 1 .. 4096 each, so that no legal shape meets a grid limit
+bool adaptx_ports_ok(int ports) { return ports >= 1 && ports <= 4096; }
 
 } // namespace
 
@@ -282,21 +157,20 @@ extern "C" int llzs_fir_adapt_matrix_power_f32(int block, int flt_len, const flo
                                                int nblk, int P, int R, int slot, void *stream)
 {
     int log2b;
-    const bool ok = adaptx_log2(block, &log2b);
-    if (!adaptx_geom_ok(ok, block, flt_len, inputs, 1, P, R, slot) || !ring || !den || nblk < 1 || !(delta > 0.f)) {
+    const bool ok = adapt_log2(block, &log2b);
+    if (!adapt_geom_ok(ok, block, flt_len, P, R, slot) || !adaptx_ports_ok(inputs) || !ring || !den || nblk < 1 || !(delta > 0.f)) {
         llzs_set_error("fir_adapt_matrix_power_f32: bad arguments (block=%d flt_len=%d inputs=%d nblk=%d P=%d R=%d slot=%d)", block,
                        flt_len, inputs, nblk, P, R, slot);
         return LLZ_ERR_ARG;
     }
-    adaptx_geom G = {};
-    G.inputs = inputs; G.P = P; G.R = R; G.cur = slot; G.flt_len = flt_len; G.delta4 = 4.f * delta;
+    const adaptx_power_geom G = {inputs, P, R, slot, 4.f * delta};
     const float2 *rg = reinterpret_cast<const float2 *>(ring);
     float2 *dn = reinterpret_cast<float2 *>(den);
     hipStream_t st = as_stream(stream);
 #define POWER(L)                                                                                                                 \
     hipLaunchKernelGGL((k_adaptx_power<L>), dim3((unsigned)nblk, (unsigned)((1 << L) / stream_threads(L))),                      \
                        dim3(stream_threads(L)), 0, st, rg, dn, G)
-    ADAPTX_DISPATCH(log2b, POWER)
+    ADAPT_DISPATCH(log2b, POWER)
 #undef POWER
     LLZ_LAUNCH_CHECK("k_adaptx_power");
     return LLZ_OK;
@@ -310,22 +184,21 @@ extern "C" int llzs_fir_adapt_matrix_error_f32(int block, const float *ypart, co
                                                int j, long pitch, void *stream)
 {
     int log2b;
-    const bool ok = adaptx_log2(block, &log2b);
-    if (!ok || outputs < 1 || outputs > 4096 || groups < 1 || !(ypart && tw && den && g && mu && d && e) || j < 0 ||
+    const bool ok = adapt_log2(block, &log2b);
+    if (!ok || !adaptx_ports_ok(outputs) || groups < 1 || !(ypart && tw && den && g && mu && d && e) || j < 0 ||
         pitch < ((long)j + 1) * block) {
         llzs_set_error("fir_adapt_matrix_error_f32: bad arguments (block=%d outputs=%d groups=%d j=%d pitch=%ld)", block, outputs,
                        groups, j, pitch);
         return LLZ_ERR_ARG;
     }
-    adaptx_geom G = {};
-    G.outputs = outputs; G.groups = groups; G.j = j; G.pitch = pitch;
+    const adaptx_error_geom G = {outputs, groups, j, pitch};
     const float2 *Y = reinterpret_cast<const float2 *>(ypart), *TW = reinterpret_cast<const float2 *>(tw);
     const float2 *dn = reinterpret_cast<const float2 *>(den);
     float2 *gs = reinterpret_cast<float2 *>(g);
     hipStream_t st = as_stream(stream);
 #define ERRK(L)                                                                                                                 \
     hipLaunchKernelGGL((k_adaptx_error<L>), dim3((unsigned)outputs), dim3(stream_threads(L)), 0, st, Y, TW, d, e, y, dn, gs, mu, G)
-    ADAPTX_DISPATCH(log2b, ERRK)
+    ADAPT_DISPATCH(log2b, ERRK)
 #undef ERRK
     LLZ_LAUNCH_CHECK("k_adaptx_error");
     return LLZ_OK;
@@ -338,24 +211,22 @@ extern "C" int llzs_fir_adapt_matrix_update_f32(int block, int flt_len, float *w
                                                 void *stream)
 {
     int log2b;
-    const bool ok = adaptx_log2(block, &log2b);
-    if (!adaptx_geom_ok(ok, block, flt_len, inputs, outputs, P, R, slot) || !(w && tw && ring && g && mu)) {
+    const bool ok = adapt_log2(block, &log2b);
+    if (!adapt_geom_ok(ok, block, flt_len, P, R, slot) || !adaptx_ports_ok(inputs) || !adaptx_ports_ok(outputs) ||
+        !(w && tw && ring && g && mu)) {
         llzs_set_error("fir_adapt_matrix_update_f32: bad arguments (block=%d flt_len=%d inputs=%d outputs=%d P=%d R=%d slot=%d)",
                        block, flt_len, inputs, outputs, P, R, slot);
         return LLZ_ERR_ARG;
     }
-    adaptx_geom G = {};
-    G.inputs = inputs; G.outputs = outputs; G.P = P; G.R = R; G.cur = slot; G.flt_len = flt_len;
-    const int tuned = llzs_tune(LLZS_TUNE_ADAPT_PPW);
-    const int ppw = tuned >= 1 ? (tuned < 64 ? tuned : 64) : (long)outputs * inputs * P >= 4096 ? 4 : 1;
-    const int nq = (P + ppw - 1) / ppw;
+    const adapt_update_geom G = {inputs, P, R, slot, flt_len};
+    const int ppw = adapt_ppw((long)outputs * inputs * P), nq = (P + ppw - 1) / ppw;
     const dim3 grid((unsigned)inputs * (unsigned)nq, (unsigned)outputs);
     float2 *W = reinterpret_cast<float2 *>(w);
     const float2 *TW = reinterpret_cast<const float2 *>(tw), *rg = reinterpret_cast<const float2 *>(ring);
     const float2 *gs = reinterpret_cast<const float2 *>(g);
     hipStream_t st = as_stream(stream);
-#define UPDATE(L) hipLaunchKernelGGL((k_adaptx_update<L>), grid, dim3(stream_threads(L)), 0, st, W, TW, rg, gs, mu, G, ppw, nq)
-    ADAPTX_DISPATCH(log2b, UPDATE)
+#define UPDATE(L) hipLaunchKernelGGL((k_adapt_update<L, true>), grid, dim3(stream_threads(L)), 0, st, W, TW, rg, gs, mu, G, ppw, nq)
+    ADAPT_DISPATCH(log2b, UPDATE)
 #undef UPDATE
     LLZ_LAUNCH_CHECK("k_adaptx_update");
     return LLZ_OK;

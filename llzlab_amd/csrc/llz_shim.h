@@ -226,8 +226,8 @@ int llzs_fir_matrix_mac_fade_f32(int block, const float *hspec, const float *hsp
 int llzs_fir_matrix_inv_fade_f32(int block, const float *ypart, const float *ypart_new, const unsigned char *ofade,
                                  const float *tw, float *out, int outputs, int nblk, int j0, int groups, long n_out,
                                  long out_pitch, int fade_done, int fade_blocks, void *stream);
-/* the partitioned frequency-domain NLMS adaptive filter (fir_adapt.hip; include/llz_adapt.h), block = 64 .. 2048: two launches
- * per block, ordered by the stream.  w = [channels][P][block] complex, the weights' packed spectra laid out and scaled as
+/* the partitioned frequency-domain NLMS adaptive filter (fir_adapt.hip, the error tail and the update kernel from
+ * adapt_steps.hpp; include/llz_adapt.h), block = 64 .. 2048: two launches per block, ordered by the stream.  w = [channels][P][block] complex, the weights' packed spectra laid out and scaled as
  * llz_host_stream_spectra builds them; tw, ring ([channels][R][block] complex), prev as llzs_fir_stream_f32's; g = [channels]
  * [block] complex scratch; mu = [channels] step sizes on the device, 0 = the channel is frozen; x, d, e, y = [channels][pitch],
  * y may be NULL.
@@ -241,8 +241,8 @@ int llzs_fir_adapt_filter_f32(int block, int flt_len, const float *w, const floa
                               int nblk, int j, long pitch, int P, int R, int slot, void *stream);
 int llzs_fir_adapt_update_f32(int block, int flt_len, float *w, const float *tw, const float *ring, const float *g,
                               const float *mu, int channels, int P, int R, int slot, void *stream);
-/* the multi-reference adaptive filter (fir_adapt_matrix.hip; include/llz_adapt_matrix.h), block = 64 .. 2048, on the matrix
- * convolver's rings: behind llzs_fir_matrix_fwd_f32 of a call's nblk blocks one power launch, then per block
+/* the multi-reference adaptive filter (fir_adapt_matrix.hip, the error tail and the update kernel from adapt_steps.hpp, the
+ * same as the filter's above; include/llz_adapt_matrix.h), block = 64 .. 2048, on the matrix convolver's rings: behind llzs_fir_matrix_fwd_f32 of a call's nblk blocks one power launch, then per block
  * llzs_fir_matrix_mac_f32 (nblk = 1, head = the block's slot, conn all ones), error and update, ordered by the stream.  w =
  * [outputs][inputs][P][block] complex laid out and scaled as hspec; den = [nblk][block] pairs of floats; g = [outputs][block]
  * complex scratch; mu = [outputs] step sizes on the device, 0 = the output is frozen; d, e, y = [outputs][pitch], y may be NULL.

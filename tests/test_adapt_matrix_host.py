@@ -73,6 +73,28 @@ def test_both_handles_take_their_groups_from_one_function():
     assert "llz_host_matrix_groups" in open(os.path.join(host, "llz_host.h")).read()
 
 
+def test_both_adaptive_handles_take_their_shared_steps_from_the_core():
+    """the init's refusals, the step sizes, get_taps and the staged call are llz_adapt_core.c's: both handles call them, and
+    neither keeps a copy of the messages that went there"""
+    host = os.path.join(CSRC, "host")
+    header = open(os.path.join(host, "llz_host.h")).read()
+    core = open(os.path.join(host, "llz_adapt_core.c")).read()
+    calls = ("llz_adapt_refuse", "llz_adapt_steps_create", "llz_adapt_steps_destroy", "llz_adapt_steps_set", "llz_adapt_get_taps",
+             "llz_adapt_io_begin", "llz_adapt_io_end", "llz_adapt_io_release")
+    moved = ("outside 0..2", "is not built", "is not a power of two", "is not k x block", "is not a finite value",
+             "in-place filtering is not supported", "of step sizes", "of weight spectra")
+    for name in calls:
+        assert name in header and len(re.findall(r"\b%s\s*\(" % name, core)) == 1, name
+    for text in moved:
+        assert text in core, text
+    for fn in ("llz_adapt_host.c", "llz_adapt_matrix_host.c"):
+        text = open(os.path.join(host, fn)).read()
+        for name in calls:
+            assert re.search(r"\b%s\s*\(" % name, text), (fn, name)
+        for other in moved + ("llz_refuse_device_overlap", "llz_stage_in", "llz_stage_out", "llz_host_stream_taps"):
+            assert other not in text, (fn, other)
+
+
 def refused(L, what, *args):
     L.llz_hip_tune(b"no_such_override", 0)                      # leaves a message that is not the init's
     before = capi.last_error()
