@@ -258,6 +258,15 @@ int llzs_fir_adapt_matrix_error_f32(int block, const float *ypart, const float *
                                     const float *d, float *e, float *y, int outputs, int groups, int j, long pitch, void *stream);
 int llzs_fir_adapt_matrix_update_f32(int block, int flt_len, float *w, const float *tw, const float *ring, const float *g,
                                      const float *mu, int inputs, int outputs, int P, int R, int slot, void *stream);
+/* the normalised LMS filter per band (adapt_bands.hip; include/llz_adapt_bands.h), float32: `taps` = K complex taps, 1..64, for
+ * every (channel, bin), one launch for a call of `frames` >= 1 frames.  x, d, e, y = [channels][frames][bins], re and im apart,
+ * y re and im both NULL or both set; w = [channels][K][bins] weights by age, h = [channels][max(K - 1, 1)][bins] history, row q
+ * holding x[-1 - q] of the call; both are read, walked through the frames and written back.  mu = [channels] step sizes on the
+ * device, 0 = the channel is frozen.  plan: out = {tap ceiling of the instance, threads per workgroup, workgroups, launches}. */
+int llzs_bands_nlms_f32(const float *xre, const float *xim, const float *dre, const float *dim, float *ere, float *eim,
+                        float *yre, float *yim, float *wre, float *wim, float *hre, float *him, const float *mu, float delta,
+                        int channels, int bins, int taps, int frames, void *stream);
+int llzs_bands_nlms_plan(int channels, int bins, int taps, int *out);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

@@ -535,6 +535,88 @@ class AdaptMatrixMC:
     __del__ = close
 
 
+class AdaptBandsMC:
+    """band signals [channels, frames, bins] float32, re and im apart (StftMC's and PfbMC's layout): llz_adapt_bands_mc_*, a
+    normalised LMS filter of `taps` complex taps for every (channel, bin), updated frame by frame (include/llz_adapt_bands.h) --
+    the step between a bank's analysis of x and d and its synthesis of e in a subband echo canceller.  The weights start at zero;
+    mu is every channel's step size (0 = frozen), delta the regularisation of the power (None: 1e-3 x taps)."""
+
+    def __init__(self, channels, bins, taps, mu=0.5, delta=None, stream=None):
+        self._L = capi.lib()
+        delta = 1e-3 * taps if delta is None else delta
+        self.handle = check_handle(self._L.llz_adapt_bands_mc_init(channels, bins, taps, mu, delta), "llz_adapt_bands_mc_init")
+        self.channels, self.bins, self.taps = channels, bins, taps
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_adapt_bands_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_adapt_bands_mc_set_stream")
+
+    def plan(self):
+        """(tap ceiling of the kernel instance, threads per workgroup, workgroups, launches per call)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_adapt_bands_mc_plan(self.handle, out), "llz_adapt_bands_mc_plan")
+        return tuple(out)
+
+    def process(self, x_re, x_im, d_re, d_im, e_re, e_im, y_re=None, y_im=None):
+        """x (reference), d (desired), e (error, written), y (filter output, written when both are given): [channels, frames,
+        bins] float32 each (torch device tensors or numpy), any number of frames, none included.  Returns (e_re, e_im)."""
+        if (y_re is None) != (y_im is None):
+            raise LlzError("AdaptBandsMC.process: y_re and y_im must both be given or both be None")
+        frames = (x_re.numel() if hasattr(x_re, "numel") else x_re.size) // (self.channels * self.bins)
+        count = self.channels * frames * self.bins
+        bufs = [("x_re", x_re), ("x_im", x_im), ("d_re", d_re), ("d_im", d_im), ("e_re", e_re), ("e_im", e_im)]
+        bufs += [("y_re", y_re), ("y_im", y_im)] if y_re is not None else []
+        ptrs = [_typed(b, "float32", count, "AdaptBandsMC.process " + name) for name, b in bufs]
+        ptrs += [None] * (8 - len(ptrs))
+        check(self._L.llz_adapt_bands_mc(self.handle, *ptrs, frames), "llz_adapt_bands_mc")
+        return e_re, e_im
+
+    def set_step(self, first, mu):
+        """step sizes of channels first .. first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
+        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float32)
+        check(self._L.llz_adapt_bands_mc_set_step(self.handle, first, mu.shape[0], mu.ctypes.data), "llz_adapt_bands_mc_set_step")
+
+    def set_taps(self, first, w):
+        """replace the weights of channels first .. first + count - 1; w: complex [count, taps, bins] (row q the taps of age q),
+        or [taps, bins] for one channel; the history is kept"""
+        w = np.asarray(w)
+        w = w[None] if w.ndim == 2 else w
+        if w.ndim != 3 or w.shape[1:] != (self.taps, self.bins):
+            raise LlzError(f"AdaptBandsMC.set_taps: w must be [count, taps = {self.taps}, bins = {self.bins}], got {w.shape}")
+        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
+        check(self._L.llz_adapt_bands_mc_set_taps(self.handle, first, w.shape[0], wre.ctypes.data, wim.ctypes.data),
+              "llz_adapt_bands_mc_set_taps")
+
+    def get_taps(self, first=0, count=None):
+        """the weights of channels first .. first + count - 1 (default: all from first) as complex64 [count, taps, bins]: the
+        handle's own float32 values"""
+        count = self.channels - first if count is None else count
+        wre = np.empty((max(count, 0), self.taps, self.bins), dtype=np.float32)
+        wim = np.empty_like(wre)
+        check(self._L.llz_adapt_bands_mc_get_taps(self.handle, first, count, wre.ctypes.data, wim.ctypes.data),
+              "llz_adapt_bands_mc_get_taps")
+        w = np.empty(wre.shape, dtype=np.complex64)
+        w.real, w.imag = wre, wim
+        return w
+
+    def reset(self, clear_taps=False):
+        check(self._L.llz_adapt_bands_mc_reset(self.handle, 1 if clear_taps else 0), "llz_adapt_bands_mc_reset")
+
+    def frames(self):
+        """frames taken since init or reset"""
+        n = C.c_longlong()
+        check(self._L.llz_adapt_bands_mc_frames(self.handle, C.byref(n)), "llz_adapt_bands_mc_frames")
+        return n.value
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_adapt_bands_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
