@@ -267,6 +267,17 @@ int llzs_bands_nlms_f32(const float *xre, const float *xim, const float *dre, co
                         float *yre, float *yim, float *wre, float *wim, float *hre, float *him, const float *mu, float delta,
                         int channels, int bins, int taps, int frames, void *stream);
 int llzs_bands_nlms_plan(int channels, int bins, int taps, int *out);
+/* its multi-reference form (adapt_bands_matrix.hip; include/llz_adapt_bands_matrix.h): `inputs` = I references, 1..8, of `taps`
+ * = K complex taps each, I K <= 64, for every (output, bin), one launch for a call of `frames` >= 1 frames.  x = [inputs][frames]
+ * [bins]; d, e, y = [outputs][frames][bins]; w = [outputs][inputs][K][bins] weights by age, read, walked and written back.  The
+ * history [inputs][max(K - 1, 1)][bins], row q holding x_i[-1 - q] of the call, is shared by the outputs: hin is read, hout --
+ * ANOTHER buffer -- takes the history behind the call's last frame, each element from one lane.  mu = [outputs] step sizes on the
+ * device.  plan: out = {inputs of the instance, entry ceiling of the instance, threads per workgroup, workgroups, launches}. */
+int llzs_matrix_bands_nlms_f32(const float *xre, const float *xim, const float *dre, const float *dim, float *ere, float *eim,
+                               float *yre, float *yim, float *wre, float *wim, const float *hin_re, const float *hin_im,
+                               float *hout_re, float *hout_im, const float *mu, float delta, int inputs, int outputs, int bins,
+                               int taps, int frames, void *stream);
+int llzs_matrix_bands_nlms_plan(int inputs, int outputs, int bins, int taps, int *out);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

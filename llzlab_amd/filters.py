@@ -617,6 +617,94 @@ class AdaptBandsMC:
     __del__ = close
 
 
+class AdaptBandsMatrixMC:
+    """band signals, float32, re and im apart (StftMC's and PfbMC's layout): llz_adapt_bands_matrix_mc_*, a normalised LMS filter
+    of `inputs` references x `taps` complex taps for every (output, bin), normalised by the joint power of the references and
+    updated frame by frame (include/llz_adapt_bands_matrix.h) -- AdaptBandsMC for a microphone that hears several loudspeakers;
+    frozen (mu = 0) with set_taps, a filter-and-sum beamformer with a weight per bin.  inputs 1..8, inputs x taps <= 64.  The
+    weights start at zero; mu is every output's step size (0 = frozen), delta the regularisation of the power (None: 1e-3 x
+    inputs x taps)."""
+
+    def __init__(self, inputs, outputs, bins, taps, mu=0.5, delta=None, stream=None):
+        self._L = capi.lib()
+        delta = 1e-3 * inputs * taps if delta is None else delta
+        self.handle = check_handle(self._L.llz_adapt_bands_matrix_mc_init(inputs, outputs, bins, taps, mu, delta),
+                                   "llz_adapt_bands_matrix_mc_init")
+        self.inputs, self.outputs, self.bins, self.taps = inputs, outputs, bins, taps
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_adapt_bands_matrix_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_adapt_bands_matrix_mc_set_stream")
+
+    def plan(self):
+        """(inputs of the kernel instance, its entry ceiling, threads per workgroup, workgroups, launches per call)"""
+        out = (C.c_int * 5)()
+        check(self._L.llz_adapt_bands_matrix_mc_plan(self.handle, out), "llz_adapt_bands_matrix_mc_plan")
+        return tuple(out)
+
+    def process(self, x, d, e, y=None):
+        """x (references), d (desired), e (error, written), y (filter output, written when given): each a pair (re, im) of
+        float32 buffers (torch device tensors or numpy, in any mix), x [inputs, frames, bins], the others [outputs, frames,
+        bins]; any number of frames, none included.  Returns e."""
+        pairs = [("x", x, self.inputs), ("d", d, self.outputs), ("e", e, self.outputs)] + ([("y", y, self.outputs)] if y is not None else [])
+        for name, p, _ in pairs:
+            if not isinstance(p, (tuple, list)) or len(p) != 2:
+                raise LlzError(f"AdaptBandsMatrixMC.process: {name} must be a pair (re, im)")
+        frames = (x[0].numel() if hasattr(x[0], "numel") else x[0].size) // (self.inputs * self.bins)
+        ptrs = [_typed(b, "float32", rows * frames * self.bins, f"AdaptBandsMatrixMC.process {name}_{part}")
+                for name, p, rows in pairs for part, b in zip(("re", "im"), p)]
+        ptrs += [None] * (8 - len(ptrs))
+        check(self._L.llz_adapt_bands_matrix_mc(self.handle, *ptrs, frames), "llz_adapt_bands_matrix_mc")
+        return e
+
+    def set_step(self, out_first, mu):
+        """step sizes of outputs out_first .. out_first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
+        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float32)
+        check(self._L.llz_adapt_bands_matrix_mc_set_step(self.handle, out_first, mu.shape[0], mu.ctypes.data),
+              "llz_adapt_bands_matrix_mc_set_step")
+
+    def set_taps(self, out_first, w, in_first=0):
+        """replace the weights of the paths (out_first .., in_first ..); w: complex [out_count, in_count, taps, bins] (row q the
+        taps of age q); the history is kept"""
+        w = np.asarray(w)
+        if w.ndim != 4 or w.shape[2:] != (self.taps, self.bins):
+            raise LlzError(f"AdaptBandsMatrixMC.set_taps: w must be [out_count, in_count, taps = {self.taps}, bins = {self.bins}], "
+                           f"got {w.shape}")
+        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
+        check(self._L.llz_adapt_bands_matrix_mc_set_taps(self.handle, out_first, w.shape[0], in_first, w.shape[1], wre.ctypes.data,
+                                                         wim.ctypes.data), "llz_adapt_bands_matrix_mc_set_taps")
+
+    def get_taps(self, out_first=0, out_count=None, in_first=0, in_count=None):
+        """the weights of the paths (out_first .., in_first ..) (default: all from there) as complex64 [out_count, in_count, taps,
+        bins]: the handle's own float32 values"""
+        out_count = self.outputs - out_first if out_count is None else out_count
+        in_count = self.inputs - in_first if in_count is None else in_count
+        wre = np.empty((max(out_count, 0), max(in_count, 0), self.taps, self.bins), dtype=np.float32)
+        wim = np.empty_like(wre)
+        check(self._L.llz_adapt_bands_matrix_mc_get_taps(self.handle, out_first, out_count, in_first, in_count, wre.ctypes.data,
+                                                         wim.ctypes.data), "llz_adapt_bands_matrix_mc_get_taps")
+        w = np.empty(wre.shape, dtype=np.complex64)
+        w.real, w.imag = wre, wim
+        return w
+
+    def reset(self, clear_taps=False):
+        check(self._L.llz_adapt_bands_matrix_mc_reset(self.handle, 1 if clear_taps else 0), "llz_adapt_bands_matrix_mc_reset")
+
+    def frames(self):
+        """frames taken since init or reset"""
+        n = C.c_longlong()
+        check(self._L.llz_adapt_bands_matrix_mc_frames(self.handle, C.byref(n)), "llz_adapt_bands_matrix_mc_frames")
+        return n.value
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_adapt_bands_matrix_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
