@@ -278,6 +278,17 @@ int llzs_matrix_bands_nlms_f32(const float *xre, const float *xim, const float *
                                float *hout_re, float *hout_im, const float *mu, float delta, int inputs, int outputs, int bins,
                                int taps, int frames, void *stream);
 int llzs_matrix_bands_nlms_plan(int inputs, int outputs, int bins, int taps, int *out);
+/* the Kalman filter per band (kalman_bands.hip; include/llz_kalman_bands.h), float32: `taps` = K complex taps, 1..32, for every
+ * (channel, bin), one launch for a call of `frames` >= 1 frames.  x, d, e, y, w and h as llzs_bands_nlms_f32 has them; var =
+ * [channels][K][bins] state variances by age and noise = [channels][bins] noise powers, read, walked through the frames and
+ * written back like w.  adapt = [channels] ints on the device, 0 = the channel is frozen.  consts = HOST {A2, 1 - A2, lam,
+ * 1 - lam, delta}, the header's float32 constants.  fill: dst[i] = value, i < count (the variances at p0).  plan: out = {tap
+ * ceiling of the instance, threads per workgroup, workgroups, launches}. */
+int llzs_kalman_bands_f32(const float *xre, const float *xim, const float *dre, const float *dim, float *ere, float *eim,
+                          float *yre, float *yim, float *wre, float *wim, float *hre, float *him, float *var, float *noise,
+                          const int *adapt, const float *consts, int channels, int bins, int taps, int frames, void *stream);
+int llzs_kalman_bands_fill_f32(float *dst, float value, size_t count, void *stream);
+int llzs_kalman_bands_plan(int channels, int bins, int taps, int *out);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

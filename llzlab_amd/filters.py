@@ -705,6 +705,112 @@ class AdaptBandsMatrixMC:
     __del__ = close
 
 
+class KalmanBandsMC:
+    """band signals [channels, frames, bins] float32, re and im apart (AdaptBandsMC's layout): llz_kalman_bands_mc_*, the diagonal
+    Kalman adaptive filter of `taps` (1..32) complex taps for every (channel, bin) (include/llz_kalman_bands.h) -- AdaptBandsMC's
+    place in a subband echo canceller, with the step controlled by a variance per tap and a tracked noise power, so that it
+    survives double-talk unattended.  a: the state transition in (0, 1]; lam: the smoothing of the noise power in [0, 1); p0: the
+    variances at init; delta: the regularisation.  Every channel adapts until set_adapt says otherwise."""
+
+    def __init__(self, channels, bins, taps, a=0.999, lam=0.9, p0=1.0, delta=1e-3, stream=None):
+        self._L = capi.lib()
+        self.handle = check_handle(self._L.llz_kalman_bands_mc_init(channels, bins, taps, a, lam, p0, delta),
+                                   "llz_kalman_bands_mc_init")
+        self.channels, self.bins, self.taps = channels, bins, taps
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_kalman_bands_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_kalman_bands_mc_set_stream")
+
+    def plan(self):
+        """(tap ceiling of the kernel instance, threads per workgroup, workgroups, launches per call)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_kalman_bands_mc_plan(self.handle, out), "llz_kalman_bands_mc_plan")
+        return tuple(out)
+
+    def process(self, x_re, x_im, d_re, d_im, e_re, e_im, y_re=None, y_im=None):
+        """x (reference), d (desired), e (error, written), y (filter output, written when both are given): [channels, frames,
+        bins] float32 each (torch device tensors or numpy), any number of frames, none included.  Returns (e_re, e_im)."""
+        if (y_re is None) != (y_im is None):
+            raise LlzError("KalmanBandsMC.process: y_re and y_im must both be given or both be None")
+        frames = (x_re.numel() if hasattr(x_re, "numel") else x_re.size) // (self.channels * self.bins)
+        count = self.channels * frames * self.bins
+        bufs = [("x_re", x_re), ("x_im", x_im), ("d_re", d_re), ("d_im", d_im), ("e_re", e_re), ("e_im", e_im)]
+        bufs += [("y_re", y_re), ("y_im", y_im)] if y_re is not None else []
+        ptrs = [_typed(b, "float32", count, "KalmanBandsMC.process " + name) for name, b in bufs]
+        ptrs += [None] * (8 - len(ptrs))
+        check(self._L.llz_kalman_bands_mc(self.handle, *ptrs, frames), "llz_kalman_bands_mc")
+        return e_re, e_im
+
+    def set_adapt(self, first, on):
+        """whether channels first .. first + count - 1 adapt: [count] truth values (or one), False = frozen"""
+        on = np.ascontiguousarray(np.atleast_1d(on) != 0, dtype=np.int32)
+        check(self._L.llz_kalman_bands_mc_set_adapt(self.handle, first, on.shape[0], on.ctypes.data), "llz_kalman_bands_mc_set_adapt")
+
+    def _rows(self, a, what):
+        a = a[None] if a.ndim == 2 else a
+        if a.ndim != 3 or a.shape[1:] != (self.taps, self.bins):
+            raise LlzError(f"KalmanBandsMC.{what}: must be [count, taps = {self.taps}, bins = {self.bins}], got {a.shape}")
+        return a
+
+    def set_taps(self, first, w):
+        """replace the weights of channels first .. first + count - 1; w: complex [count, taps, bins] (row q the taps of age q),
+        or [taps, bins] for one channel; history, variances and noise powers are kept"""
+        w = self._rows(np.asarray(w), "set_taps")
+        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
+        check(self._L.llz_kalman_bands_mc_set_taps(self.handle, first, w.shape[0], wre.ctypes.data, wim.ctypes.data),
+              "llz_kalman_bands_mc_set_taps")
+
+    def get_taps(self, first=0, count=None):
+        """the weights of channels first .. first + count - 1 (default: all from first) as complex64 [count, taps, bins]"""
+        count = self.channels - first if count is None else count
+        wre = np.empty((max(count, 0), self.taps, self.bins), dtype=np.float32)
+        wim = np.empty_like(wre)
+        check(self._L.llz_kalman_bands_mc_get_taps(self.handle, first, count, wre.ctypes.data, wim.ctypes.data),
+              "llz_kalman_bands_mc_get_taps")
+        w = np.empty(wre.shape, dtype=np.complex64)
+        w.real, w.imag = wre, wim
+        return w
+
+    def set_variance(self, first, p):
+        """replace the variances of channels first .. first + count - 1; p: real [count, taps, bins] or [taps, bins], finite and
+        >= 0 -- raising them re-opens adaptation after a known path change"""
+        p = np.ascontiguousarray(self._rows(np.asarray(p), "set_variance"), dtype=np.float32)
+        check(self._L.llz_kalman_bands_mc_set_variance(self.handle, first, p.shape[0], p.ctypes.data),
+              "llz_kalman_bands_mc_set_variance")
+
+    def get_variance(self, first=0, count=None):
+        """the variances of channels first .. first + count - 1 as float32 [count, taps, bins]"""
+        count = self.channels - first if count is None else count
+        p = np.empty((max(count, 0), self.taps, self.bins), dtype=np.float32)
+        check(self._L.llz_kalman_bands_mc_get_variance(self.handle, first, count, p.ctypes.data), "llz_kalman_bands_mc_get_variance")
+        return p
+
+    def get_noise(self, first=0, count=None):
+        """the noise powers of channels first .. first + count - 1 as float32 [count, bins]"""
+        count = self.channels - first if count is None else count
+        psi = np.empty((max(count, 0), self.bins), dtype=np.float32)
+        check(self._L.llz_kalman_bands_mc_get_noise(self.handle, first, count, psi.ctypes.data), "llz_kalman_bands_mc_get_noise")
+        return psi
+
+    def reset(self, clear=False):
+        check(self._L.llz_kalman_bands_mc_reset(self.handle, 1 if clear else 0), "llz_kalman_bands_mc_reset")
+
+    def frames(self):
+        """frames taken since init or reset"""
+        n = C.c_longlong()
+        check(self._L.llz_kalman_bands_mc_frames(self.handle, C.byref(n)), "llz_kalman_bands_mc_frames")
+        return n.value
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_kalman_bands_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
