@@ -227,6 +227,19 @@ def lib():
     sig("llz_kalman_bands_mc_frames", i, ul, C.POINTER(C.c_longlong))
     sig("llz_kalman_bands_mc_plan", i, ul, C.POINTER(C.c_int))
     sig("llz_kalman_bands_mc_set_stream", i, ul, vp)
+    # llz_suppress_bands.h
+    sig("llz_suppress_bands_mc_default_cfg", None, vp)
+    sig("llz_suppress_bands_mc_init", ul, i, i, vp)
+    sig("llz_suppress_bands_mc_uninit", None, ul)
+    sig("llz_suppress_bands_mc", i, ul, vp, vp, vp, vp, vp, vp, vp, i)
+    sig("llz_suppress_bands_mc_set_floor", i, ul, i, i, vp)
+    sig("llz_suppress_bands_mc_set_leak", i, ul, i, i, vp)
+    sig("llz_suppress_bands_mc_set_enable", i, ul, i, i, vp)
+    sig("llz_suppress_bands_mc_get_state", i, ul, i, i, i, vp)
+    sig("llz_suppress_bands_mc_reset", i, ul)
+    sig("llz_suppress_bands_mc_frames", i, ul, C.POINTER(C.c_longlong))
+    sig("llz_suppress_bands_mc_plan", i, ul, C.POINTER(C.c_int))
+    sig("llz_suppress_bands_mc_set_stream", i, ul, vp)
     # llz_adapt_matrix.h
     sig("llz_adapt_matrix_mc_init", ul, i, i, i, i, i, C.c_float, C.c_float)
     sig("llz_adapt_matrix_mc_uninit", None, ul)

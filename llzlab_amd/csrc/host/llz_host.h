@@ -20,7 +20,8 @@ enum {
     LLZ_TAG_FFTX = 0x4c5a5458, LLZ_TAG_FIRB = 0x4c5a4642, LLZ_TAG_IIRB = 0x4c5a4942, LLZ_TAG_FIRS = 0x4c5a4653,
     LLZ_TAG_FIRX = 0x4c5a4658, LLZ_TAG_ADPT = 0x4c5a4144, LLZ_TAG_ADPX = 0x4c5a4158,
     LLZ_TAG_ASRC = 0x4c5a5352, LLZ_TAG_PFB = 0x4c5a5046, LLZ_TAG_ADPB = 0x4c5a4142,
-    LLZ_TAG_ADBX = 0x4c5a4258, LLZ_TAG_KALB = 0x4c5a4b42
+    LLZ_TAG_ADBX = 0x4c5a4258, LLZ_TAG_KALB = 0x4c5a4b42,
+    LLZ_TAG_SUPB = 0x4c5a5342
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))

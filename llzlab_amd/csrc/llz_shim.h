@@ -289,6 +289,18 @@ int llzs_kalman_bands_f32(const float *xre, const float *xim, const float *dre, 
                           const int *adapt, const float *consts, int channels, int bins, int taps, int frames, void *stream);
 int llzs_kalman_bands_fill_f32(float *dst, float value, size_t count, void *stream);
 int llzs_kalman_bands_plan(int channels, int bins, int taps, int *out);
+/* the noise and residual-echo postfilter per band (suppress_bands.hip; include/llz_suppress_bands.h), float32: a real gain for
+ * every (channel, bin, frame), one launch for a call of `frames` >= 1 frames.  e, y (both NULL or both set), o and g (NULL: not
+ * stored) = [channels][frames][bins].  state = [7][channels][bins], S Smin Stmp q N R Z, read, walked through the frames and
+ * written back.  floors, leaks = [channels] floats and enable = [channels] ints on the device, 0 = the channel is passed through.
+ * consts = HOST {omas, omaq, omad, omb, kt, aq, beta, rho, delta, t1}, the header's float32 constants; window = W.  n0 = the frame
+ * count at the call's first frame folded into [0, 2 W): the count itself below W, else W + count % W.  fill: dst[i] = value,
+ * i < count (q at 1).  plan: out = {with_y != 0, threads per workgroup, workgroups, launches}. */
+int llzs_suppress_bands_f32(const float *ere, const float *eim, const float *yre, const float *yim, float *ore, float *oim,
+                            float *g, float *state, const float *floors, const float *leaks, const int *enable,
+                            const float *consts, int window, int channels, int bins, int frames, int n0, void *stream);
+int llzs_suppress_bands_fill_f32(float *dst, float value, size_t count, void *stream);
+int llzs_suppress_bands_plan(int channels, int bins, int with_y, int *out);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,
                       int channels, long n, long in_pitch, int flt_len, void *stream);

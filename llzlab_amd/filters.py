@@ -811,6 +811,98 @@ class KalmanBandsMC:
     __del__ = close
 
 
+class SuppressCfg(C.Structure):
+    """llz_suppress_cfg of include/llz_suppress_bands.h"""
+    _fields_ = [("window", C.c_int), ("as_", C.c_float), ("aq", C.c_float), ("ad", C.c_float), ("t0", C.c_float),
+                ("t1", C.c_float), ("beta", C.c_float), ("rho", C.c_float), ("delta", C.c_float)]
+
+
+class SuppressBandsMC:
+    """band signals [channels, frames, bins] float32, re and im apart (KalmanBandsMC's layout): llz_suppress_bands_mc_*, the noise
+    and residual-echo postfilter behind a subband echo canceller (include/llz_suppress_bands.h) -- a real gain per (channel, bin,
+    frame) from a tracked noise power (MCRA), a decision-directed Wiener rule and a peak-hold residual-echo estimate eta |y|^2.
+    It takes KalmanBandsMC's e and, on request, y; without y it is a noise suppressor for any band signal.  window: frames of
+    the minimum search and of the start-up, which is taken as noise only; the other parameters are the header's.  Every channel
+    is enabled, with a floor of 0.1 and no leakage, until the setters say otherwise."""
+    STATES = ("S", "Smin", "Stmp", "q", "N", "R", "Z")
+
+    def __init__(self, channels, bins, window=128, as_=0.8, aq=0.2, ad=0.95, t0=2.0, t1=5.0, beta=0.98, rho=0.6, delta=1e-6,
+                 stream=None):
+        self._L = capi.lib()
+        cfg = SuppressCfg()
+        self._L.llz_suppress_bands_mc_default_cfg(C.byref(cfg))
+        cfg.window, cfg.as_, cfg.aq, cfg.ad, cfg.t0, cfg.t1, cfg.beta, cfg.rho, cfg.delta = window, as_, aq, ad, t0, t1, beta, rho, delta
+        self.handle = check_handle(self._L.llz_suppress_bands_mc_init(channels, bins, C.byref(cfg)), "llz_suppress_bands_mc_init")
+        self.channels, self.bins, self.window = channels, bins, window
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_suppress_bands_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_suppress_bands_mc_set_stream")
+
+    def plan(self):
+        """(1 when the last call took y else 0, threads per workgroup, workgroups, launches per call)"""
+        out = (C.c_int * 4)()
+        check(self._L.llz_suppress_bands_mc_plan(self.handle, out), "llz_suppress_bands_mc_plan")
+        return tuple(out)
+
+    def process(self, e_re, e_im, o_re, o_im, y_re=None, y_im=None, g=None):
+        """e (the canceller's error), o (written), y (its echo estimate, read when both are given), g (the gain, written when
+        given): [channels, frames, bins] float32 each (torch device tensors or numpy), any number of frames, none included.
+        Returns (o_re, o_im)."""
+        if (y_re is None) != (y_im is None):
+            raise LlzError("SuppressBandsMC.process: y_re and y_im must both be given or both be None")
+        frames = (e_re.numel() if hasattr(e_re, "numel") else e_re.size) // (self.channels * self.bins)
+        count = self.channels * frames * self.bins
+        bufs = [("e_re", e_re), ("e_im", e_im), ("y_re", y_re), ("y_im", y_im), ("o_re", o_re), ("o_im", o_im), ("g", g)]
+        ptrs = [None if b is None else _typed(b, "float32", count, "SuppressBandsMC.process " + name) for name, b in bufs]
+        check(self._L.llz_suppress_bands_mc(self.handle, *ptrs, frames), "llz_suppress_bands_mc")
+        return o_re, o_im
+
+    def _per_channel(self, name, first, values, dtype):
+        v = np.ascontiguousarray(np.atleast_1d(values), dtype=dtype)
+        check(getattr(self._L, "llz_suppress_bands_mc_" + name)(self.handle, first, v.shape[0], v.ctypes.data),
+              "llz_suppress_bands_mc_" + name)
+
+    def set_floor(self, first, gmin):
+        """the gain floors of channels first .. first + count - 1: [count] values (or one) in [0, 1]"""
+        self._per_channel("set_floor", first, gmin, np.float32)
+
+    def set_leak(self, first, eta):
+        """the echo leakages of channels first .. first + count - 1: [count] values (or one), finite and >= 0"""
+        self._per_channel("set_leak", first, eta, np.float32)
+
+    def set_enable(self, first, on):
+        """whether channels first .. first + count - 1 are processed: [count] truth values (or one), False = passed through"""
+        self._per_channel("set_enable", first, np.atleast_1d(on) != 0, np.int32)
+
+    def get_state(self, which, first=0, count=None):
+        """state value `which` (0..6 or one of STATES) of channels first .. first + count - 1 as float32 [count, bins]"""
+        which = self.STATES.index(which) if isinstance(which, str) else which
+        count = self.channels - first if count is None else count
+        out = np.empty((max(count, 0), self.bins), dtype=np.float32)
+        check(self._L.llz_suppress_bands_mc_get_state(self.handle, which, first, count, out.ctypes.data),
+              "llz_suppress_bands_mc_get_state")
+        return out
+
+    def reset(self):
+        """state and frame count back to init; flags, floors and leakages are kept"""
+        check(self._L.llz_suppress_bands_mc_reset(self.handle), "llz_suppress_bands_mc_reset")
+
+    def frames(self):
+        """frames taken since init or reset"""
+        n = C.c_longlong()
+        check(self._L.llz_suppress_bands_mc_frames(self.handle, C.byref(n)), "llz_suppress_bands_mc_frames")
+        return n.value
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_suppress_bands_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ IIR
 class IirFilter:
     """Single channel direct form I, double, host buffers: llz_iir_filter_*."""
