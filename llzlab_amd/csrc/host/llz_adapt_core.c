@@ -13,6 +13,20 @@
 
 static int adapt_mu_ok(float mu) { return mu >= 0.f && mu <= 2.f; }                            /* a NaN fails both */
 
+int llz_adapt_refuse_mu(const char *who, float mu)
+{
+    if (adapt_mu_ok(mu)) return 0;
+    llzs_set_error("%s: mu %g outside 0..2", who, (double)mu);
+    return 1;
+}
+
+int llz_adapt_refuse_delta(const char *who, float delta)
+{
+    if (delta > 0.f && isfinite(delta)) return 0;                                               /* a NaN fails the first */
+    llzs_set_error("%s: delta %g is not a finite value above 0", who, (double)delta);
+    return 1;
+}
+
 int llz_adapt_refuse(const char *who, int block, int frame_len, int max_blocks, int flt_len, float mu, float delta)
 {
     if (block == 4096) {
@@ -35,15 +49,7 @@ int llz_adapt_refuse(const char *who, int block, int frame_len, int max_blocks, 
         llzs_set_error("%s: flt_len %d outside 1..%d", who, flt_len, LLZS_FIR_PART_MAX_TAPS);
         return 1;
     }
-    if (!adapt_mu_ok(mu)) {
-        llzs_set_error("%s: mu %g outside 0..2", who, (double)mu);
-        return 1;
-    }
-    if (!(delta > 0.f) || !isfinite(delta)) {
-        llzs_set_error("%s: delta %g is not a finite value above 0", who, (double)delta);
-        return 1;
-    }
-    return 0;
+    return llz_adapt_refuse_mu(who, mu) || llz_adapt_refuse_delta(who, delta);
 }
 
 int llz_adapt_steps_create(llz_adapt_steps_t *s, const char *who, int count, float mu)

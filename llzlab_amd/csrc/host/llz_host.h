@@ -200,6 +200,10 @@ int   llz_bind_finish(llz_bind_t *b, int count, void *stream, int rc);
  * in 64..2048; 4096 has a message of its own), frame_len = k x block with k >= 1 (max_blocks != 0: k in 1..max_blocks), flt_len,
  * mu in 0..2, delta finite and above 0 */
 int  llz_adapt_refuse(const char *who, int block, int frame_len, int max_blocks, int flt_len, float mu, float delta);
+/* its last two on their own, for the per-band filters: "<who>: mu <mu> outside 0..2" and "<who>: delta <delta> is not a finite
+ * value above 0" */
+int  llz_adapt_refuse_mu(const char *who, float mu);
+int  llz_adapt_refuse_delta(const char *who, float delta);
 
 /* the step sizes of `count` rows (channels, outputs): the device array the kernels read and its host copy, which tells a call
  * whether anything adapts */
@@ -234,6 +238,70 @@ int  llz_adapt_io_begin(llz_adapt_io_t *io, const char *who, const float *x, siz
                         size_t bytes, void *stream);
 int  llz_adapt_io_end(llz_adapt_io_t *io, int rc, void *stream);
 void llz_adapt_io_release(llz_adapt_io_t *io);
+
+/* ---- llz_bands_core.c: what the per-band handles share (llz_adapt_bands_mc, llz_adapt_bands_matrix_mc, llz_kalman_bands_mc,
+ * llz_suppress_bands_mc) ---- */
+
+#define LLZ_BANDS_MAX_BINS 4097
+#define LLZ_BANDS_MAX_CHANNELS 65535
+enum { LLZ_BANDS_MAX_BUFS = 8 };
+
+/* an init's refusal of a count: 1 and "<who>: <name> <value> outside <lowest>..<highest>" */
+int  llz_bands_refuse_count(const char *who, const char *name, int value, int lowest, int highest);
+/* a call's refusals behind its handle, 1 when refused: frames negative or frames x bins not below 2^31; half a y */
+int  llz_bands_refuse_call(const char *who, int frames, int bins, const float *yre, const float *yim);
+
+/* One caller buffer of a call, in the order the kernel takes them, the inputs first.  user NULL: an optional buffer that is
+ * absent -- it is not classified, refused, staged or counted. */
+typedef struct {
+    const char *name;
+    const void *user;
+    size_t bytes;
+    int optional;
+} llz_bands_buf_t;
+/* x, d, e and an optional y, re and im apart, of xb and db bytes: the table of the three adaptive calls, from their parameters */
+#define LLZ_BANDS_XDEY(xb, db)                                                                                             \
+    { { "xre", xre, xb, 0 }, { "xim", xim, xb, 0 }, { "dre", dre, db, 0 }, { "dim", dim, db, 0 },                          \
+      { "ere", ere, db, 0 }, { "eim", eim, db, 0 }, { "yre", yre, db, 1 }, { "yim", yim, db, 1 } }
+typedef struct {
+    llz_stage_t st[LLZ_BANDS_MAX_BUFS];
+    void *dev[LLZ_BANDS_MAX_BUFS];      /* what to launch with: the caller's device memory or the stage; NULL when absent */
+    void *back[LLZ_BANDS_MAX_BUFS];     /* host memory an output is copied back to, or NULL */
+    size_t bytes[LLZ_BANDS_MAX_BUFS];
+    int count, inputs, entered, prev;
+} llz_bands_io_t;
+/* what every per-band handle starts with */
+typedef struct {
+    llz_head_t head;
+    long long frames;                   /* frames since init or reset */
+    llz_bands_io_t io;
+} llz_bands_t;
+/* The staged call.  begin: a missing buffer that is not optional is refused ("<who>: NULL buffer"); then the handle's device is
+ * entered, the buffers are classified, every output is refused against every buffer in front of it (llz_refuse_device_overlap),
+ * and only then inputs are staged and uploaded and outputs reserved, in the table's order; out of device memory the message
+ * names the buffers and their bytes (split != 0: b[0]'s as x's and b[split]'s).  io.dev is what to launch with.  end(rc of the
+ * launch) counts the frames of a launch that was issued, copies the host outputs back, leaves the device and returns frames or
+ * the first error; it is called whatever begin returned. */
+int  llz_bands_begin(llz_bands_t *f, const char *who, const llz_bands_buf_t *b, int count, int inputs, int split);
+int  llz_bands_end(llz_bands_t *f, int rc, int frames);
+void llz_bands_release(llz_bands_t *f);
+
+/* the handle, or NULL with "<who>: bad handle" or, out being NULL, "<who>: no out": the head of plan and frames */
+void *llz_bands_out(unsigned long h, int tag, const char *who, const void *out);
+int  llz_bands_frames(unsigned long h, int tag, const char *who, long long *out);
+/* the refusals of a set_* or get_* call behind its handle, 1 when refused: a or b NULL; rows [first, first + count) outside
+ * [0, have), with the rows' noun ("channels", "outputs", "inputs") */
+int  llz_bands_refuse_range(const char *who, const char *noun, int first, int count, int have, const void *a, const void *b);
+/* rows [first, first + count) of a state array of row_bytes per row, up from src (not NULL) or down to dst, on the handle's
+ * device and ordered on its stream; _pair: the re and im arrays of `row` floats per row, one after the other */
+int  llz_bands_copy(const llz_bands_t *f, void *d_state, size_t row_bytes, int first, int count, const void *src, void *dst);
+int  llz_bands_copy_pair(const llz_bands_t *f, float *const d_state[2], size_t row, int first, int count, const float *src_re,
+                         const float *src_im, float *dst_re, float *dst_im);
+/* zeros in `count` floats of a re and an im array, on the stream */
+int  llz_bands_zero_pair(float *const d[2], size_t count, void *stream);
+/* flags [first, first + count) of a device array of ints to on[] != 0 (on NULL: all 1), through llz_bands_copy; out of host
+ * memory "<who>: no host memory for <bytes> B of <what>" */
+int  llz_bands_flags(const llz_bands_t *f, const char *who, const char *what, int *d_flags, int first, int count, const int *on);
 
 /* ---- llz_fade.c: the crossfade state of the delay-line convolvers (llz_fir_xfade_stream_mc, llz_fir_xfade_matrix_mc) ---- */
 

@@ -1,29 +1,22 @@
 /* llz_suppress_bands_host.c -- include/llz_suppress_bands.h: llz_suppress_bands_mc, the noise and residual-echo postfilter per
- * band (kernel K4m, suppress_bands.hip), after llz_kalman_bands_host.c.  The head, the staged call and the overlap refusal are
- * llz_util.c's.  What is this file's own: the state -- seven rows [channels][bins], which the one launch of a call reads and writes
- * back -- in the layout of get_state, so that it is a plain copy on the stream; the floors, leakages and flags per channel; the
- * float32 constants of the recursion; the frame counter, which the kernel gets folded into two windows; and the seven caller
- * buffers of a call, three of them optional. */
+ * band (kernel K4m, suppress_bands.hip).  The head is llz_util.c's, the staged call, the counter, the copies and the flag upload
+ * llz_bands_core.c's.  What is this file's own: the state -- seven rows [channels][bins], which the one launch of a call reads and
+ * writes back -- in the layout of get_state, so that it is a plain copy on the stream; the floors, leakages and flags per
+ * channel; the float32 constants of the recursion; the folding of the frame counter into two windows for the kernel; and the
+ * seven caller buffers of a call, three of them optional. */
 #include <math.h>
 #include <stdlib.h>
 #include "llz_host.h"
 #include "../../../include/llz_suppress_bands.h"
 
-#define SUPPRESS_MAX_BINS 4097
-
-enum { B_ERE, B_EIM, B_YRE, B_YIM, B_ORE, B_OIM, B_G, B_COUNT, B_INPUTS = B_ORE };
-static const char *const suppress_name[B_COUNT] = { "ere", "eim", "yre", "yim", "ore", "oim", "g" };
-
 typedef struct {
-    llz_head_t head;
+    llz_bands_t b;
     int channels, bins, window;
     int with_y;                         /* the last call's form, for plan */
     float consts[10];                   /* omas, omaq, omad, omb, kt, aq, beta, rho, delta, t1: each formed once, in float32 */
-    long long frames;                   /* frames since init or reset */
     float *d_state;                     /* device [7][channels][bins]: S, Smin, Stmp, q, N, R, Z */
     float *d_floor, *d_leak;            /* device [channels] */
     int *d_on;                          /* device [channels]: 1 = the channel is processed */
-    llz_stage_t st[B_COUNT];
 } suppress_t;
 
 static void suppress_destroy(void *p)
@@ -33,8 +26,8 @@ static void suppress_destroy(void *p)
     llzs_free(f->d_floor);
     llzs_free(f->d_leak);
     llzs_free(f->d_on);
-    for (int b = 0; b < B_COUNT; b++) llz_stage_release(&f->st[b]);
-    f->head.tag = 0;
+    llz_bands_release(&f->b);
+    f->b.head.tag = 0;
     free(f);
 }
 
@@ -58,38 +51,25 @@ static int suppress_unit(const char *who, const char *name, float v)
 
 static int suppress_refuse(const char *who, int channels, int bins, const llz_suppress_cfg *cfg)
 {
-    if (channels < 1 || channels > 65535) {
-        llzs_set_error("%s: channels %d outside 1..65535", who, channels);
+    if (llz_bands_refuse_count(who, "channels", channels, 1, LLZ_BANDS_MAX_CHANNELS) ||
+        llz_bands_refuse_count(who, "bins", bins, 1, LLZ_BANDS_MAX_BINS) || llz_bands_refuse_count(who, "window", cfg->window, 2, 65535))
         return 1;
-    }
-    if (bins < 1 || bins > SUPPRESS_MAX_BINS) {
-        llzs_set_error("%s: bins %d outside 1..%d", who, bins, SUPPRESS_MAX_BINS);
-        return 1;
-    }
-    if (cfg->window < 2 || cfg->window > 65535) {
-        llzs_set_error("%s: window %d outside 2..65535", who, cfg->window);
-        return 1;
-    }
     if (suppress_unit(who, "as", cfg->as) || suppress_unit(who, "aq", cfg->aq) || suppress_unit(who, "ad", cfg->ad) ||
         suppress_unit(who, "beta", cfg->beta) || suppress_unit(who, "rho", cfg->rho)) return 1;
     if (!(cfg->t0 > 0.f) || !(cfg->t1 > cfg->t0) || !isfinite(cfg->t1)) {
         llzs_set_error("%s: thresholds t0 %g, t1 %g are not finite with 0 < t0 < t1", who, (double)cfg->t0, (double)cfg->t1);
         return 1;
     }
-    if (!(cfg->delta > 0.f) || !isfinite(cfg->delta)) {
-        llzs_set_error("%s: delta %g is not a finite value above 0", who, (double)cfg->delta);
-        return 1;
-    }
-    return 0;
+    return llz_adapt_refuse_delta(who, cfg->delta);
 }
 
 /* S = Smin = Stmp = N = R = Z = 0, q = 1 and the counter at 0, ordered on the handle's stream */
 static int suppress_clear(suppress_t *f)
 {
     const size_t row = suppress_row(f);
-    int rc = llzs_memset(f->d_state, 0, sizeof(float) * (size_t)LLZ_SUPPRESS_STATES * row, f->head.stream);
-    if (rc == LLZ_OK) rc = llzs_suppress_bands_fill_f32(f->d_state + (size_t)LLZ_SUPPRESS_Q * row, 1.f, row, f->head.stream);
-    if (rc == LLZ_OK) f->frames = 0;
+    int rc = llzs_memset(f->d_state, 0, sizeof(float) * (size_t)LLZ_SUPPRESS_STATES * row, f->b.head.stream);
+    if (rc == LLZ_OK) rc = llzs_fill_f32(f->d_state + (size_t)LLZ_SUPPRESS_Q * row, 1.f, row, f->b.head.stream);
+    if (rc == LLZ_OK) f->b.frames = 0;
     return rc;
 }
 
@@ -115,7 +95,7 @@ unsigned long llz_suppress_bands_mc_init(int channels, int bins, const llz_suppr
     const size_t cbytes = sizeof(float) * (size_t)channels;
     float *floors = NULL;
     int *flags = NULL;
-    int rc = f->head.device < 0 ? LLZ_ERR_DEVICE : LLZ_OK;
+    int rc = f->b.head.device < 0 ? LLZ_ERR_DEVICE : LLZ_OK;
     if (rc == LLZ_OK) {
         f->d_state = (float *)llzs_malloc(sbytes);
         f->d_floor = (float *)llzs_malloc(cbytes);
@@ -140,9 +120,9 @@ unsigned long llz_suppress_bands_mc_init(int channels, int bins, const llz_suppr
             floors[c] = 0.1f;
             flags[c] = 1;
         }
-        rc = llzs_h2d(f->d_floor, floors, cbytes, f->head.stream);
-        if (rc == LLZ_OK) rc = llzs_h2d(f->d_on, flags, sizeof(int) * (size_t)channels, f->head.stream);
-        if (rc == LLZ_OK) rc = llzs_memset(f->d_leak, 0, cbytes, f->head.stream);
+        rc = llzs_h2d(f->d_floor, floors, cbytes, f->b.head.stream);
+        if (rc == LLZ_OK) rc = llzs_h2d(f->d_on, flags, sizeof(int) * (size_t)channels, f->b.head.stream);
+        if (rc == LLZ_OK) rc = llzs_memset(f->d_leak, 0, cbytes, f->b.head.stream);
     }
     free(floors);
     free(flags);
@@ -162,83 +142,28 @@ int llz_suppress_bands_mc(unsigned long h, const float *ere, const float *eim, c
 {
     const char *who = "llz_suppress_bands_mc";
     suppress_t *f = (suppress_t *)llz_handle(h, LLZ_TAG_SUPB, who);
-    if (!f) return LLZ_ERR_ARG;
-    if (frames < 0 || (long long)frames * f->bins > 2147483647LL) {
-        llzs_set_error("%s: frames %d outside 0..%d (frames x bins below 2^31, bins %d)", who, frames, 2147483647 / f->bins,
-                       f->bins);
-        return LLZ_ERR_ARG;
-    }
-    if (!yre != !yim) {
-        llzs_set_error("%s: yre and yim must both be NULL or both be set", who);
-        return LLZ_ERR_ARG;
-    }
+    if (!f || llz_bands_refuse_call(who, frames, f->bins, yre, yim)) return LLZ_ERR_ARG;
     if (frames == 0) return 0;
-    if (!ere || !eim || !ore || !oim) {
-        llzs_set_error("%s: NULL buffer", who);
-        return LLZ_ERR_ARG;
-    }
-    const void *user[B_COUNT] = { ere, eim, yre, yim, ore, oim, g };                            /* yre, yim and g may be absent */
     const size_t bytes = sizeof(float) * (size_t)f->channels * (size_t)frames * (size_t)f->bins;
-    const int prev = llzs_device_enter(f->head.device);
-    int on_dev[B_COUNT] = { 0 }, rc = LLZ_OK;
-    for (int b = 0; b < B_COUNT && rc == LLZ_OK; b++)
-        if (user[b] && (on_dev[b] = llzs_is_device_ptr(user[b])) < 0) rc = LLZ_ERR_ARG;         /* a buffer of another GPU: message set */
-    /* every output against every input and every output in front of it, before anything is staged or launched */
-    for (int o = B_INPUTS; o < B_COUNT && rc == LLZ_OK; o++)
-        for (int i = 0; i < o && rc == LLZ_OK; i++)
-            if (user[o] && user[i])
-                rc = llz_refuse_device_overlap(who, suppress_name[i], user[i], bytes, on_dev[i], suppress_name[o], user[o], bytes,
-                                               on_dev[o]);
-    void *dev[B_COUNT] = { NULL };
-    int nbuf = 0;
-    for (int b = 0; b < B_COUNT; b++) {
-        if (!user[b]) continue;
-        nbuf++;
-        dev[b] = b < B_INPUTS ? (void *)llz_stage_in(&f->st[b], user[b], bytes, on_dev[b], f->head.stream, &rc)
-                              : llz_stage_out(&f->st[b], (void *)user[b], bytes, on_dev[b], &rc);
-    }
-    if (rc == LLZ_ERR_NOMEM) llzs_set_error("%s: no device memory to stage %d buffers of %zu B", who, nbuf, bytes);
+    const llz_bands_buf_t buf[] = { { "ere", ere, bytes, 0 }, { "eim", eim, bytes, 0 }, { "yre", yre, bytes, 1 }, { "yim", yim, bytes, 1 },
+                                    { "ore", ore, bytes, 0 }, { "oim", oim, bytes, 0 }, { "g", g, bytes, 1 } };
+    void *const *dev = f->b.io.dev;
+    int rc = llz_bands_begin(&f->b, who, buf, 7, 4, 0);
     if (rc == LLZ_OK) {
         const int W = f->window;
-        const int n0 = f->frames < W ? (int)f->frames : W + (int)(f->frames % W);
-        rc = llzs_suppress_bands_f32((const float *)dev[B_ERE], (const float *)dev[B_EIM], (const float *)dev[B_YRE],
-                                     (const float *)dev[B_YIM], (float *)dev[B_ORE], (float *)dev[B_OIM], (float *)dev[B_G],
-                                     f->d_state, f->d_floor, f->d_leak, f->d_on, f->consts, W, f->channels, f->bins, frames, n0,
-                                     f->head.stream);
+        const int n0 = f->b.frames < W ? (int)f->b.frames : W + (int)(f->b.frames % W);
+        rc = llzs_suppress_bands_f32(dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], f->d_state, f->d_floor, f->d_leak,
+                                     f->d_on, f->consts, W, f->channels, f->bins, frames, n0, f->b.head.stream);
     }
-    if (rc == LLZ_OK) {
-        f->frames += frames;
-        f->with_y = yre != NULL;
-    }
-    for (int o = B_INPUTS; o < B_COUNT && rc == LLZ_OK; o++)
-        if (user[o] && !on_dev[o]) rc = llzs_d2h((void *)user[o], dev[o], bytes, f->head.stream);
-    llzs_device_leave(prev);
-    return rc == LLZ_OK ? frames : rc;
+    if (rc == LLZ_OK) f->with_y = yre != NULL;
+    return llz_bands_end(&f->b, rc, frames);
 }
 
 /* the handle and a channel range inside it, or NULL with a message naming who */
 static suppress_t *suppress_range(unsigned long h, const char *who, int first, int count, const void *a)
 {
     suppress_t *f = (suppress_t *)llz_handle(h, LLZ_TAG_SUPB, who);
-    if (!f) return NULL;
-    if (!a) {
-        llzs_set_error("%s: NULL buffer", who);
-        return NULL;
-    }
-    if (first < 0 || count < 1 || first >= f->channels || count > f->channels - first) {
-        llzs_set_error("%s: channels [%d, %d + %d) outside the handle's [0, %d)", who, first, first, count, f->channels);
-        return NULL;
-    }
-    return f;
-}
-
-/* `bytes` up to a per-channel array, ordered on the stream behind the calls already issued */
-static int suppress_upload(suppress_t *f, void *d_dst, const void *src, size_t bytes)
-{
-    const int prev = llzs_device_enter(f->head.device);
-    const int rc = llzs_h2d(d_dst, src, bytes, f->head.stream);
-    llzs_device_leave(prev);
-    return rc;
+    return f && !llz_bands_refuse_range(who, "channels", first, count, f->channels, a, a) ? f : NULL;
 }
 
 int llz_suppress_bands_mc_set_floor(unsigned long h, int first, int count, const float *gmin)
@@ -251,7 +176,7 @@ int llz_suppress_bands_mc_set_floor(unsigned long h, int first, int count, const
             llzs_set_error("%s: floor %g of channel %d is not in [0, 1]", who, (double)gmin[c], first + c);
             return LLZ_ERR_ARG;
         }
-    return suppress_upload(f, f->d_floor + first, gmin, sizeof(float) * (size_t)count);
+    return llz_bands_copy(&f->b, f->d_floor, sizeof(float), first, count, gmin, NULL);
 }
 
 int llz_suppress_bands_mc_set_leak(unsigned long h, int first, int count, const float *eta)
@@ -264,24 +189,14 @@ int llz_suppress_bands_mc_set_leak(unsigned long h, int first, int count, const 
             llzs_set_error("%s: leakage %g of channel %d is not finite and at least 0", who, (double)eta[c], first + c);
             return LLZ_ERR_ARG;
         }
-    return suppress_upload(f, f->d_leak + first, eta, sizeof(float) * (size_t)count);
+    return llz_bands_copy(&f->b, f->d_leak, sizeof(float), first, count, eta, NULL);
 }
 
 int llz_suppress_bands_mc_set_enable(unsigned long h, int first, int count, const int *on)
 {
     const char *who = "llz_suppress_bands_mc_set_enable";
     suppress_t *f = suppress_range(h, who, first, count, on);
-    if (!f) return LLZ_ERR_ARG;
-    const size_t bytes = sizeof(int) * (size_t)count;
-    int *flags = (int *)malloc(bytes);
-    if (!flags) {
-        llzs_set_error("%s: no host memory for %zu B of flags", who, bytes);
-        return LLZ_ERR_NOMEM;
-    }
-    for (int c = 0; c < count; c++) flags[c] = on[c] != 0;
-    const int rc = suppress_upload(f, f->d_on + first, flags, bytes);
-    free(flags);
-    return rc;
+    return f ? llz_bands_flags(&f->b, who, "flags", f->d_on, first, count, on) : LLZ_ERR_ARG;
 }
 
 int llz_suppress_bands_mc_get_state(unsigned long h, int which, int first, int count, float *out)
@@ -293,18 +208,14 @@ int llz_suppress_bands_mc_get_state(unsigned long h, int which, int first, int c
         llzs_set_error("%s: state value %d outside 0..%d (S, Smin, Stmp, q, N, R, Z)", who, which, LLZ_SUPPRESS_STATES - 1);
         return LLZ_ERR_ARG;
     }
-    const int prev = llzs_device_enter(f->head.device);
-    const int rc = llzs_d2h(out, f->d_state + (size_t)which * suppress_row(f) + (size_t)first * (size_t)f->bins,
-                            sizeof(float) * (size_t)count * (size_t)f->bins, f->head.stream);
-    llzs_device_leave(prev);
-    return rc;
+    return llz_bands_copy(&f->b, f->d_state + (size_t)which * suppress_row(f), sizeof(float) * (size_t)f->bins, first, count, NULL, out);
 }
 
 int llz_suppress_bands_mc_reset(unsigned long h)
 {
     suppress_t *f = (suppress_t *)llz_handle(h, LLZ_TAG_SUPB, "llz_suppress_bands_mc_reset");
     if (!f) return LLZ_ERR_ARG;
-    const int prev = llzs_device_enter(f->head.device);
+    const int prev = llzs_device_enter(f->b.head.device);
     const int rc = suppress_clear(f);
     llzs_device_leave(prev);
     return rc;
@@ -312,27 +223,13 @@ int llz_suppress_bands_mc_reset(unsigned long h)
 
 int llz_suppress_bands_mc_frames(unsigned long h, long long *out)
 {
-    const char *who = "llz_suppress_bands_mc_frames";
-    suppress_t *f = (suppress_t *)llz_handle(h, LLZ_TAG_SUPB, who);
-    if (!f) return LLZ_ERR_ARG;
-    if (!out) {
-        llzs_set_error("%s: no out", who);
-        return LLZ_ERR_ARG;
-    }
-    *out = f->frames;
-    return LLZ_OK;
+    return llz_bands_frames(h, LLZ_TAG_SUPB, "llz_suppress_bands_mc_frames", out);
 }
 
 int llz_suppress_bands_mc_plan(unsigned long h, int out[4])
 {
-    const char *who = "llz_suppress_bands_mc_plan";
-    suppress_t *f = (suppress_t *)llz_handle(h, LLZ_TAG_SUPB, who);
-    if (!f) return LLZ_ERR_ARG;
-    if (!out) {
-        llzs_set_error("%s: no out", who);
-        return LLZ_ERR_ARG;
-    }
-    return llzs_suppress_bands_plan(f->channels, f->bins, f->with_y, out);
+    const suppress_t *f = (const suppress_t *)llz_bands_out(h, LLZ_TAG_SUPB, "llz_suppress_bands_mc_plan", out);
+    return f ? llzs_suppress_bands_plan(f->channels, f->bins, f->with_y, out) : LLZ_ERR_ARG;
 }
 
 int llz_suppress_bands_mc_set_stream(unsigned long h, void *stream)

@@ -15,37 +15,9 @@
 //   p    = fma(x_im[q], x_im[q], fma(x_re[q], x_re[q], p))
 //   g    = (mu e) / (p + delta), a product and a correctly rounded quotient per component
 //   w_re[q] = fma(g_im, x_im[q], fma(g_re, x_re[q], w_re[q]));    w_im[q] = fma(-g_re, x_im[q], fma(g_im, x_re[q], w_im[q]))
-#include "common.hpp"
+#include "bands_steps.hpp"
 
 namespace {
-
-constexpr int BANDS_THREADS = 64;       // a workgroup is one wave: no lane shares anything with another
-
-template <int KC> struct bands_live {   // the taps an instance can take for granted: K > KC / 2 selects it (KC = 4: K >= 1)
-    static constexpr int value = KC == 4 ? 1 : KC / 2 + 1;
-};
-
-// element `off` (a byte offset below 2^32) behind a scalar base: one 32-bit register of address per lane for the whole state.
-// The base is pinned to scalar registers; left alone, the compiler folds the lane's offset into it and keeps a 64-bit address
-// per load in vector registers (twice the registers of the state itself in the prologue).
-__device__ __forceinline__ float bands_ld(const float *base, unsigned off)
-{
-    asm("" : "+s"(base));
-    return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off);
-}
-__device__ __forceinline__ void bands_st(float *base, unsigned off, float v)
-{
-    asm("" : "+s"(base));
-    *reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off) = v;
-}
-
-// an unrolled loop over the ages leaves at the first tap that does not exist; the empty statement keeps the test a scalar
-// branch (without it the compiler computes every tap of the ceiling and selects, at twice the registers)
-#define BANDS_TAPS(q)                                                                                                     \
-    _Pragma("unroll") for (int q = 0; q < KC; q++)                                                                        \
-        if (q >= LIVE && q >= K) break;                                                                                   \
-        else if (bands_keep_branch(), true)
-__device__ __forceinline__ void bands_keep_branch() { asm volatile(""); }
 
 template <int KC, bool HAS_Y>
 __global__ void __launch_bounds__(BANDS_THREADS)
@@ -55,7 +27,7 @@ k_bands_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const
              float *__restrict__ him, const float *__restrict__ mu, float delta, int lanes, int bins, int K, int frames)
 {
 #pragma clang fp contract(off)
-    constexpr int LIVE = bands_live<KC>::value;
+    constexpr int LIVE = bands_live<KC, 4, 1>::value;
     const int g0 = (int)blockIdx.x * BANDS_THREADS, g = g0 + (int)threadIdx.x;
     if (g >= lanes) return;
     const int c = g / bins, k = g - c * bins;
@@ -69,7 +41,7 @@ k_bands_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const
     float wr[KC], wi[KC], xr[KC], xi[KC];                                 // xr[q] = x[m - q] behind frame m's shift
 #pragma unroll
     for (int q = 0; q < KC; q++) wr[q] = wi[q] = xr[q] = xi[q] = 0.f;
-    BANDS_TAPS(q) {
+    BANDS_WALK(q, KC, K) {
         wr[q] = bands_ld(wre + wbase + (size_t)q * bins, woff);
         wi[q] = bands_ld(wim + wbase + (size_t)q * bins, woff);
         if (q + 1 < K) {                                                  // x[-1 - q]: shifted to age q + 1 by the first frame
@@ -92,17 +64,11 @@ k_bands_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const
             ndr = dre[o + bins];
             ndi = dim[o + bins];
         }
-        // the history moves on by one register, dead ones included: they take older frames that nothing reads, and a plain chain of
-        // moves leaves the walks below nothing to merge where they end
-#pragma unroll
-        for (int q = KC - 1; q > 0; q--) {
-            xr[q] = xr[q - 1];
-            xi[q] = xi[q - 1];
-        }
+        bands_shift<1>(xr, xi);
         xr[0] = cxr;
         xi[0] = cxi;
         float ar = 0.f, ai = 0.f, p = 0.f;                                // y and the power take their term of age q
-        BANDS_TAPS(q) {
+        BANDS_WALK(q, KC, K) {
             ar = __builtin_fmaf(wr[q], xr[q], ar);
             ar = __builtin_fmaf(-wi[q], xi[q], ar);
             ai = __builtin_fmaf(wr[q], xi[q], ai);
@@ -120,7 +86,7 @@ k_bands_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const
         if (step != 0.f) {
             const float den = p + delta;
             const float gr = (step * er) / den, gi = (step * ei) / den;
-            BANDS_TAPS(q) {
+            BANDS_WALK(q, KC, K) {
                 wr[q] = __builtin_fmaf(gr, xr[q], wr[q]);
                 wr[q] = __builtin_fmaf(gi, xi[q], wr[q]);
                 wi[q] = __builtin_fmaf(gi, xr[q], wi[q]);
@@ -128,7 +94,7 @@ k_bands_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const
             }
         }
     }
-    BANDS_TAPS(q) {
+    BANDS_WALK(q, KC, K) {
         bands_st(wre + wbase + (size_t)q * bins, woff, wr[q]);
         bands_st(wim + wbase + (size_t)q * bins, woff, wi[q]);
         if (q + 1 < K) {                                                  // x[last - q] is the next call's x[-1 - q]
@@ -137,17 +103,12 @@ k_bands_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const
         }
     }
 }
-#undef BANDS_TAPS
+static const int NLMS_LOWEST = 4, NLMS_HIGHEST = 64;                      // the tap ceilings of the instances
 
-static int bands_ceiling(int taps) { return taps <= 4 ? 4 : taps <= 8 ? 8 : taps <= 16 ? 16 : taps <= 32 ? 32 : 64; }
-
-static int bands_shape(const char *who, int channels, int bins, int taps)
+static int nlms_shape(const char *who, int channels, int bins, int taps)
 {
-    if (channels < 1 || channels > 65535 || bins < 1 || bins > 4097 || taps < 1 || taps > 64) {
-        llzs_set_error("%s: bad shape (channels=%d bins=%d taps=%d)", who, channels, bins, taps);
-        return LLZ_ERR_ARG;
-    }
-    return LLZ_OK;
+    const bands_dim dims[] = { { "channels", channels, 65535 }, { "bins", bins, 4097 }, { "taps", taps, NLMS_HIGHEST } };
+    return bands_shape(who, dims, 3);
 }
 
 } // namespace
@@ -162,10 +123,10 @@ extern "C" int llzs_bands_nlms_f32(const float *xre, const float *xim, const flo
         llzs_set_error("%s: bad arguments", who);
         return LLZ_ERR_ARG;
     }
-    const int rc = bands_shape(who, channels, bins, taps);
+    const int rc = nlms_shape(who, channels, bins, taps);
     if (rc != LLZ_OK) return rc;
     const int lanes = channels * bins;                                     // at most 65535 x 4097
-    const dim3 grid((unsigned)((lanes + BANDS_THREADS - 1) / BANDS_THREADS)), block(BANDS_THREADS);
+    const dim3 grid(bands_grid(lanes)), block(BANDS_THREADS);
 #define BANDS_LAUNCH(KC)                                                                                                  \
     do {                                                                                                                  \
         if (yre)                                                                                                          \
@@ -175,7 +136,7 @@ extern "C" int llzs_bands_nlms_f32(const float *xre, const float *xim, const flo
             hipLaunchKernelGGL((k_bands_nlms<KC, false>), grid, block, 0, as_stream(stream), xre, xim, dre, dim, ere, eim, yre, \
                                yim, wre, wim, hre, him, mu, delta, lanes, bins, taps, frames);                            \
     } while (0)
-    switch (bands_ceiling(taps)) {
+    switch (bands_ceiling(taps, NLMS_LOWEST, NLMS_HIGHEST)) {
     case 4: BANDS_LAUNCH(4); break;
     case 8: BANDS_LAUNCH(8); break;
     case 16: BANDS_LAUNCH(16); break;
@@ -189,15 +150,9 @@ extern "C" int llzs_bands_nlms_f32(const float *xre, const float *xim, const flo
 
 extern "C" int llzs_bands_nlms_plan(int channels, int bins, int taps, int *out)
 {
-    if (!out) {
-        llzs_set_error("bands_nlms_plan: no out");
-        return LLZ_ERR_ARG;
-    }
-    const int rc = bands_shape("bands_nlms_plan", channels, bins, taps);
-    if (rc != LLZ_OK) return rc;
-    out[0] = bands_ceiling(taps);
-    out[1] = BANDS_THREADS;
-    out[2] = (channels * bins + BANDS_THREADS - 1) / BANDS_THREADS;
-    out[3] = 1;
-    return LLZ_OK;
+    const char *who = "bands_nlms_plan";
+    int rc = bands_no_out(who, out);
+    if (rc == LLZ_OK) rc = nlms_shape(who, channels, bins, taps);
+    if (rc == LLZ_OK) bands_plan_tail(out, bands_ceiling(taps, NLMS_LOWEST, NLMS_HIGHEST), channels * bins);
+    return rc;
 }

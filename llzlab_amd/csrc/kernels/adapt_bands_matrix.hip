@@ -22,40 +22,14 @@
 //   g    = (mu e) / (p + delta), a product and a correctly rounded quotient per component
 //   w_re[j] = fma(g_im, x_im[j], fma(g_re, x_re[j], w_re[j]));    w_im[j] = fma(-g_re, x_im[j], fma(g_im, x_re[j], w_im[j]))
 // With I = 1 this is k_bands_nlms instruction for instruction in every sum, and its bits.
-#include "common.hpp"
+#include "bands_steps.hpp"
 
 namespace {
 
-constexpr int BMX_THREADS = 64;         // a workgroup is one wave: no lane shares anything with another but the history it reads
-constexpr int BMX_MAX_INPUTS = 8, BMX_MAX_ENTRIES = 64;
-
-template <int I, int JC> struct bmx_live {      // the entries an instance can take for granted
-    static constexpr int value = JC == 8 ? I : JC / 2 + 1;
-};
-
-// element `off` (a byte offset below 2^32) behind a scalar base, as in adapt_bands.hip: the base is pinned to scalar registers, so
-// the state and the references cost one 32-bit register of address per lane each
-__device__ __forceinline__ float bmx_ld(const float *base, unsigned off)
-{
-    asm("" : "+s"(base));
-    return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off);
-}
-__device__ __forceinline__ void bmx_st(float *base, unsigned off, float v)
-{
-    asm("" : "+s"(base));
-    *reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off) = v;
-}
-
-// an unrolled loop over the entries leaves at the first one that does not exist; the empty statement keeps the test a scalar
-// branch (without it the compiler computes every entry of the ceiling and selects, at twice the registers)
-#define BMX_ENTRIES(j)                                                                                                    \
-    _Pragma("unroll") for (int j = 0; j < JC; j++)                                                                        \
-        if (j >= LIVE && j >= J) break;                                                                                   \
-        else if (bmx_keep_branch(), true)
-__device__ __forceinline__ void bmx_keep_branch() { asm volatile(""); }
+constexpr int BMX_MAX_INPUTS = 8, BMX_LOWEST = 8, BMX_MAX_ENTRIES = 64;   // (the entry ceilings of the instances: 8 .. 64)
 
 template <int I, int JC, bool HAS_Y>
-__global__ void __launch_bounds__(BMX_THREADS)
+__global__ void __launch_bounds__(BANDS_THREADS)
 k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim, const float *__restrict__ dre,
                     const float *__restrict__ dim, float *__restrict__ ere, float *__restrict__ eim, float *__restrict__ yre,
                     float *__restrict__ yim, float *__restrict__ wre, float *__restrict__ wim, const float *__restrict__ hin_re,
@@ -63,8 +37,8 @@ k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim
                     const float *__restrict__ mu, float delta, int lanes, int bins, int K, int frames)
 {
 #pragma clang fp contract(off)
-    constexpr int LIVE = bmx_live<I, JC>::value;
-    const int g0 = (int)blockIdx.x * BMX_THREADS, g = g0 + (int)threadIdx.x;
+    constexpr int LIVE = bands_live<JC, BMX_LOWEST, I>::value;
+    const int g0 = (int)blockIdx.x * BANDS_THREADS, g = g0 + (int)threadIdx.x;
     if (g >= lanes) return;
     const int o = g / bins, k = g - o * bins;
     const float step = mu[o];
@@ -78,15 +52,15 @@ k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim
     float wr[JC], wi[JC], xr[JC], xi[JC];                                 // xr[q I + i] = x_i[m - q] behind frame m's shift
 #pragma unroll
     for (int j = 0; j < JC; j++) wr[j] = wi[j] = xr[j] = xi[j] = 0.f;
-    BMX_ENTRIES(j) {
+    BANDS_WALK(j, JC, J) {
         const int q = j / I, i = j - q * I;
         const size_t wrow = ((size_t)i * K + q) * bins;                   // weights [O][I][K][bins]
-        wr[j] = bmx_ld(wre + wbase + wrow, woff);
-        wi[j] = bmx_ld(wim + wbase + wrow, woff);
+        wr[j] = bands_ld(wre + wbase + wrow, woff);
+        wi[j] = bands_ld(wim + wbase + wrow, woff);
         if (j + I < J) {                                                  // x_i[-1 - q]: shifted to age q + 1 by the first frame
             const size_t hrow = ((size_t)i * H + q) * bins;               // history [I][H][bins]
-            xr[j] = bmx_ld(hin_re + hrow, koff);
-            xi[j] = bmx_ld(hin_im + hrow, koff);
+            xr[j] = bands_ld(hin_re + hrow, koff);
+            xi[j] = bands_ld(hin_im + hrow, koff);
         }
     }
     const size_t fb = (size_t)frames * bins;                              // a row of x, d, e, y
@@ -94,8 +68,8 @@ k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim
     float nxr[I], nxi[I], ndr = dre[row], ndi = dim[row];
 #pragma unroll
     for (int i = 0; i < I; i++) {
-        nxr[i] = bmx_ld(xre + (size_t)i * fb, koff);
-        nxi[i] = bmx_ld(xim + (size_t)i * fb, koff);
+        nxr[i] = bands_ld(xre + (size_t)i * fb, koff);
+        nxi[i] = bands_ld(xim + (size_t)i * fb, koff);
     }
     // frame 0 has arrived before the loop is entered: a wait for it at the loop's head would, from frame 1 on, wait for the
     // stores of the frame before as well
@@ -115,25 +89,20 @@ k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim
             const size_t next = (size_t)(m + 1) * bins;
 #pragma unroll
             for (int i = 0; i < I; i++) {
-                nxr[i] = bmx_ld(xre + (size_t)i * fb + next, koff);
-                nxi[i] = bmx_ld(xim + (size_t)i * fb + next, koff);
+                nxr[i] = bands_ld(xre + (size_t)i * fb + next, koff);
+                nxi[i] = bands_ld(xim + (size_t)i * fb + next, koff);
             }
             ndr = dre[at + bins];
             ndi = dim[at + bins];
         }
-        // every input's history moves on by one age, I registers, dead ones included: they take older frames that nothing reads
-#pragma unroll
-        for (int j = JC - 1; j >= I; j--) {
-            xr[j] = xr[j - I];
-            xi[j] = xi[j - I];
-        }
+        bands_shift<I>(xr, xi);                                           // every input's history moves on by one age
 #pragma unroll
         for (int i = 0; i < I; i++) {
             xr[i] = cxr[i];
             xi[i] = cxi[i];
         }
         float ar = 0.f, ai = 0.f, p = 0.f;                                // y and the joint power take their term of entry j
-        BMX_ENTRIES(j) {
+        BANDS_WALK(j, JC, J) {
             ar = __builtin_fmaf(wr[j], xr[j], ar);
             ar = __builtin_fmaf(-wi[j], xi[j], ar);
             ai = __builtin_fmaf(wr[j], xi[j], ai);
@@ -151,7 +120,7 @@ k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim
         if (step != 0.f) {
             const float den = p + delta;
             const float gr = (step * er) / den, gi = (step * ei) / den;
-            BMX_ENTRIES(j) {
+            BANDS_WALK(j, JC, J) {
                 wr[j] = __builtin_fmaf(gr, xr[j], wr[j]);
                 wr[j] = __builtin_fmaf(gi, xi[j], wr[j]);
                 wi[j] = __builtin_fmaf(gi, xr[j], wi[j]);
@@ -159,35 +128,30 @@ k_bands_matrix_nlms(const float *__restrict__ xre, const float *__restrict__ xim
             }
         }
     }
-    BMX_ENTRIES(j) {
+    BANDS_WALK(j, JC, J) {
         const int q = j / I, i = j - q * I;
         const size_t wrow = ((size_t)i * K + q) * bins;
-        bmx_st(wre + wbase + wrow, woff, wr[j]);
-        bmx_st(wim + wbase + wrow, woff, wi[j]);
+        bands_st(wre + wbase + wrow, woff, wr[j]);
+        bands_st(wim + wbase + wrow, woff, wi[j]);
     }
     if (o == 0) {                                                         // one writer per element of the other history buffer
-        BMX_ENTRIES(j) {
+        BANDS_WALK(j, JC, J) {
             if (j + I < J) {                                              // x_i[last - q] is the next call's x_i[-1 - q]
                 const int q = j / I, i = j - q * I;
                 const size_t hrow = ((size_t)i * H + q) * bins;
-                bmx_st(hout_re + hrow, koff, xr[j]);
-                bmx_st(hout_im + hrow, koff, xi[j]);
+                bands_st(hout_re + hrow, koff, xr[j]);
+                bands_st(hout_im + hrow, koff, xi[j]);
             }
         }
     }
 }
-#undef BMX_ENTRIES
-
-static int bmx_ceiling(int entries) { return entries <= 8 ? 8 : entries <= 16 ? 16 : entries <= 32 ? 32 : 64; }
+static int bmx_ceiling(int entries) { return bands_ceiling(entries, BMX_LOWEST, BMX_MAX_ENTRIES); }
 
 static int bmx_shape(const char *who, int inputs, int outputs, int bins, int taps)
 {
-    if (inputs < 1 || inputs > BMX_MAX_INPUTS || outputs < 1 || outputs > 4096 || bins < 1 || bins > 4097 || taps < 1 ||
-        inputs * taps > BMX_MAX_ENTRIES) {
-        llzs_set_error("%s: bad shape (inputs=%d outputs=%d bins=%d taps=%d)", who, inputs, outputs, bins, taps);
-        return LLZ_ERR_ARG;
-    }
-    return LLZ_OK;
+    const bands_dim dims[] = { { "inputs", inputs, BMX_MAX_INPUTS }, { "outputs", outputs, 4096 }, { "bins", bins, 4097 },
+                               { "taps", taps, BMX_MAX_ENTRIES } };
+    return bands_shape(who, dims, 4, inputs < 1 || taps < 1 || inputs * taps <= BMX_MAX_ENTRIES);
 }
 
 struct bmx_args {
@@ -203,7 +167,7 @@ struct bmx_args {
 
 template <int I, int JC, bool HAS_Y> static void bmx_launch_as(const bmx_args &a)
 {
-    const dim3 grid((unsigned)((a.lanes + BMX_THREADS - 1) / BMX_THREADS)), block(BMX_THREADS);
+    const dim3 grid(bands_grid(a.lanes)), block(BANDS_THREADS);
     hipLaunchKernelGGL((k_bands_matrix_nlms<I, JC, HAS_Y>), grid, block, 0, a.stream, a.xre, a.xim, a.dre, a.dim, a.ere, a.eim,
                        a.yre, a.yim, a.wre, a.wim, a.hin_re, a.hin_im, a.hout_re, a.hout_im, a.mu, a.delta, a.lanes, a.bins, a.taps,
                        a.frames);
@@ -263,16 +227,12 @@ extern "C" int llzs_matrix_bands_nlms_f32(const float *xre, const float *xim, co
 
 extern "C" int llzs_matrix_bands_nlms_plan(int inputs, int outputs, int bins, int taps, int *out)
 {
-    if (!out) {
-        llzs_set_error("bands_matrix_nlms_plan: no out");
-        return LLZ_ERR_ARG;
+    const char *who = "bands_matrix_nlms_plan";
+    int rc = bands_no_out(who, out);
+    if (rc == LLZ_OK) rc = bmx_shape(who, inputs, outputs, bins, taps);
+    if (rc == LLZ_OK) {
+        out[0] = inputs;
+        bands_plan_tail(out + 1, bmx_ceiling(inputs * taps), outputs * bins);
     }
-    const int rc = bmx_shape("bands_matrix_nlms_plan", inputs, outputs, bins, taps);
-    if (rc != LLZ_OK) return rc;
-    out[0] = inputs;
-    out[1] = bmx_ceiling(inputs * taps);
-    out[2] = BMX_THREADS;
-    out[3] = (outputs * bins + BMX_THREADS - 1) / BMX_THREADS;
-    out[4] = 1;
-    return LLZ_OK;
+    return rc;
 }

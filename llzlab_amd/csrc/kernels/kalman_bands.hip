@@ -1,10 +1,10 @@
 // kalman_bands.hip -- llz_kalman_bands_mc (include/llz_kalman_bands.h): the diagonal state-space (Kalman) adaptive filter of K
 // complex taps for every (channel, bin) of a batch of band signals, float32, one launch per call whatever its frames.
 //
-//   k_bands_kalman<KC, HAS_Y>   k_bands_nlms's plan (adapt_bands.hip, which is left as it is: its two helpers and its tap walk are
-//                      copied here): a lane owns one (channel, bin), lane g = c bins + k; a workgroup is one wave.  The lane loads
-//                      its K weights, K variances, its noise power and K - 1 history values, walks the call's frames with frame
-//                      m + 1 requested while frame m is worked on, and stores the state back behind the last frame.
+//   k_bands_kalman<KC, HAS_Y>   k_bands_nlms's plan (adapt_bands.hip) over bands_steps.hpp: a lane owns one (channel, bin), lane
+//                      g = c bins + k; a workgroup is one wave.  The lane loads its K weights, K variances, its noise power and
+//                      K - 1 history values, walks the call's frames with frame m + 1 requested while frame m is worked on, and
+//                      stores the state back behind the last frame.
 // Weights, history and variances are register arrays of KC = the tap ceiling of the instance (4, 8, 16, 32) entries, indexed by
 // the AGE q alone with constant indices: 5 KC + 1 registers of state per lane, 161 at the ceiling of 32 -- which is why there is
 // no instance of 64.  Taps q >= K do not exist (scalar guards, K is the launch's).
@@ -21,41 +21,16 @@
 //   w_re[q] = fma(k_im, x_im[q], fma(k_re, x_re[q], w_re[q]));    w_im[q] = fma(-k_re, x_im[q], fma(k_im, x_re[q], w_im[q]))
 //   c     = 1 - u[q] r;  c < 0: c = 0                              the clamp of the reciprocal form
 //   P[q]  = fma(omA2, fma(w_im[q], w_im[q], w_re[q] * w_re[q]), (A2 c) P[q])
-#include "common.hpp"
+#include "bands_steps.hpp"
 
 namespace {
-
-constexpr int KALMAN_THREADS = 64;      // a workgroup is one wave: no lane shares anything with another
-
-template <int KC> struct kalman_live {  // the taps an instance can take for granted: K > KC / 2 selects it (KC = 4: K >= 1)
-    static constexpr int value = KC == 4 ? 1 : KC / 2 + 1;
-};
-
-// element `off` (a byte offset below 2^32) behind a scalar base: one 32-bit register of address per lane for the whole state
-__device__ __forceinline__ float kalman_ld(const float *base, unsigned off)
-{
-    asm("" : "+s"(base));
-    return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off);
-}
-__device__ __forceinline__ void kalman_st(float *base, unsigned off, float v)
-{
-    asm("" : "+s"(base));
-    *reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off) = v;
-}
-
-// an unrolled loop over the ages leaves at the first tap that does not exist; the empty statement keeps the test a scalar branch
-#define KALMAN_TAPS(q)                                                                                                    \
-    _Pragma("unroll") for (int q = 0; q < KC; q++)                                                                        \
-        if (q >= LIVE && q >= K) break;                                                                                   \
-        else if (kalman_keep_branch(), true)
-__device__ __forceinline__ void kalman_keep_branch() { asm volatile(""); }
 
 struct kalman_consts {                  // formed once by the host layer, in float32
     float A2, omA2, lam, oml, delta;
 };
 
 template <int KC, bool HAS_Y>
-__global__ void __launch_bounds__(KALMAN_THREADS)
+__global__ void __launch_bounds__(BANDS_THREADS)
 k_bands_kalman(const float *__restrict__ xre, const float *__restrict__ xim, const float *__restrict__ dre,
                const float *__restrict__ dim, float *__restrict__ ere, float *__restrict__ eim, float *__restrict__ yre,
                float *__restrict__ yim, float *__restrict__ wre, float *__restrict__ wim, float *__restrict__ hre,
@@ -63,8 +38,8 @@ k_bands_kalman(const float *__restrict__ xre, const float *__restrict__ xim, con
                kalman_consts kc, int lanes, int bins, int K, int frames)
 {
 #pragma clang fp contract(off)
-    constexpr int LIVE = kalman_live<KC>::value;
-    const int g0 = (int)blockIdx.x * KALMAN_THREADS, g = g0 + (int)threadIdx.x;
+    constexpr int LIVE = bands_live<KC, 4, 1>::value;
+    const int g0 = (int)blockIdx.x * BANDS_THREADS, g = g0 + (int)threadIdx.x;
     if (g >= lanes) return;
     const int c = g / bins, k = g - c * bins;
     const bool on = adapt[c] != 0;
@@ -77,13 +52,13 @@ k_bands_kalman(const float *__restrict__ xre, const float *__restrict__ xim, con
     float wr[KC], wi[KC], xr[KC], xi[KC], P[KC];                          // xr[q] = x[m - q] behind frame m's shift
 #pragma unroll
     for (int q = 0; q < KC; q++) wr[q] = wi[q] = xr[q] = xi[q] = P[q] = 0.f;
-    KALMAN_TAPS(q) {
-        wr[q] = kalman_ld(wre + wbase + (size_t)q * bins, woff);
-        wi[q] = kalman_ld(wim + wbase + (size_t)q * bins, woff);
-        P[q] = kalman_ld(var + wbase + (size_t)q * bins, woff);
+    BANDS_WALK(q, KC, K) {
+        wr[q] = bands_ld(wre + wbase + (size_t)q * bins, woff);
+        wi[q] = bands_ld(wim + wbase + (size_t)q * bins, woff);
+        P[q] = bands_ld(var + wbase + (size_t)q * bins, woff);
         if (q + 1 < K) {                                                  // x[-1 - q]: shifted to age q + 1 by the first frame
-            xr[q] = kalman_ld(hre + hbase + (size_t)q * bins, hoff);
-            xi[q] = kalman_ld(him + hbase + (size_t)q * bins, hoff);
+            xr[q] = bands_ld(hre + hbase + (size_t)q * bins, hoff);
+            xi[q] = bands_ld(him + hbase + (size_t)q * bins, hoff);
         }
     }
     float psi = noise[g];
@@ -101,16 +76,11 @@ k_bands_kalman(const float *__restrict__ xre, const float *__restrict__ xim, con
             ndr = dre[o + bins];
             ndi = dim[o + bins];
         }
-        // the history moves on by one register, dead ones included (k_bands_nlms's plain chain of moves)
-#pragma unroll
-        for (int q = KC - 1; q > 0; q--) {
-            xr[q] = xr[q - 1];
-            xi[q] = xi[q - 1];
-        }
+        bands_shift<1>(xr, xi);
         xr[0] = cxr;
         xi[0] = cxi;
         float ar = 0.f, ai = 0.f;
-        KALMAN_TAPS(q) {
+        BANDS_WALK(q, KC, K) {
             ar = __builtin_fmaf(wr[q], xr[q], ar);
             ar = __builtin_fmaf(-wi[q], xi[q], ar);
             ai = __builtin_fmaf(wr[q], xi[q], ai);
@@ -126,10 +96,10 @@ k_bands_kalman(const float *__restrict__ xre, const float *__restrict__ xim, con
         if (on) {
             psi = __builtin_fmaf(kc.lam, psi, kc.oml * __builtin_fmaf(ei, ei, er * er));
             float s = psi + kc.delta;
-            KALMAN_TAPS(q) s = s + P[q] * __builtin_fmaf(xi[q], xi[q], xr[q] * xr[q]);
+            BANDS_WALK(q, KC, K) s = s + P[q] * __builtin_fmaf(xi[q], xi[q], xr[q] * xr[q]);
             const float r = 1.f / s;
             const float gr = er * r, gi = ei * r;
-            KALMAN_TAPS(q) {
+            BANDS_WALK(q, KC, K) {
                 const float u = P[q] * __builtin_fmaf(xi[q], xi[q], xr[q] * xr[q]);
                 const float kr = gr * P[q], ki = gi * P[q];
                 wr[q] = __builtin_fmaf(kr, xr[q], wr[q]);
@@ -142,34 +112,23 @@ k_bands_kalman(const float *__restrict__ xre, const float *__restrict__ xim, con
             }
         }
     }
-    KALMAN_TAPS(q) {
-        kalman_st(wre + wbase + (size_t)q * bins, woff, wr[q]);           // (a frozen channel's come back with the bits they had)
-        kalman_st(wim + wbase + (size_t)q * bins, woff, wi[q]);
-        kalman_st(var + wbase + (size_t)q * bins, woff, P[q]);
+    BANDS_WALK(q, KC, K) {
+        bands_st(wre + wbase + (size_t)q * bins, woff, wr[q]);           // (a frozen channel's come back with the bits they had)
+        bands_st(wim + wbase + (size_t)q * bins, woff, wi[q]);
+        bands_st(var + wbase + (size_t)q * bins, woff, P[q]);
         if (q + 1 < K) {                                                  // x[last - q] is the next call's x[-1 - q]
-            kalman_st(hre + hbase + (size_t)q * bins, hoff, xr[q]);
-            kalman_st(him + hbase + (size_t)q * bins, hoff, xi[q]);
+            bands_st(hre + hbase + (size_t)q * bins, hoff, xr[q]);
+            bands_st(him + hbase + (size_t)q * bins, hoff, xi[q]);
         }
     }
     noise[g] = psi;
 }
-#undef KALMAN_TAPS
-
-__global__ void __launch_bounds__(256) k_kalman_fill(float *__restrict__ dst, float v, size_t count)
-{
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) dst[i] = v;
-}
-
-static int kalman_ceiling(int taps) { return taps <= 4 ? 4 : taps <= 8 ? 8 : taps <= 16 ? 16 : 32; }
+static const int KALMAN_LOWEST = 4, KALMAN_HIGHEST = 32;                  // the tap ceilings of the instances
 
 static int kalman_shape(const char *who, int channels, int bins, int taps)
 {
-    if (channels < 1 || channels > 65535 || bins < 1 || bins > 4097 || taps < 1 || taps > 32) {
-        llzs_set_error("%s: bad shape (channels=%d bins=%d taps=%d)", who, channels, bins, taps);
-        return LLZ_ERR_ARG;
-    }
-    return LLZ_OK;
+    const bands_dim dims[] = { { "channels", channels, 65535 }, { "bins", bins, 4097 }, { "taps", taps, KALMAN_HIGHEST } };
+    return bands_shape(who, dims, 3);
 }
 
 } // namespace
@@ -189,7 +148,7 @@ extern "C" int llzs_kalman_bands_f32(const float *xre, const float *xim, const f
     if (rc != LLZ_OK) return rc;
     const kalman_consts kc = { consts[0], consts[1], consts[2], consts[3], consts[4] };
     const int lanes = channels * bins;                                     // at most 65535 x 4097
-    const dim3 grid((unsigned)((lanes + KALMAN_THREADS - 1) / KALMAN_THREADS)), block(KALMAN_THREADS);
+    const dim3 grid(bands_grid(lanes)), block(BANDS_THREADS);
 #define KALMAN_LAUNCH(KC)                                                                                                 \
     do {                                                                                                                  \
         if (yre)                                                                                                          \
@@ -199,7 +158,7 @@ extern "C" int llzs_kalman_bands_f32(const float *xre, const float *xim, const f
             hipLaunchKernelGGL((k_bands_kalman<KC, false>), grid, block, 0, as_stream(stream), xre, xim, dre, dim, ere, eim,    \
                                yre, yim, wre, wim, hre, him, var, noise, adapt, kc, lanes, bins, taps, frames);           \
     } while (0)
-    switch (kalman_ceiling(taps)) {
+    switch (bands_ceiling(taps, KALMAN_LOWEST, KALMAN_HIGHEST)) {
     case 4: KALMAN_LAUNCH(4); break;
     case 8: KALMAN_LAUNCH(8); break;
     case 16: KALMAN_LAUNCH(16); break;
@@ -210,30 +169,11 @@ extern "C" int llzs_kalman_bands_f32(const float *xre, const float *xim, const f
     return LLZ_OK;
 }
 
-extern "C" int llzs_kalman_bands_fill_f32(float *dst, float value, size_t count, void *stream)
-{
-    if (!dst || count < 1) {
-        llzs_set_error("kalman_bands_fill_f32: bad arguments");
-        return LLZ_ERR_ARG;
-    }
-    const size_t blocks = (count + 255) / 256;
-    hipLaunchKernelGGL(k_kalman_fill, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, as_stream(stream), dst,
-                       value, count);
-    LLZ_LAUNCH_CHECK("k_kalman_fill");
-    return LLZ_OK;
-}
-
 extern "C" int llzs_kalman_bands_plan(int channels, int bins, int taps, int *out)
 {
-    if (!out) {
-        llzs_set_error("kalman_bands_plan: no out");
-        return LLZ_ERR_ARG;
-    }
-    const int rc = kalman_shape("kalman_bands_plan", channels, bins, taps);
-    if (rc != LLZ_OK) return rc;
-    out[0] = kalman_ceiling(taps);
-    out[1] = KALMAN_THREADS;
-    out[2] = (channels * bins + KALMAN_THREADS - 1) / KALMAN_THREADS;
-    out[3] = 1;
-    return LLZ_OK;
+    const char *who = "kalman_bands_plan";
+    int rc = bands_no_out(who, out);
+    if (rc == LLZ_OK) rc = kalman_shape(who, channels, bins, taps);
+    if (rc == LLZ_OK) bands_plan_tail(out, bands_ceiling(taps, KALMAN_LOWEST, KALMAN_HIGHEST), channels * bins);
+    return rc;
 }

@@ -123,6 +123,26 @@ extern "C" int llzs_memset(void *dst, int value, size_t bytes, void *stream)
     return LLZ_OK;
 }
 
+// llzs_memset writes bytes; a float other than 0 takes a kernel (a grid-stride walk of at most 65536 workgroups)
+__global__ void __launch_bounds__(256) k_fill_f32(float *__restrict__ dst, float v, size_t count)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) dst[i] = v;
+}
+
+extern "C" int llzs_fill_f32(float *dst, float value, size_t count, void *stream)
+{
+    if (!dst || count < 1) {
+        llzs_set_error("fill_f32: bad arguments");
+        return LLZ_ERR_ARG;
+    }
+    const size_t blocks = (count + 255) / 256;
+    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, as_stream(stream), dst,
+                       value, count);
+    LLZ_LAUNCH_CHECK("k_fill_f32");
+    return LLZ_OK;
+}
+
 extern "C" int llzs_sync(void *stream)
 {
     LLZ_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));

@@ -1,11 +1,11 @@
 // suppress_bands.hip -- llz_suppress_bands_mc (include/llz_suppress_bands.h): the noise and residual-echo postfilter, a real gain
 // for every (channel, bin, frame) of a batch of band signals, float32, one launch per call whatever its frames.
 //
-//   k_bands_suppress<HAS_Y, HAS_G>   k_bands_kalman's plan (kalman_bands.hip, which is left as it is): a lane owns one (channel,
-//                      bin), lane g = c bins + k; a workgroup is one wave.  The lane loads its seven state values and its channel's
-//                      floor, leakage and flag, walks the call's frames with the next SUPPRESS_DEPTH frames requested while one is
-//                      worked on, and stores the state back behind the last frame.  HAS_Y: the echo estimate is read; HAS_G: the
-//                      gain is stored.
+//   k_bands_suppress<HAS_Y, HAS_G>   k_bands_kalman's plan (kalman_bands.hip) without taps, so of bands_steps.hpp it takes the
+//                      launch arithmetic alone: a lane owns one (channel, bin), lane g = c bins + k; a workgroup is one wave.
+//                      The lane loads its seven state values and its channel's floor, leakage and flag, walks the call's frames
+//                      with the next SUPPRESS_DEPTH frames requested while one is worked on, and stores the state back behind
+//                      the last frame.  HAS_Y: the echo estimate is read; HAS_G: the gain is stored.
 // The frame number n = count + m decides between the start-up and the running form and when the minimum's windows swap.  It is the
 // same for every lane, so the host passes it folded into [0, 2 W) -- n below W as it is, anything else as W + n % W -- and the
 // kernel counts it on in a scalar register: both decisions are scalar branches and no frame pays for a modulo.
@@ -15,11 +15,10 @@
 //   Q = (N + delta) + R;  rq = 1 / Q;  prio = fma(beta, Z rq, omb max(pe rq - 1, 0));  G = clamp(prio / (1 + prio), gmin, 1)
 //   o = G e;  Z = |o|^2
 // Two correctly rounded reciprocals per frame behind the start-up, three in the running form; every decision is a select.
-#include "common.hpp"
+#include "bands_steps.hpp"
 
 namespace {
 
-constexpr int SUPPRESS_THREADS = 64;    // a workgroup is one wave: no lane shares anything with another
 #ifndef SUPPRESS_DEPTH
 #define SUPPRESS_DEPTH 1                // frames in flight ahead of the one worked on: 2 gains nothing, 4 loses
 #endif
@@ -30,7 +29,7 @@ struct suppress_consts {                // formed once by the host layer, in flo
 };
 
 template <bool HAS_Y, bool HAS_G>
-__global__ void __launch_bounds__(SUPPRESS_THREADS)
+__global__ void __launch_bounds__(BANDS_THREADS)
 k_bands_suppress(const float *__restrict__ ere, const float *__restrict__ eim, const float *__restrict__ yre,
                  const float *__restrict__ yim, float *__restrict__ ore, float *__restrict__ oim, float *__restrict__ gout,
                  float *__restrict__ state, const float *__restrict__ floors, const float *__restrict__ leaks,
@@ -38,7 +37,7 @@ k_bands_suppress(const float *__restrict__ ere, const float *__restrict__ eim, c
 {
 #pragma clang fp contract(off)
     constexpr int D = SUPPRESS_DEPTH;
-    const int g = (int)blockIdx.x * SUPPRESS_THREADS + (int)threadIdx.x;
+    const int g = (int)blockIdx.x * BANDS_THREADS + (int)threadIdx.x;
     if (g >= lanes) return;
     const int c = g / bins, k = g - c * bins;
     const bool on = enable[c] != 0;
@@ -138,19 +137,10 @@ k_bands_suppress(const float *__restrict__ ere, const float *__restrict__ eim, c
     st[6 * (size_t)lanes] = Z;
 }
 
-__global__ void __launch_bounds__(256) k_suppress_fill(float *__restrict__ dst, float v, size_t count)
-{
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) dst[i] = v;
-}
-
 static int suppress_shape(const char *who, int channels, int bins)
 {
-    if (channels < 1 || channels > 65535 || bins < 1 || bins > 4097) {
-        llzs_set_error("%s: bad shape (channels=%d bins=%d)", who, channels, bins);
-        return LLZ_ERR_ARG;
-    }
-    return LLZ_OK;
+    const bands_dim dims[] = { { "channels", channels, 65535 }, { "bins", bins, 4097 } };
+    return bands_shape(who, dims, 2);
 }
 
 } // namespace
@@ -171,7 +161,7 @@ extern "C" int llzs_suppress_bands_f32(const float *ere, const float *eim, const
     const suppress_consts sc = { consts[0], consts[1], consts[2], consts[3], consts[4], consts[5], consts[6], consts[7],
                                  consts[8], consts[9], (unsigned)window };
     const int lanes = channels * bins;                                     // at most 65535 x 4097
-    const dim3 grid((unsigned)((lanes + SUPPRESS_THREADS - 1) / SUPPRESS_THREADS)), block(SUPPRESS_THREADS);
+    const dim3 grid(bands_grid(lanes)), block(BANDS_THREADS);
 #define SUPPRESS_LAUNCH(Y, G)                                                                                             \
     hipLaunchKernelGGL((k_bands_suppress<Y, G>), grid, block, 0, as_stream(stream), ere, eim, yre, yim, ore, oim, g, state, \
                        floors, leaks, enable, sc, lanes, bins, frames, (unsigned)n0)
@@ -184,30 +174,11 @@ extern "C" int llzs_suppress_bands_f32(const float *ere, const float *eim, const
     return LLZ_OK;
 }
 
-extern "C" int llzs_suppress_bands_fill_f32(float *dst, float value, size_t count, void *stream)
-{
-    if (!dst || count < 1) {
-        llzs_set_error("suppress_bands_fill_f32: bad arguments");
-        return LLZ_ERR_ARG;
-    }
-    const size_t blocks = (count + 255) / 256;
-    hipLaunchKernelGGL(k_suppress_fill, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, as_stream(stream), dst,
-                       value, count);
-    LLZ_LAUNCH_CHECK("k_suppress_fill");
-    return LLZ_OK;
-}
-
 extern "C" int llzs_suppress_bands_plan(int channels, int bins, int with_y, int *out)
 {
-    if (!out) {
-        llzs_set_error("suppress_bands_plan: no out");
-        return LLZ_ERR_ARG;
-    }
-    const int rc = suppress_shape("suppress_bands_plan", channels, bins);
-    if (rc != LLZ_OK) return rc;
-    out[0] = with_y != 0;
-    out[1] = SUPPRESS_THREADS;
-    out[2] = (channels * bins + SUPPRESS_THREADS - 1) / SUPPRESS_THREADS;
-    out[3] = 1;
-    return LLZ_OK;
+    const char *who = "suppress_bands_plan";
+    int rc = bands_no_out(who, out);
+    if (rc == LLZ_OK) rc = suppress_shape(who, channels, bins);
+    if (rc == LLZ_OK) bands_plan_tail(out, with_y != 0, channels * bins);
+    return rc;
 }

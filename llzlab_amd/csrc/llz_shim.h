@@ -22,6 +22,7 @@ int   llzs_h2d(void *dev_dst, const void *host_src, size_t bytes, void *stream);
 int   llzs_d2h(void *host_dst, const void *dev_src, size_t bytes, void *stream);   /* synchronous for the caller */
 int   llzs_d2d(void *dev_dst, const void *dev_src, size_t bytes, void *stream);    /* asynchronous on stream */
 int   llzs_memset(void *dev_dst, int value, size_t bytes, void *stream);
+int   llzs_fill_f32(float *dst, float value, size_t count, void *stream);          /* dst[i] = value, i < count, on stream */
 int   llzs_sync(void *stream);
 int   llzs_is_device_ptr(const void *p);
 
@@ -282,24 +283,22 @@ int llzs_matrix_bands_nlms_plan(int inputs, int outputs, int bins, int taps, int
  * (channel, bin), one launch for a call of `frames` >= 1 frames.  x, d, e, y, w and h as llzs_bands_nlms_f32 has them; var =
  * [channels][K][bins] state variances by age and noise = [channels][bins] noise powers, read, walked through the frames and
  * written back like w.  adapt = [channels] ints on the device, 0 = the channel is frozen.  consts = HOST {A2, 1 - A2, lam,
- * 1 - lam, delta}, the header's float32 constants.  fill: dst[i] = value, i < count (the variances at p0).  plan: out = {tap
- * ceiling of the instance, threads per workgroup, workgroups, launches}. */
+ * 1 - lam, delta}, the header's float32 constants.  plan: out = {tap ceiling of the instance, threads per workgroup, workgroups,
+ * launches}. */
 int llzs_kalman_bands_f32(const float *xre, const float *xim, const float *dre, const float *dim, float *ere, float *eim,
                           float *yre, float *yim, float *wre, float *wim, float *hre, float *him, float *var, float *noise,
                           const int *adapt, const float *consts, int channels, int bins, int taps, int frames, void *stream);
-int llzs_kalman_bands_fill_f32(float *dst, float value, size_t count, void *stream);
 int llzs_kalman_bands_plan(int channels, int bins, int taps, int *out);
 /* the noise and residual-echo postfilter per band (suppress_bands.hip; include/llz_suppress_bands.h), float32: a real gain for
  * every (channel, bin, frame), one launch for a call of `frames` >= 1 frames.  e, y (both NULL or both set), o and g (NULL: not
  * stored) = [channels][frames][bins].  state = [7][channels][bins], S Smin Stmp q N R Z, read, walked through the frames and
  * written back.  floors, leaks = [channels] floats and enable = [channels] ints on the device, 0 = the channel is passed through.
  * consts = HOST {omas, omaq, omad, omb, kt, aq, beta, rho, delta, t1}, the header's float32 constants; window = W.  n0 = the frame
- * count at the call's first frame folded into [0, 2 W): the count itself below W, else W + count % W.  fill: dst[i] = value,
- * i < count (q at 1).  plan: out = {with_y != 0, threads per workgroup, workgroups, launches}. */
+ * count at the call's first frame folded into [0, 2 W): the count itself below W, else W + count % W.  plan: out = {with_y != 0,
+ * threads per workgroup, workgroups, launches}. */
 int llzs_suppress_bands_f32(const float *ere, const float *eim, const float *yre, const float *yim, float *ore, float *oim,
                             float *g, float *state, const float *floors, const float *leaks, const int *enable,
                             const float *consts, int window, int channels, int bins, int frames, int n0, void *stream);
-int llzs_suppress_bands_fill_f32(float *dst, float value, size_t count, void *stream);
 int llzs_suppress_bands_plan(int channels, int bins, int with_y, int *out);
 /* hist_new[c][:] = last (flt_len-1) samples of concat(hist_old[c], in[c][0:n]) */
 int llzs_fir_tail_f32(const float *in, const float *hist_old, float *hist_new,

@@ -535,113 +535,149 @@ class AdaptMatrixMC:
     __del__ = close
 
 
-class AdaptBandsMC:
-    """band signals [channels, frames, bins] float32, re and im apart (StftMC's and PfbMC's layout): llz_adapt_bands_mc_*, a
-    normalised LMS filter of `taps` complex taps for every (channel, bin), updated frame by frame (include/llz_adapt_bands.h) --
-    the step between a bank's analysis of x and d and its synthesis of e in a subband echo canceller.  The weights start at zero;
-    mu is every channel's step size (0 = frozen), delta the regularisation of the power (None: 1e-3 x taps)."""
+class _BandsFilter:
+    """What the per-band classes share: the calls every llz_*_bands_*_mc family has (_P is its C prefix, _PLAN the length of
+    its plan), the typed pointers of process and the complex [..., taps, bins] weights of set_taps / get_taps.  Messages carry
+    the name of the class that was called."""
+    _P = None
+    _PLAN = 4
 
-    def __init__(self, channels, bins, taps, mu=0.5, delta=None, stream=None):
+    def _call(self, name, *args):
+        check(getattr(self._L, self._P + name)(self.handle, *args), self._P + name)
+
+    def _open(self, stream, *args):
         self._L = capi.lib()
-        delta = 1e-3 * taps if delta is None else delta
-        self.handle = check_handle(self._L.llz_adapt_bands_mc_init(channels, bins, taps, mu, delta), "llz_adapt_bands_mc_init")
-        self.channels, self.bins, self.taps = channels, bins, taps
+        self.handle = check_handle(getattr(self._L, self._P + "_init")(*args), self._P + "_init")
         if stream is not None:
             self.set_stream(stream)
 
     def set_stream(self, stream):
-        check(self._L.llz_adapt_bands_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_adapt_bands_mc_set_stream")
+        self._call("_set_stream", _stream_ptr(stream))
 
     def plan(self):
-        """(tap ceiling of the kernel instance, threads per workgroup, workgroups, launches per call)"""
-        out = (C.c_int * 4)()
-        check(self._L.llz_adapt_bands_mc_plan(self.handle, out), "llz_adapt_bands_mc_plan")
+        """the launch of a call: what names the kernel instance (see the class), then threads per workgroup, workgroups and
+        launches per call"""
+        out = (C.c_int * self._PLAN)()
+        self._call("_plan", out)
         return tuple(out)
+
+    def frames(self):
+        """frames taken since init or reset"""
+        n = C.c_longlong()
+        self._call("_frames", C.byref(n))
+        return n.value
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            getattr(self._L, self._P + "_uninit")(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+    def _frames_in(self, buf, rows):
+        return (buf.numel() if hasattr(buf, "numel") else buf.size) // (rows * self.bins)
+
+    def _process(self, frames, bufs):
+        """the call itself; bufs: (name, buffer or None, rows) in the C call's order, each [rows, frames, bins] float32"""
+        who = type(self).__name__ + ".process "
+        ptrs = [None if b is None else _typed(b, "float32", rows * frames * self.bins, who + name) for name, b, rows in bufs]
+        self._call("", *ptrs, frames)
+
+    def _process_xdey(self, x_re, x_im, d_re, d_im, e_re, e_im, y_re, y_im):
+        self._both_or_neither(y_re, y_im)
+        rows = self.channels
+        self._process(self._frames_in(x_re, rows), [("x_re", x_re, rows), ("x_im", x_im, rows), ("d_re", d_re, rows),
+                                                    ("d_im", d_im, rows), ("e_re", e_re, rows), ("e_im", e_im, rows),
+                                                    ("y_re", y_re, rows), ("y_im", y_im, rows)])
+        return e_re, e_im
+
+    def _both_or_neither(self, y_re, y_im):
+        if (y_re is None) != (y_im is None):
+            raise LlzError(f"{type(self).__name__}.process: y_re and y_im must both be given or both be None")
+
+    def _rows(self, a, what, must, lead=1):
+        """a when it is [lead dimensions..., taps, bins]; else the error '<class>.<what>: <must>, taps = .., bins = ..], got ..'"""
+        if a.ndim != lead + 2 or a.shape[lead:] != (self.taps, self.bins):
+            raise LlzError(f"{type(self).__name__}.{what}: {must}, taps = {self.taps}, bins = {self.bins}], got {a.shape}")
+        return a
+
+    def _set_taps(self, w, *where):
+        """complex weights up as a float32 re and im array; where: the C call's arguments between the handle and the arrays"""
+        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
+        self._call("_set_taps", *where, wre.ctypes.data, wim.ctypes.data)
+
+    def _get_taps(self, lead, *where):
+        """the weights [*lead, taps, bins] as complex64: the handle's own float32 values"""
+        wre = np.empty(tuple(max(n, 0) for n in lead) + (self.taps, self.bins), dtype=np.float32)
+        wim = np.empty_like(wre)
+        self._call("_get_taps", *where, wre.ctypes.data, wim.ctypes.data)
+        w = np.empty(wre.shape, dtype=np.complex64)
+        w.real, w.imag = wre, wim
+        return w
+
+    def _get_rows(self, name, first, count, *tail):
+        """float32 [count, *tail] of channels first .. first + count - 1 (count None: all from first) from the getter `name`"""
+        count = self.channels - first if count is None else count
+        out = np.empty((max(count, 0),) + tail, dtype=np.float32)
+        self._call(name, first, count, out.ctypes.data)
+        return out
+
+    def _set_rows(self, name, first, values, dtype):
+        v = np.ascontiguousarray(values, dtype=dtype)
+        self._call(name, first, v.shape[0], v.ctypes.data)
+
+
+class AdaptBandsMC(_BandsFilter):
+    """band signals [channels, frames, bins] float32, re and im apart (StftMC's and PfbMC's layout): llz_adapt_bands_mc_*, a
+    normalised LMS filter of `taps` complex taps for every (channel, bin), updated frame by frame (include/llz_adapt_bands.h) --
+    the step between a bank's analysis of x and d and its synthesis of e in a subband echo canceller.  The weights start at zero;
+    mu is every channel's step size (0 = frozen), delta the regularisation of the power (None: 1e-3 x taps).  plan() starts with
+    the tap ceiling of the kernel instance."""
+    _P = "llz_adapt_bands_mc"
+
+    def __init__(self, channels, bins, taps, mu=0.5, delta=None, stream=None):
+        self.channels, self.bins, self.taps = channels, bins, taps
+        self._open(stream, channels, bins, taps, mu, 1e-3 * taps if delta is None else delta)
 
     def process(self, x_re, x_im, d_re, d_im, e_re, e_im, y_re=None, y_im=None):
         """x (reference), d (desired), e (error, written), y (filter output, written when both are given): [channels, frames,
         bins] float32 each (torch device tensors or numpy), any number of frames, none included.  Returns (e_re, e_im)."""
-        if (y_re is None) != (y_im is None):
-            raise LlzError("AdaptBandsMC.process: y_re and y_im must both be given or both be None")
-        frames = (x_re.numel() if hasattr(x_re, "numel") else x_re.size) // (self.channels * self.bins)
-        count = self.channels * frames * self.bins
-        bufs = [("x_re", x_re), ("x_im", x_im), ("d_re", d_re), ("d_im", d_im), ("e_re", e_re), ("e_im", e_im)]
-        bufs += [("y_re", y_re), ("y_im", y_im)] if y_re is not None else []
-        ptrs = [_typed(b, "float32", count, "AdaptBandsMC.process " + name) for name, b in bufs]
-        ptrs += [None] * (8 - len(ptrs))
-        check(self._L.llz_adapt_bands_mc(self.handle, *ptrs, frames), "llz_adapt_bands_mc")
-        return e_re, e_im
+        return self._process_xdey(x_re, x_im, d_re, d_im, e_re, e_im, y_re, y_im)
 
     def set_step(self, first, mu):
         """step sizes of channels first .. first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
-        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float32)
-        check(self._L.llz_adapt_bands_mc_set_step(self.handle, first, mu.shape[0], mu.ctypes.data), "llz_adapt_bands_mc_set_step")
+        self._set_rows("_set_step", first, np.atleast_1d(mu), np.float32)
 
     def set_taps(self, first, w):
         """replace the weights of channels first .. first + count - 1; w: complex [count, taps, bins] (row q the taps of age q),
         or [taps, bins] for one channel; the history is kept"""
         w = np.asarray(w)
-        w = w[None] if w.ndim == 2 else w
-        if w.ndim != 3 or w.shape[1:] != (self.taps, self.bins):
-            raise LlzError(f"AdaptBandsMC.set_taps: w must be [count, taps = {self.taps}, bins = {self.bins}], got {w.shape}")
-        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
-        check(self._L.llz_adapt_bands_mc_set_taps(self.handle, first, w.shape[0], wre.ctypes.data, wim.ctypes.data),
-              "llz_adapt_bands_mc_set_taps")
+        w = self._rows(w[None] if w.ndim == 2 else w, "set_taps", "w must be [count")
+        self._set_taps(w, first, w.shape[0])
 
     def get_taps(self, first=0, count=None):
         """the weights of channels first .. first + count - 1 (default: all from first) as complex64 [count, taps, bins]: the
         handle's own float32 values"""
         count = self.channels - first if count is None else count
-        wre = np.empty((max(count, 0), self.taps, self.bins), dtype=np.float32)
-        wim = np.empty_like(wre)
-        check(self._L.llz_adapt_bands_mc_get_taps(self.handle, first, count, wre.ctypes.data, wim.ctypes.data),
-              "llz_adapt_bands_mc_get_taps")
-        w = np.empty(wre.shape, dtype=np.complex64)
-        w.real, w.imag = wre, wim
-        return w
+        return self._get_taps((count,), first, count)
 
     def reset(self, clear_taps=False):
-        check(self._L.llz_adapt_bands_mc_reset(self.handle, 1 if clear_taps else 0), "llz_adapt_bands_mc_reset")
-
-    def frames(self):
-        """frames taken since init or reset"""
-        n = C.c_longlong()
-        check(self._L.llz_adapt_bands_mc_frames(self.handle, C.byref(n)), "llz_adapt_bands_mc_frames")
-        return n.value
-
-    def close(self):
-        if getattr(self, "handle", 0):
-            self._L.llz_adapt_bands_mc_uninit(self.handle)
-            self.handle = 0
-
-    __del__ = close
+        self._call("_reset", 1 if clear_taps else 0)
 
 
-class AdaptBandsMatrixMC:
+class AdaptBandsMatrixMC(_BandsFilter):
     """band signals, float32, re and im apart (StftMC's and PfbMC's layout): llz_adapt_bands_matrix_mc_*, a normalised LMS filter
     of `inputs` references x `taps` complex taps for every (output, bin), normalised by the joint power of the references and
     updated frame by frame (include/llz_adapt_bands_matrix.h) -- AdaptBandsMC for a microphone that hears several loudspeakers;
     frozen (mu = 0) with set_taps, a filter-and-sum beamformer with a weight per bin.  inputs 1..8, inputs x taps <= 64.  The
     weights start at zero; mu is every output's step size (0 = frozen), delta the regularisation of the power (None: 1e-3 x
-    inputs x taps)."""
+    inputs x taps).  plan() starts with the inputs of the kernel instance and its entry ceiling."""
+    _P = "llz_adapt_bands_matrix_mc"
+    _PLAN = 5
 
     def __init__(self, inputs, outputs, bins, taps, mu=0.5, delta=None, stream=None):
-        self._L = capi.lib()
-        delta = 1e-3 * inputs * taps if delta is None else delta
-        self.handle = check_handle(self._L.llz_adapt_bands_matrix_mc_init(inputs, outputs, bins, taps, mu, delta),
-                                   "llz_adapt_bands_matrix_mc_init")
         self.inputs, self.outputs, self.bins, self.taps = inputs, outputs, bins, taps
-        if stream is not None:
-            self.set_stream(stream)
-
-    def set_stream(self, stream):
-        check(self._L.llz_adapt_bands_matrix_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_adapt_bands_matrix_mc_set_stream")
-
-    def plan(self):
-        """(inputs of the kernel instance, its entry ceiling, threads per workgroup, workgroups, launches per call)"""
-        out = (C.c_int * 5)()
-        check(self._L.llz_adapt_bands_matrix_mc_plan(self.handle, out), "llz_adapt_bands_matrix_mc_plan")
-        return tuple(out)
+        self._open(stream, inputs, outputs, bins, taps, mu, 1e-3 * inputs * taps if delta is None else delta)
 
     def process(self, x, d, e, y=None):
         """x (references), d (desired), e (error, written), y (filter output, written when given): each a pair (re, im) of
@@ -651,164 +687,82 @@ class AdaptBandsMatrixMC:
         for name, p, _ in pairs:
             if not isinstance(p, (tuple, list)) or len(p) != 2:
                 raise LlzError(f"AdaptBandsMatrixMC.process: {name} must be a pair (re, im)")
-        frames = (x[0].numel() if hasattr(x[0], "numel") else x[0].size) // (self.inputs * self.bins)
-        ptrs = [_typed(b, "float32", rows * frames * self.bins, f"AdaptBandsMatrixMC.process {name}_{part}")
-                for name, p, rows in pairs for part, b in zip(("re", "im"), p)]
-        ptrs += [None] * (8 - len(ptrs))
-        check(self._L.llz_adapt_bands_matrix_mc(self.handle, *ptrs, frames), "llz_adapt_bands_matrix_mc")
+        bufs = [(f"{name}_{part}", b, rows) for name, p, rows in pairs for part, b in zip(("re", "im"), p)]
+        self._process(self._frames_in(x[0], self.inputs), bufs + [("y", None, 0)] * (8 - len(bufs)))
         return e
 
     def set_step(self, out_first, mu):
         """step sizes of outputs out_first .. out_first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
-        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float32)
-        check(self._L.llz_adapt_bands_matrix_mc_set_step(self.handle, out_first, mu.shape[0], mu.ctypes.data),
-              "llz_adapt_bands_matrix_mc_set_step")
+        self._set_rows("_set_step", out_first, np.atleast_1d(mu), np.float32)
 
     def set_taps(self, out_first, w, in_first=0):
         """replace the weights of the paths (out_first .., in_first ..); w: complex [out_count, in_count, taps, bins] (row q the
         taps of age q); the history is kept"""
-        w = np.asarray(w)
-        if w.ndim != 4 or w.shape[2:] != (self.taps, self.bins):
-            raise LlzError(f"AdaptBandsMatrixMC.set_taps: w must be [out_count, in_count, taps = {self.taps}, bins = {self.bins}], "
-                           f"got {w.shape}")
-        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
-        check(self._L.llz_adapt_bands_matrix_mc_set_taps(self.handle, out_first, w.shape[0], in_first, w.shape[1], wre.ctypes.data,
-                                                         wim.ctypes.data), "llz_adapt_bands_matrix_mc_set_taps")
+        w = self._rows(np.asarray(w), "set_taps", "w must be [out_count, in_count", lead=2)
+        self._set_taps(w, out_first, w.shape[0], in_first, w.shape[1])
 
     def get_taps(self, out_first=0, out_count=None, in_first=0, in_count=None):
         """the weights of the paths (out_first .., in_first ..) (default: all from there) as complex64 [out_count, in_count, taps,
         bins]: the handle's own float32 values"""
         out_count = self.outputs - out_first if out_count is None else out_count
         in_count = self.inputs - in_first if in_count is None else in_count
-        wre = np.empty((max(out_count, 0), max(in_count, 0), self.taps, self.bins), dtype=np.float32)
-        wim = np.empty_like(wre)
-        check(self._L.llz_adapt_bands_matrix_mc_get_taps(self.handle, out_first, out_count, in_first, in_count, wre.ctypes.data,
-                                                         wim.ctypes.data), "llz_adapt_bands_matrix_mc_get_taps")
-        w = np.empty(wre.shape, dtype=np.complex64)
-        w.real, w.imag = wre, wim
-        return w
+        return self._get_taps((out_count, in_count), out_first, out_count, in_first, in_count)
 
     def reset(self, clear_taps=False):
-        check(self._L.llz_adapt_bands_matrix_mc_reset(self.handle, 1 if clear_taps else 0), "llz_adapt_bands_matrix_mc_reset")
-
-    def frames(self):
-        """frames taken since init or reset"""
-        n = C.c_longlong()
-        check(self._L.llz_adapt_bands_matrix_mc_frames(self.handle, C.byref(n)), "llz_adapt_bands_matrix_mc_frames")
-        return n.value
-
-    def close(self):
-        if getattr(self, "handle", 0):
-            self._L.llz_adapt_bands_matrix_mc_uninit(self.handle)
-            self.handle = 0
-
-    __del__ = close
+        self._call("_reset", 1 if clear_taps else 0)
 
 
-class KalmanBandsMC:
+class KalmanBandsMC(_BandsFilter):
     """band signals [channels, frames, bins] float32, re and im apart (AdaptBandsMC's layout): llz_kalman_bands_mc_*, the diagonal
     Kalman adaptive filter of `taps` (1..32) complex taps for every (channel, bin) (include/llz_kalman_bands.h) -- AdaptBandsMC's
     place in a subband echo canceller, with the step controlled by a variance per tap and a tracked noise power, so that it
     survives double-talk unattended.  a: the state transition in (0, 1]; lam: the smoothing of the noise power in [0, 1); p0: the
-    variances at init; delta: the regularisation.  Every channel adapts until set_adapt says otherwise."""
+    variances at init; delta: the regularisation.  Every channel adapts until set_adapt says otherwise.  plan() starts with the
+    tap ceiling of the kernel instance."""
+    _P = "llz_kalman_bands_mc"
 
     def __init__(self, channels, bins, taps, a=0.999, lam=0.9, p0=1.0, delta=1e-3, stream=None):
-        self._L = capi.lib()
-        self.handle = check_handle(self._L.llz_kalman_bands_mc_init(channels, bins, taps, a, lam, p0, delta),
-                                   "llz_kalman_bands_mc_init")
         self.channels, self.bins, self.taps = channels, bins, taps
-        if stream is not None:
-            self.set_stream(stream)
-
-    def set_stream(self, stream):
-        check(self._L.llz_kalman_bands_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_kalman_bands_mc_set_stream")
-
-    def plan(self):
-        """(tap ceiling of the kernel instance, threads per workgroup, workgroups, launches per call)"""
-        out = (C.c_int * 4)()
-        check(self._L.llz_kalman_bands_mc_plan(self.handle, out), "llz_kalman_bands_mc_plan")
-        return tuple(out)
+        self._open(stream, channels, bins, taps, a, lam, p0, delta)
 
     def process(self, x_re, x_im, d_re, d_im, e_re, e_im, y_re=None, y_im=None):
         """x (reference), d (desired), e (error, written), y (filter output, written when both are given): [channels, frames,
         bins] float32 each (torch device tensors or numpy), any number of frames, none included.  Returns (e_re, e_im)."""
-        if (y_re is None) != (y_im is None):
-            raise LlzError("KalmanBandsMC.process: y_re and y_im must both be given or both be None")
-        frames = (x_re.numel() if hasattr(x_re, "numel") else x_re.size) // (self.channels * self.bins)
-        count = self.channels * frames * self.bins
-        bufs = [("x_re", x_re), ("x_im", x_im), ("d_re", d_re), ("d_im", d_im), ("e_re", e_re), ("e_im", e_im)]
-        bufs += [("y_re", y_re), ("y_im", y_im)] if y_re is not None else []
-        ptrs = [_typed(b, "float32", count, "KalmanBandsMC.process " + name) for name, b in bufs]
-        ptrs += [None] * (8 - len(ptrs))
-        check(self._L.llz_kalman_bands_mc(self.handle, *ptrs, frames), "llz_kalman_bands_mc")
-        return e_re, e_im
+        return self._process_xdey(x_re, x_im, d_re, d_im, e_re, e_im, y_re, y_im)
 
     def set_adapt(self, first, on):
         """whether channels first .. first + count - 1 adapt: [count] truth values (or one), False = frozen"""
-        on = np.ascontiguousarray(np.atleast_1d(on) != 0, dtype=np.int32)
-        check(self._L.llz_kalman_bands_mc_set_adapt(self.handle, first, on.shape[0], on.ctypes.data), "llz_kalman_bands_mc_set_adapt")
+        self._set_rows("_set_adapt", first, np.atleast_1d(on) != 0, np.int32)
 
-    def _rows(self, a, what):
-        a = a[None] if a.ndim == 2 else a
-        if a.ndim != 3 or a.shape[1:] != (self.taps, self.bins):
-            raise LlzError(f"KalmanBandsMC.{what}: must be [count, taps = {self.taps}, bins = {self.bins}], got {a.shape}")
-        return a
+    def _rows3(self, a, what):
+        return self._rows(a[None] if a.ndim == 2 else a, what, "must be [count")
 
     def set_taps(self, first, w):
         """replace the weights of channels first .. first + count - 1; w: complex [count, taps, bins] (row q the taps of age q),
         or [taps, bins] for one channel; history, variances and noise powers are kept"""
-        w = self._rows(np.asarray(w), "set_taps")
-        wre, wim = np.ascontiguousarray(w.real, dtype=np.float32), np.ascontiguousarray(w.imag, dtype=np.float32)
-        check(self._L.llz_kalman_bands_mc_set_taps(self.handle, first, w.shape[0], wre.ctypes.data, wim.ctypes.data),
-              "llz_kalman_bands_mc_set_taps")
+        w = self._rows3(np.asarray(w), "set_taps")
+        self._set_taps(w, first, w.shape[0])
 
     def get_taps(self, first=0, count=None):
         """the weights of channels first .. first + count - 1 (default: all from first) as complex64 [count, taps, bins]"""
         count = self.channels - first if count is None else count
-        wre = np.empty((max(count, 0), self.taps, self.bins), dtype=np.float32)
-        wim = np.empty_like(wre)
-        check(self._L.llz_kalman_bands_mc_get_taps(self.handle, first, count, wre.ctypes.data, wim.ctypes.data),
-              "llz_kalman_bands_mc_get_taps")
-        w = np.empty(wre.shape, dtype=np.complex64)
-        w.real, w.imag = wre, wim
-        return w
+        return self._get_taps((count,), first, count)
 
     def set_variance(self, first, p):
         """replace the variances of channels first .. first + count - 1; p: real [count, taps, bins] or [taps, bins], finite and
         >= 0 -- raising them re-opens adaptation after a known path change"""
-        p = np.ascontiguousarray(self._rows(np.asarray(p), "set_variance"), dtype=np.float32)
-        check(self._L.llz_kalman_bands_mc_set_variance(self.handle, first, p.shape[0], p.ctypes.data),
-              "llz_kalman_bands_mc_set_variance")
+        self._set_rows("_set_variance", first, self._rows3(np.asarray(p), "set_variance"), np.float32)
 
     def get_variance(self, first=0, count=None):
         """the variances of channels first .. first + count - 1 as float32 [count, taps, bins]"""
-        count = self.channels - first if count is None else count
-        p = np.empty((max(count, 0), self.taps, self.bins), dtype=np.float32)
-        check(self._L.llz_kalman_bands_mc_get_variance(self.handle, first, count, p.ctypes.data), "llz_kalman_bands_mc_get_variance")
-        return p
+        return self._get_rows("_get_variance", first, count, self.taps, self.bins)
 
     def get_noise(self, first=0, count=None):
         """the noise powers of channels first .. first + count - 1 as float32 [count, bins]"""
-        count = self.channels - first if count is None else count
-        psi = np.empty((max(count, 0), self.bins), dtype=np.float32)
-        check(self._L.llz_kalman_bands_mc_get_noise(self.handle, first, count, psi.ctypes.data), "llz_kalman_bands_mc_get_noise")
-        return psi
+        return self._get_rows("_get_noise", first, count, self.bins)
 
     def reset(self, clear=False):
-        check(self._L.llz_kalman_bands_mc_reset(self.handle, 1 if clear else 0), "llz_kalman_bands_mc_reset")
-
-    def frames(self):
-        """frames taken since init or reset"""
-        n = C.c_longlong()
-        check(self._L.llz_kalman_bands_mc_frames(self.handle, C.byref(n)), "llz_kalman_bands_mc_frames")
-        return n.value
-
-    def close(self):
-        if getattr(self, "handle", 0):
-            self._L.llz_kalman_bands_mc_uninit(self.handle)
-            self.handle = 0
-
-    __del__ = close
+        self._call("_reset", 1 if clear else 0)
 
 
 class SuppressCfg(C.Structure):
@@ -817,90 +771,57 @@ class SuppressCfg(C.Structure):
                 ("t1", C.c_float), ("beta", C.c_float), ("rho", C.c_float), ("delta", C.c_float)]
 
 
-class SuppressBandsMC:
+class SuppressBandsMC(_BandsFilter):
     """band signals [channels, frames, bins] float32, re and im apart (KalmanBandsMC's layout): llz_suppress_bands_mc_*, the noise
     and residual-echo postfilter behind a subband echo canceller (include/llz_suppress_bands.h) -- a real gain per (channel, bin,
     frame) from a tracked noise power (MCRA), a decision-directed Wiener rule and a peak-hold residual-echo estimate eta |y|^2.
     It takes KalmanBandsMC's e and, on request, y; without y it is a noise suppressor for any band signal.  window: frames of
     the minimum search and of the start-up, which is taken as noise only; the other parameters are the header's.  Every channel
-    is enabled, with a floor of 0.1 and no leakage, until the setters say otherwise."""
+    is enabled, with a floor of 0.1 and no leakage, until the setters say otherwise.  plan() starts with 1 when the last call
+    took y, else 0."""
+    _P = "llz_suppress_bands_mc"
     STATES = ("S", "Smin", "Stmp", "q", "N", "R", "Z")
 
     def __init__(self, channels, bins, window=128, as_=0.8, aq=0.2, ad=0.95, t0=2.0, t1=5.0, beta=0.98, rho=0.6, delta=1e-6,
                  stream=None):
-        self._L = capi.lib()
         cfg = SuppressCfg()
-        self._L.llz_suppress_bands_mc_default_cfg(C.byref(cfg))
+        capi.lib().llz_suppress_bands_mc_default_cfg(C.byref(cfg))
         cfg.window, cfg.as_, cfg.aq, cfg.ad, cfg.t0, cfg.t1, cfg.beta, cfg.rho, cfg.delta = window, as_, aq, ad, t0, t1, beta, rho, delta
-        self.handle = check_handle(self._L.llz_suppress_bands_mc_init(channels, bins, C.byref(cfg)), "llz_suppress_bands_mc_init")
         self.channels, self.bins, self.window = channels, bins, window
-        if stream is not None:
-            self.set_stream(stream)
-
-    def set_stream(self, stream):
-        check(self._L.llz_suppress_bands_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_suppress_bands_mc_set_stream")
-
-    def plan(self):
-        """(1 when the last call took y else 0, threads per workgroup, workgroups, launches per call)"""
-        out = (C.c_int * 4)()
-        check(self._L.llz_suppress_bands_mc_plan(self.handle, out), "llz_suppress_bands_mc_plan")
-        return tuple(out)
+        self._open(stream, channels, bins, C.byref(cfg))
 
     def process(self, e_re, e_im, o_re, o_im, y_re=None, y_im=None, g=None):
         """e (the canceller's error), o (written), y (its echo estimate, read when both are given), g (the gain, written when
         given): [channels, frames, bins] float32 each (torch device tensors or numpy), any number of frames, none included.
         Returns (o_re, o_im)."""
-        if (y_re is None) != (y_im is None):
-            raise LlzError("SuppressBandsMC.process: y_re and y_im must both be given or both be None")
-        frames = (e_re.numel() if hasattr(e_re, "numel") else e_re.size) // (self.channels * self.bins)
-        count = self.channels * frames * self.bins
+        self._both_or_neither(y_re, y_im)
         bufs = [("e_re", e_re), ("e_im", e_im), ("y_re", y_re), ("y_im", y_im), ("o_re", o_re), ("o_im", o_im), ("g", g)]
-        ptrs = [None if b is None else _typed(b, "float32", count, "SuppressBandsMC.process " + name) for name, b in bufs]
-        check(self._L.llz_suppress_bands_mc(self.handle, *ptrs, frames), "llz_suppress_bands_mc")
+        self._process(self._frames_in(e_re, self.channels), [(name, b, self.channels) for name, b in bufs])
         return o_re, o_im
-
-    def _per_channel(self, name, first, values, dtype):
-        v = np.ascontiguousarray(np.atleast_1d(values), dtype=dtype)
-        check(getattr(self._L, "llz_suppress_bands_mc_" + name)(self.handle, first, v.shape[0], v.ctypes.data),
-              "llz_suppress_bands_mc_" + name)
 
     def set_floor(self, first, gmin):
         """the gain floors of channels first .. first + count - 1: [count] values (or one) in [0, 1]"""
-        self._per_channel("set_floor", first, gmin, np.float32)
+        self._set_rows("_set_floor", first, np.atleast_1d(gmin), np.float32)
 
     def set_leak(self, first, eta):
         """the echo leakages of channels first .. first + count - 1: [count] values (or one), finite and >= 0"""
-        self._per_channel("set_leak", first, eta, np.float32)
+        self._set_rows("_set_leak", first, np.atleast_1d(eta), np.float32)
 
     def set_enable(self, first, on):
         """whether channels first .. first + count - 1 are processed: [count] truth values (or one), False = passed through"""
-        self._per_channel("set_enable", first, np.atleast_1d(on) != 0, np.int32)
+        self._set_rows("_set_enable", first, np.atleast_1d(on) != 0, np.int32)
 
     def get_state(self, which, first=0, count=None):
         """state value `which` (0..6 or one of STATES) of channels first .. first + count - 1 as float32 [count, bins]"""
         which = self.STATES.index(which) if isinstance(which, str) else which
         count = self.channels - first if count is None else count
         out = np.empty((max(count, 0), self.bins), dtype=np.float32)
-        check(self._L.llz_suppress_bands_mc_get_state(self.handle, which, first, count, out.ctypes.data),
-              "llz_suppress_bands_mc_get_state")
+        self._call("_get_state", which, first, count, out.ctypes.data)
         return out
 
     def reset(self):
         """state and frame count back to init; flags, floors and leakages are kept"""
-        check(self._L.llz_suppress_bands_mc_reset(self.handle), "llz_suppress_bands_mc_reset")
-
-    def frames(self):
-        """frames taken since init or reset"""
-        n = C.c_longlong()
-        check(self._L.llz_suppress_bands_mc_frames(self.handle, C.byref(n)), "llz_suppress_bands_mc_frames")
-        return n.value
-
-    def close(self):
-        if getattr(self, "handle", 0):
-            self._L.llz_suppress_bands_mc_uninit(self.handle)
-            self.handle = 0
-
-    __del__ = close
+        self._call("_reset")
 
 
 # ------------------------------------------------------------------------------------------ IIR

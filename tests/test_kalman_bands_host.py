@@ -37,7 +37,7 @@ PROTOTYPES = {
     P + "_set_stream": r"\bint\s+%s\s*\(\s*unsigned long \w+,\s*void \*\w+\s*\)",
 }
 NEW = list(PROTOTYPES)
-SHIMS = {"llzs_kalman_bands_f32", "llzs_kalman_bands_fill_f32", "llzs_kalman_bands_plan"}
+SHIMS = {"llzs_kalman_bands_f32", "llzs_kalman_bands_plan"}
 GOOD = (2, 33, 8, 0.999, 0.9, 1.0, 1e-3)           # channels, bins, taps, a, lam, p0, delta
 
 

@@ -37,7 +37,7 @@ PROTOTYPES = {
     P + "_set_stream": r"\bint\s+%s\s*\(\s*unsigned long \w+,\s*void \*\w+\s*\)",
 }
 NEW = list(PROTOTYPES)
-SHIMS = {"llzs_suppress_bands_f32", "llzs_suppress_bands_fill_f32", "llzs_suppress_bands_plan"}
+SHIMS = {"llzs_suppress_bands_f32", "llzs_suppress_bands_plan"}
 FIELDS = ("window", "as_", "aq", "ad", "t0", "t1", "beta", "rho", "delta")
 
 
