@@ -227,6 +227,20 @@ def lib():
     sig("llz_kalman_bands_mc_frames", i, ul, C.POINTER(C.c_longlong))
     sig("llz_kalman_bands_mc_plan", i, ul, C.POINTER(C.c_int))
     sig("llz_kalman_bands_mc_set_stream", i, ul, vp)
+    # llz_kalman_bands_matrix.h
+    sig("llz_kalman_bands_matrix_mc_init", ul, i, i, i, i, C.c_float, C.c_float, C.c_float, C.c_float)
+    sig("llz_kalman_bands_matrix_mc_uninit", None, ul)
+    sig("llz_kalman_bands_matrix_mc", i, ul, vp, vp, vp, vp, vp, vp, vp, vp, i)
+    sig("llz_kalman_bands_matrix_mc_set_adapt", i, ul, i, i, vp)
+    sig("llz_kalman_bands_matrix_mc_set_taps", i, ul, i, i, i, i, vp, vp)
+    sig("llz_kalman_bands_matrix_mc_get_taps", i, ul, i, i, i, i, vp, vp)
+    sig("llz_kalman_bands_matrix_mc_set_variance", i, ul, i, i, i, i, vp)
+    sig("llz_kalman_bands_matrix_mc_get_variance", i, ul, i, i, i, i, vp)
+    sig("llz_kalman_bands_matrix_mc_get_noise", i, ul, i, i, vp)
+    sig("llz_kalman_bands_matrix_mc_reset", i, ul, i)
+    sig("llz_kalman_bands_matrix_mc_frames", i, ul, C.POINTER(C.c_longlong))
+    sig("llz_kalman_bands_matrix_mc_plan", i, ul, C.POINTER(C.c_int))
+    sig("llz_kalman_bands_matrix_mc_set_stream", i, ul, vp)
     # llz_suppress_bands.h
     sig("llz_suppress_bands_mc_default_cfg", None, vp)
     sig("llz_suppress_bands_mc_init", ul, i, i, vp)

@@ -1,6 +1,7 @@
-/* llz_bands_core.c -- what the four per-band handles share (llz_adapt_bands_host.c: llz_adapt_bands_mc;
+/* llz_bands_core.c -- what the five per-band handles share (llz_adapt_bands_host.c: llz_adapt_bands_mc;
  * llz_adapt_bands_matrix_host.c: llz_adapt_bands_matrix_mc; llz_kalman_bands_host.c: llz_kalman_bands_mc;
- * llz_suppress_bands_host.c: llz_suppress_bands_mc), declared in llz_host.h: the refusal of a count outside its range, the
+ * llz_kalman_bands_matrix_host.c: llz_kalman_bands_matrix_mc; llz_suppress_bands_host.c: llz_suppress_bands_mc), declared in
+ * llz_host.h: the refusal of a count outside its range, the
  * refusals of a call behind its handle, the staged call around the one launch, the frame counter, the range check and the copies
  * of the set_* and get_* calls, the zeroing of a re / im pair and the upload of a flag array.  Every message here exists once.
  * The state itself, the init with its allocation message and the arguments of the launch are each handle's own. */

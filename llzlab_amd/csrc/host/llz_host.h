@@ -21,7 +21,7 @@ enum {
     LLZ_TAG_FIRX = 0x4c5a4658, LLZ_TAG_ADPT = 0x4c5a4144, LLZ_TAG_ADPX = 0x4c5a4158,
     LLZ_TAG_ASRC = 0x4c5a5352, LLZ_TAG_PFB = 0x4c5a5046, LLZ_TAG_ADPB = 0x4c5a4142,
     LLZ_TAG_ADBX = 0x4c5a4258, LLZ_TAG_KALB = 0x4c5a4b42,
-    LLZ_TAG_SUPB = 0x4c5a5342
+    LLZ_TAG_SUPB = 0x4c5a5342, LLZ_TAG_KALX = 0x4c5a4b58
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))
@@ -240,7 +240,7 @@ int  llz_adapt_io_end(llz_adapt_io_t *io, int rc, void *stream);
 void llz_adapt_io_release(llz_adapt_io_t *io);
 
 /* ---- llz_bands_core.c: what the per-band handles share (llz_adapt_bands_mc, llz_adapt_bands_matrix_mc, llz_kalman_bands_mc,
- * llz_suppress_bands_mc) ---- */
+ * llz_kalman_bands_matrix_mc, llz_suppress_bands_mc) ---- */
 
 #define LLZ_BANDS_MAX_BINS 4097
 #define LLZ_BANDS_MAX_CHANNELS 65535

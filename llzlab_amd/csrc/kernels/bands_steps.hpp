@@ -9,6 +9,8 @@
 // What is NOT here, because sharing it changes the instruction text of an instance (DESIGN.md, K4j-K4m "Shared code"): the output
 // sum y = sum w[q] x[q], which as an inline function reorders its two fma chains in several instances of k_bands_kalman, and the
 // epilogue's state store, which split per array reorders the stores and moves register counts.  Both stay written out.
+//
+// A fifth kernel stands on the same pieces: kalman_bands_matrix.hip (K4n, k_bands_matrix_kalman), K4l's recursion on K4k's plan.
 #pragma once
 #include <stdio.h>
 #include "common.hpp"

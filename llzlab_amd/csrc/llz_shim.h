@@ -289,6 +289,17 @@ int llzs_kalman_bands_f32(const float *xre, const float *xim, const float *dre, 
                           float *yre, float *yim, float *wre, float *wim, float *hre, float *him, float *var, float *noise,
                           const int *adapt, const float *consts, int channels, int bins, int taps, int frames, void *stream);
 int llzs_kalman_bands_plan(int channels, int bins, int taps, int *out);
+/* its multi-reference form (kalman_bands_matrix.hip; include/llz_kalman_bands_matrix.h): `inputs` = I references, 1..8, of `taps`
+ * = K complex taps each, I K <= 32, for every (output, bin), one launch for a call of `frames` >= 1 frames.  x, d, e, y, w, hin
+ * and hout -- ANOTHER buffer -- as llzs_matrix_bands_nlms_f32 has them; var = [outputs][inputs][K][bins] state variances and noise
+ * = [outputs][bins] noise powers, read, walked through the frames and written back like w.  adapt = [outputs] ints on the device,
+ * 0 = the output is frozen (the history moves on all the same).  consts as llzs_kalman_bands_f32's.  plan: out = {inputs of the
+ * instance, entry ceiling of the instance, threads per workgroup, workgroups, launches}. */
+int llzs_mkalman_bands_f32(const float *xre, const float *xim, const float *dre, const float *dim, float *ere, float *eim,
+                           float *yre, float *yim, float *wre, float *wim, const float *hin_re, const float *hin_im,
+                           float *hout_re, float *hout_im, float *var, float *noise, const int *adapt, const float *consts,
+                           int inputs, int outputs, int bins, int taps, int frames, void *stream);
+int llzs_mkalman_bands_plan(int inputs, int outputs, int bins, int taps, int *out);
 /* the noise and residual-echo postfilter per band (suppress_bands.hip; include/llz_suppress_bands.h), float32: a real gain for
  * every (channel, bin, frame), one launch for a call of `frames` >= 1 frames.  e, y (both NULL or both set), o and g (NULL: not
  * stored) = [channels][frames][bins].  state = [7][channels][bins], S Smin Stmp q N R Z, read, walked through the frames and

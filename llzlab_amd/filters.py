@@ -591,6 +591,16 @@ class _BandsFilter:
                                                     ("y_re", y_re, rows), ("y_im", y_im, rows)])
         return e_re, e_im
 
+    def _process_pairs(self, x, d, e, y):
+        """the call of the multi-reference classes: x [inputs, ...], d, e and an optional y [outputs, ...], each a pair (re, im)"""
+        pairs = [("x", x, self.inputs), ("d", d, self.outputs), ("e", e, self.outputs)] + ([("y", y, self.outputs)] if y is not None else [])
+        for name, p, _ in pairs:
+            if not isinstance(p, (tuple, list)) or len(p) != 2:
+                raise LlzError(f"{type(self).__name__}.process: {name} must be a pair (re, im)")
+        bufs = [(f"{name}_{part}", b, rows) for name, p, rows in pairs for part, b in zip(("re", "im"), p)]
+        self._process(self._frames_in(x[0], self.inputs), bufs + [("y", None, 0)] * (8 - len(bufs)))
+        return e
+
     def _both_or_neither(self, y_re, y_im):
         if (y_re is None) != (y_im is None):
             raise LlzError(f"{type(self).__name__}.process: y_re and y_im must both be given or both be None")
@@ -683,13 +693,7 @@ class AdaptBandsMatrixMC(_BandsFilter):
         """x (references), d (desired), e (error, written), y (filter output, written when given): each a pair (re, im) of
         float32 buffers (torch device tensors or numpy, in any mix), x [inputs, frames, bins], the others [outputs, frames,
         bins]; any number of frames, none included.  Returns e."""
-        pairs = [("x", x, self.inputs), ("d", d, self.outputs), ("e", e, self.outputs)] + ([("y", y, self.outputs)] if y is not None else [])
-        for name, p, _ in pairs:
-            if not isinstance(p, (tuple, list)) or len(p) != 2:
-                raise LlzError(f"AdaptBandsMatrixMC.process: {name} must be a pair (re, im)")
-        bufs = [(f"{name}_{part}", b, rows) for name, p, rows in pairs for part, b in zip(("re", "im"), p)]
-        self._process(self._frames_in(x[0], self.inputs), bufs + [("y", None, 0)] * (8 - len(bufs)))
-        return e
+        return self._process_pairs(x, d, e, y)
 
     def set_step(self, out_first, mu):
         """step sizes of outputs out_first .. out_first + count - 1: [count] values in [0, 2] (or one number), 0 = frozen"""
@@ -760,6 +764,71 @@ class KalmanBandsMC(_BandsFilter):
     def get_noise(self, first=0, count=None):
         """the noise powers of channels first .. first + count - 1 as float32 [count, bins]"""
         return self._get_rows("_get_noise", first, count, self.bins)
+
+    def reset(self, clear=False):
+        self._call("_reset", 1 if clear else 0)
+
+
+class KalmanBandsMatrixMC(_BandsFilter):
+    """band signals, float32, re and im apart (AdaptBandsMatrixMC's layout): llz_kalman_bands_matrix_mc_*, the diagonal Kalman
+    adaptive filter of `inputs` references x `taps` complex taps for every (output, bin) (include/llz_kalman_bands_matrix.h) --
+    KalmanBandsMC for a microphone that hears several loudspeakers: a variance per path and tap and one tracked noise power per
+    (output, bin), so that it survives double-talk unattended.  inputs 1..8, inputs x taps <= 32.  a, lam, p0 and delta are
+    KalmanBandsMC's.  Every output adapts until set_adapt says otherwise.  plan() starts with the inputs of the kernel instance
+    and its entry ceiling."""
+    _P = "llz_kalman_bands_matrix_mc"
+    _PLAN = 5
+
+    def __init__(self, inputs, outputs, bins, taps, a=0.999, lam=0.9, p0=1.0, delta=1e-3, stream=None):
+        self.inputs, self.outputs, self.bins, self.taps = inputs, outputs, bins, taps
+        self._open(stream, inputs, outputs, bins, taps, a, lam, p0, delta)
+
+    def process(self, x, d, e, y=None):
+        """x (references), d (desired), e (error, written), y (filter output, written when given): each a pair (re, im) of
+        float32 buffers (torch device tensors or numpy, in any mix), x [inputs, frames, bins], the others [outputs, frames,
+        bins]; any number of frames, none included.  Returns e."""
+        return self._process_pairs(x, d, e, y)
+
+    def set_adapt(self, out_first, on):
+        """whether outputs out_first .. out_first + count - 1 adapt: [count] truth values (or one), False = frozen"""
+        self._set_rows("_set_adapt", out_first, np.atleast_1d(on) != 0, np.int32)
+
+    def _counts(self, out_first, out_count, in_first, in_count):
+        return (self.outputs - out_first if out_count is None else out_count,
+                self.inputs - in_first if in_count is None else in_count)
+
+    def set_taps(self, out_first, w, in_first=0):
+        """replace the weights of the paths (out_first .., in_first ..); w: complex [out_count, in_count, taps, bins] (row q the
+        taps of age q); history, variances and noise powers are kept"""
+        w = self._rows(np.asarray(w), "set_taps", "w must be [out_count, in_count", lead=2)
+        self._set_taps(w, out_first, w.shape[0], in_first, w.shape[1])
+
+    def get_taps(self, out_first=0, out_count=None, in_first=0, in_count=None):
+        """the weights of the paths (out_first .., in_first ..) (default: all from there) as complex64 [out_count, in_count, taps,
+        bins]: the handle's own float32 values"""
+        out_count, in_count = self._counts(out_first, out_count, in_first, in_count)
+        return self._get_taps((out_count, in_count), out_first, out_count, in_first, in_count)
+
+    def set_variance(self, out_first, p, in_first=0):
+        """replace the variances of the paths (out_first .., in_first ..); p: real [out_count, in_count, taps, bins], finite and
+        >= 0 -- raising them re-opens adaptation after a known path change"""
+        p = self._rows(np.asarray(p), "set_variance", "p must be [out_count, in_count", lead=2)
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        self._call("_set_variance", out_first, p.shape[0], in_first, p.shape[1], p.ctypes.data)
+
+    def get_variance(self, out_first=0, out_count=None, in_first=0, in_count=None):
+        """the variances of the paths (out_first .., in_first ..) as float32 [out_count, in_count, taps, bins]"""
+        out_count, in_count = self._counts(out_first, out_count, in_first, in_count)
+        p = np.empty((max(out_count, 0), max(in_count, 0), self.taps, self.bins), dtype=np.float32)
+        self._call("_get_variance", out_first, out_count, in_first, in_count, p.ctypes.data)
+        return p
+
+    def get_noise(self, out_first=0, out_count=None):
+        """the noise powers of outputs out_first .. out_first + count - 1 as float32 [count, bins]"""
+        out_count = self.outputs - out_first if out_count is None else out_count
+        psi = np.empty((max(out_count, 0), self.bins), dtype=np.float32)
+        self._call("_get_noise", out_first, out_count, psi.ctypes.data)
+        return psi
 
     def reset(self, clear=False):
         self._call("_reset", 1 if clear else 0)
