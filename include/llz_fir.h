@@ -105,6 +105,10 @@ int llz_fir_filter_mc_pitched(unsigned long handle, const float *in, float *out,
 int llz_fir_filter_mc_flush(unsigned long handle, float *out);
 int llz_fir_filter_mc_flt_len(unsigned long handle);
 int llz_fir_filter_mc_algo(unsigned long handle);
+/* LLZ_FIR_ALGO_OVERLAP_SAVE: taps that are symmetric about a centre tap c = 32 K, K = 1..4 (65, 129, 193, 257 taps), are
+ * filtered with the real spectrum of the centred taps.  Returns the K the handle's next call takes under the tunes set now, 0
+ * for the complex spectrum product (every other tap set, every other algo, the ols_real_product = 0 tune). */
+int llz_fir_filter_mc_real_rows(unsigned long handle);
 /* LLZ_FIR_ALGO_PARTITIONED keeps the contract above.  Each call filters concat(history, frame) from scratch -- nothing spectral
  * is carried from call to call -- so a call costs about frame_len + flt_len samples of work: a frame much shorter than the
  * filter is legal but wasteful.  The flush runs through the same kernels.  The block spectra live in scratch allocated at init

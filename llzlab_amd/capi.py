@@ -140,6 +140,7 @@ def lib():
     sig("llz_fir_filter_mc_flush", i, ul, vp)
     sig("llz_fir_filter_mc_flt_len", i, ul)
     sig("llz_fir_filter_mc_algo", i, ul)
+    sig("llz_fir_filter_mc_real_rows", i, ul)
     sig("llz_fir_filter_mc_partition_plan", i, ul, i, C.POINTER(C.c_int))
     sig("llz_fir_filter_mc_set_stream", i, ul, vp)
     # llz_fir.h part 3

@@ -3,6 +3,7 @@
  * (reference libllzfilter/llz_fir.c:442-625) and the multi-channel float32 batch extension.  Plain C; the device
  * is reached only through llz_shim.h.
  */
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../../include/llz_fir.h"
@@ -164,7 +165,7 @@ typedef struct {
 static void firm_destroy(firm_t *f)
 {
     if (!f) return;
-    llzs_free(f->d_taps); llzs_free(f->d_hbank); llzs_free(f->ols.hfreq); llzs_free(f->ols.twid); llzs_free(f->ols.tw2k); llzs_free(f->ols.tw4k);
+    llzs_free(f->d_taps); llzs_free(f->d_hbank); llzs_free(f->ols.hfreq); llzs_free(f->ols.hreal); llzs_free(f->ols.twid); llzs_free(f->ols.tw2k); llzs_free(f->ols.tw4k);
     llzs_free(f->d_hist[0]); llzs_free(f->d_hist[1]); llzs_free(f->d_zero);
     llzs_free(f->d_hpart); llzs_free(f->d_ptw); llzs_free(f->d_scratch);
     llz_stage_release(&f->st_in); llz_stage_release(&f->st_out);
@@ -206,18 +207,55 @@ static void firm_w(float *dst, const double *cs, int m)
     dst[1] = (float)(-cs[2 * m + 1]);
 }
 
+/* The real spectrum product of the 1024-point overlap-save.  Taps that are symmetric about a centre tap c have, centred at
+ * index 0 (g[n] = taps[n + c], circularly in 1024), a real spectrum, and IFFT(FFT(x) G)[p] = y[p + c] for p in [c, 1023 - c]: the
+ * stored samples y[256 .. 1023] of a block are all there, c samples early.  The kernels take the shift in whole register rows
+ * of 32 samples, so the form is taken for c = 32 K, K = 1..4 (65, 129, 193, 257 taps: every length of that kind the library
+ * designs is symmetric), and only where the float taps mirror bit for bit -- the dropped imaginary part is then rounding of
+ * the cos / sin table alone.  Returns K, or 0 for the complex product (also under the ols_real_product = 0 tune). */
+int llz_host_ols_real_rows(const float *taps, int flt_len)
+{
+    const int c = (flt_len - 1) / 2;
+    if (llzs_tune(LLZS_TUNE_OLS_REAL_PRODUCT) == 0 || flt_len % 2 == 0 || c % 32 != 0 || c < 32 || c > 128) return 0;
+    for (int i = 0; i < c; i++)
+        if (memcmp(&taps[i], &taps[flt_len - 1 - i], sizeof(float)) != 0) return 0;
+    return c / 32;
+}
+
+/* dst[k] = Re DFT_1024(g)[k] / 1024, k < 1024 in natural order, in double from cs = llz_host_cs_table(cs, 1024) (the device
+ * table is its cast to float); *imag_max (may be NULL) = the largest |Im DFT_1024(g)[k]| / 1024 that is dropped */
+void llz_host_ols_real_table(double *dst, double *imag_max, const float *taps, int flt_len, const double *cs)
+{
+    const int c = (flt_len - 1) / 2;
+    double worst = 0.0;
+    for (int k = 0; k < 1024; k++) {
+        double re = 0.0, im = 0.0;
+        for (int t = 0; t < flt_len; t++) {
+            const int m = (int)(((long)k * (t - c + 1024)) % 1024);        /* g[t - c] = taps[t] */
+            re += (double)taps[t] * cs[2 * m];
+            im -= (double)taps[t] * cs[2 * m + 1];
+        }
+        dst[k] = re / 1024;
+        if (fabs(im / 1024) > worst) worst = fabs(im / 1024);
+    }
+    if (imag_max) *imag_max = worst;
+}
+
 /* the tables of the N-point overlap-save (llzs_ols_tables): the spectrum of the (float-rounded) taps scaled by 1/N in
  * P = N / 1024 planes, the 32 x 32 twiddles W_1024^(ab) = W_N^(P ab), W_2048^n (N = 2048, 4096) and W_4096^n (N = 4096, 8192),
- * all from one quadrant-exact cos / sin table of size N.  Direct DFT in double (up to 6145 x 8192 terms), setup time only. */
+ * all from one quadrant-exact cos / sin table of size N.  Direct DFT in double (up to 6145 x 8192 terms), setup time only.  1024
+ * points, K = llz_host_ols_real_rows > 0: the real table of the centred taps next to them (512 complex entries' worth). */
 static int firm_build_ols_tables(firm_t *f, const float *taps, int N)
 {
     const int P = N / 1024;
-    /* complex entries of hfreq, twid, tw2k, tw4k (0: the rung has no such table) */
-    const int count[4] = {N, 1024, (N == 2048 || N == 4096) ? 1024 : 0, N >= 4096 ? 2048 : 0};
-    float **dev[4] = {&f->ols.hfreq, &f->ols.twid, &f->ols.tw2k, &f->ols.tw4k};
-    float *host[4];
+    const int K = N == 1024 ? llz_host_ols_real_rows(taps, f->flt_len) : 0;
+    /* complex entries of hfreq, twid, tw2k, tw4k, hreal (0: the rung has no such table) */
+    const int count[5] = {N, 1024, (N == 2048 || N == 4096) ? 1024 : 0, N >= 4096 ? 2048 : 0, K ? 512 : 0};
+    float **dev[5] = {&f->ols.hfreq, &f->ols.twid, &f->ols.tw2k, &f->ols.tw4k, &f->ols.hreal};
+    float *host[5];
     int rc = LLZ_OK;
-    for (int i = 0; i < 4; i++) {
+    f->ols.real_rows = K;
+    for (int i = 0; i < 5; i++) {
         host[i] = count[i] ? (float *)malloc(sizeof(float) * 2 * (size_t)count[i]) : NULL;
         if (count[i] && !host[i]) rc = LLZ_ERR_NOMEM;
     }
@@ -241,13 +279,20 @@ static int firm_build_ols_tables(firm_t *f, const float *taps, int N)
             for (int b = 0; b < 32; b++) firm_w(&tw[2 * (a * 32 + b)], cs, (P * a * b) % N);
         for (int i = 0; i < count[2]; i++) firm_w(&w2[2 * i], cs, i * (N / 2048));
         for (int i = 0; i < count[3]; i++) firm_w(&w4[2 * i], cs, i * (N / 4096));
-        /* allocate, then upload in the order hfreq, twid, tw2k, tw4k: a sharded init records the tables in upload order */
-        for (int i = 0; i < 4; i++)
+        double *g = K ? (double *)malloc(sizeof(double) * 1024) : NULL;
+        if (K && !g) rc = LLZ_ERR_NOMEM;
+        if (g) {
+            llz_host_ols_real_table(g, NULL, taps, f->flt_len, cs);
+            for (int k = 0; k < 1024; k++) host[4][k] = (float)g[k];
+            free(g);
+        }
+        /* allocate, then upload in the order hfreq, twid, tw2k, tw4k, hreal: a sharded init records the tables in upload order */
+        for (int i = 0; i < 5; i++)
             if (count[i] && !(*dev[i] = (float *)llzs_malloc(sizeof(float) * 2 * (size_t)count[i]))) rc = LLZ_ERR_NOMEM;
-        for (int i = 0; i < 4 && rc == LLZ_OK; i++)
+        for (int i = 0; i < 5 && rc == LLZ_OK; i++)
             if (count[i]) rc = llzs_h2d_table(*dev[i], host[i], sizeof(float) * 2 * (size_t)count[i]);
     }
-    for (int i = 0; i < 4; i++) free(host[i]);
+    for (int i = 0; i < 5; i++) free(host[i]);
     free(cs);
     return rc;
 }
@@ -475,6 +520,13 @@ void llz_fir_filter_mc_uninit(unsigned long handle)
 int llz_fir_filter_mc_flt_len(unsigned long handle)
 {
     return LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM) ? ((firm_t *)handle)->flt_len : LLZ_ERR_ARG;
+}
+
+int llz_fir_filter_mc_real_rows(unsigned long handle)
+{
+    if (!LLZ_HANDLE_OK(handle, firm_t, LLZ_TAG_FIRM)) return LLZ_ERR_ARG;
+    const firm_t *f = (const firm_t *)handle;
+    return f->algo == LLZ_FIR_ALGO_OVERLAP_SAVE ? llzs_fir_ols_real_rows(&f->ols) : 0;
 }
 
 int llz_fir_filter_mc_algo(unsigned long handle)

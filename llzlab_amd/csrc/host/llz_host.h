@@ -82,6 +82,13 @@ int llz_host_mdct_pretwiddles_f32(int N, float **tc, float **ts);
  * twiddles come from */
 void llz_host_cs_table(double *cs, int N);
 
+/* the real spectrum product of the 1024-point overlap-save (llz_fir_host.c): K = c / 32 for float taps that mirror bit for bit
+ * about tap c = (flt_len - 1) / 2 = 32, 64, 96 or 128, else 0 (also under the ols_real_product = 0 tune); and the table it
+ * takes, in double (the device table is its cast to float): dst[k] = Re DFT_1024(g)[k] / 1024, g[n] = taps[n + c] circularly,
+ * natural order, cs: llz_host_cs_table(cs, 1024); *imag_max (may be NULL): the largest dropped |Im| / 1024 */
+int  llz_host_ols_real_rows(const float *taps, int flt_len);
+void llz_host_ols_real_table(double *dst, double *imag_max, const float *taps, int flt_len, const double *cs);
+
 /* one tap row into the [P][N] complex floats of its partition spectra (LLZ_FIR_ALGO_PARTITIONED), P = ceil(flt_len / (N / 2)):
  * row p = DFT_N(taps[p N / 2 .. (p + 1) N / 2), zero-padded) / N, computed in double and rounded to float once, in the order of a
  * decimation-in-frequency transform's output (entry i = bin bitrev(i)); cs: llz_host_cs_table(cs, N); z: 2 N doubles of work

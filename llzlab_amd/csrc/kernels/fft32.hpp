@@ -145,13 +145,14 @@ __device__ __forceinline__ int xaddr(int row, int col) { return row * OLS_PITCH 
 
 // wcol: the column this lane's registers go to (its index in the twiddle W^(row * wcol) as well); rrow: the row it reads
 // back.  The half-wave's lanes must cover 0..31 once in each (any lane order: the overlap-save kernel's wide I/O form
-// owns permuted columns).
-template <bool INV>
+// owns permuted columns).  SKIP1: register 0 meets twiddle row 0, which is all ones, and is left as it is -- the product with
+// (1, 0) is fma(-a.y, 0, a.x * 1), the same bits for finite data (the headline overlap-save kernels ask for it).
+template <bool INV, bool SKIP1 = false>
 __device__ __forceinline__ void transpose_twiddle(cf (&v)[32], float *buf, const float2 *__restrict__ tw, int wcol, int rrow)
 {
     // inter-pass twiddle W_1024^(+-brev5(r)*wcol) applied on the way out, then two single-plane transposes
 #pragma unroll
-    for (int r = 0; r < 32; r++) {
+    for (int r = SKIP1 ? 1 : 0; r < 32; r++) {
         const float2 w = tw[brev5(r) * 32 + wcol];
         v[r] = cmul<INV>(v[r], cf{w.x, w.y});
     }

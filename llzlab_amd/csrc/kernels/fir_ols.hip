@@ -40,6 +40,30 @@
 //     are 96 KB at a 96 KB stride: never aligned, and no whole number of 6 KB jobs makes 32 KB.  The copy stand-in of both
 //     shapes (tools/ubench/ols_io.hip sb, profiles/r04/ubench_ols_io_superblock.txt): 5.80 against 5.57 TB/s; the kernel:
 //     6.28 against 6.40 ms on the headline, same box, alternating (profiles/r04/ab_ols_superblock.txt).
+//   * the spectrum product, template parameter K of both 1024-point kernels (ols_filter<K>, ols_walk.hpp).  K = 0: the complex
+//     product with DFT(taps) / 1024.  K = 1..4: taps that mirror bit for bit about tap c = 32 K (65, 129, 193, 257 taps: every
+//     filter of such a length the library designs, the headline's among them) are centred at index 0 on the host, where their
+//     spectrum is REAL (llzs_ols_tables.hreal: 1024 floats, the first 4 KB of the spectrum's LDS slot; the other 4 KB stay
+//     unused): two multiplies and one ds_read_b32 per bin instead of a complex product and a ds_read_b64, and the block comes out
+//     c samples early -- register row m is sample row m + K, the stores keep sample rows >= 8 (>= 16 in the short job) as
+//     before, same addresses in the same order.  Valid because the circular product is the linear one for p in [c, 1023 - c],
+//     i.e. for samples 2c..1023 of the block, and 2c <= 256.  Such a call also leaves register 0 out of the inter-pass twiddle
+//     (transpose_twiddle<INV, true>: row 0 of W_1024^(ab) is all ones; the same bits on finite data).  The host decides K from
+//     the float taps at init (llz_host_ols_real_rows), the launcher takes it per call (ols_real_rows; the ols_real_product tune:
+//     0 = complex).  The transform block of the steady-state job: 1948 -> 1847 vector ALU instructions per wave and job.
+//   * addresses of the super-block walk's requests and stores: one 64-bit address per sub-stream and job, the 24 rows (128 B
+//     apart) in the instructions' offsets: 4 vector ALU instructions in the request block instead of 50 (a sign extension and
+//     a 64-bit add every second load).  Same loads and stores, same order, same non-temporal hints.
+//     Both together, parent against this, bench.py alternating on one box (profiles/headline_diet/ab_headline.txt): 6.47..6.50
+//     -> 6.24..6.27 ms per step, ratio 0.963, on a second box 6.38..6.39 -> 6.10..6.14, ratio 0.960, every run of the one below
+//     every run of the other; there, each part on its own: without the real product 6.28..6.29, without the addresses
+//     6.19..6.21.  The instruction counts per block: profiles/headline_diet/isa_counts.txt (tools/isa_counts.py).
+//   * not done: the 48 + 16 register copies at the back edge of the ten-job loop (the prefetched rows and the carried overlaps
+//     moved to the registers the next iteration reads).  Requests are issued before the transform, so a request set's
+//     registers must differ from the 64 the transform still reads; two sets that swap roles (five iterations of two jobs)
+//     take the 48 x 2 copies of the rows that are used once away, but a row that is also the next job's overlap lives through
+//     three requests, and ten jobs are no multiple of three: that loop compiles to 40 copies per two jobs, 254 VGPRs and
+//     66 KB of code against 48 KB, and 6.12..6.13 ms against 6.10..6.14 without it on the second box: no gain, not kept.
 //   * known and deliberately left alone: in the compiled job loop an s_waitcnt vmcnt(0) follows the prefetch requests directly,
 //     before the transform's first instruction, so a wave does not overlap its own prefetch with its own transform; the other
 //     wave of the SIMD does.  A third wave to hide that wait changed nothing (profiles/r02/ab_ols_no_prefetch_three_waves.txt).
@@ -69,6 +93,8 @@ struct ols_smem {
     float *buf;
 };
 
+// K > 0: hfreq is the real table (1024 floats, llzs_ols_tables.hreal), which takes the first half of the spectrum's 8 KB
+template <int K>
 __device__ __forceinline__ ols_smem ols_tables(char *smem, const float2 *__restrict__ hfreq, const float2 *__restrict__ twid)
 {
     ols_smem m;
@@ -76,7 +102,8 @@ __device__ __forceinline__ ols_smem ols_tables(char *smem, const float2 *__restr
     m.h = m.tw + 1024;                                        // [1024]    FFT(taps)/1024, natural bins
     for (int i = threadIdx.x; i < 1024; i += OLS_THREADS) {
         m.tw[i] = twid[i];
-        m.h[i] = hfreq[i];
+        if constexpr (K > 0) reinterpret_cast<float *>(m.h)[i] = reinterpret_cast<const float *>(hfreq)[i];
+        else m.h[i] = hfreq[i];
     }
     __syncthreads();
     const int wave = threadIdx.x >> 6, half = (threadIdx.x >> 5) & 1;
@@ -90,13 +117,14 @@ __device__ __forceinline__ ols_smem ols_tables(char *smem, const float2 *__restr
 // segment start waits on memory (a first form requested past the segment's end and discarded the data: 1/16 of the input
 // fetched twice, 3 % slower on the headline; it was also slower on batches of a single round: 0.21 against 0.13 ms on 64
 // channels x 63 taps).  Both halves of a wave step through their segments together (a segment that is short at the end of a
-// channel idles its tail).
+// channel idles its tail).  K: the spectrum product (ols_filter), 0 = complex.
+template <int K>
 __global__ void __launch_bounds__(OLS_THREADS, 2)
 k_fir_ols_seg_f32(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ hist,
                     const float2 *__restrict__ hfreq, const float2 *__restrict__ twid, ols_geom G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const ols_smem S = ols_tables(smem, hfreq, twid);
+    const ols_smem S = ols_tables<K>(smem, hfreq, twid);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l5 = lane & 31;
@@ -147,8 +175,8 @@ k_fir_ols_seg_f32(const float *__restrict__ in, float *__restrict__ out, const f
             if (!in_pair)
                 ols_load_halo(halo_n, g.half ? nrow[1] : nrow[0], hist ? hist + (size_t)nown.c * G.keep : nullptr,
                               nown.j0 * OLS_JOB, g.col, G.keep, nown.live);
-            ols_filter(v, u, S.buf, S.tw, S.h, l5, g.col);
-            ols_store(u, orow, s, live, g, G.n);
+            ols_filter<K>(v, u, S.buf, S.tw, S.h, l5, g.col);
+            ols_store<K>(u, orow, s, live, g, G.n);
         }
         cur[0] = nxt[0];
         cur[1] = nxt[1];
@@ -168,12 +196,13 @@ k_fir_ols_seg_f32(const float *__restrict__ in, float *__restrict__ out, const f
 // halos of the half-wave's next super-block; both halves of a wave step together; a ragged last super-block of a row runs all
 // 11 jobs on clamped requests and bounded stores (a dead region 1 is an all-zero imaginary part).  The launcher takes this
 // form only where rows and pitches keep the regions 32 KB-aligned and the batch fills the machine (ols_sb_applies).
+template <int K>
 __global__ void __launch_bounds__(OLS_THREADS, 2)
 k_fir_ols_chain_f32(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ hist,
                     const float2 *__restrict__ hfreq, const float2 *__restrict__ twid, ols_geom G /* a segment = a super-block */)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const ols_smem S = ols_tables(smem, hfreq, twid);
+    const ols_smem S = ols_tables<K>(smem, hfreq, twid);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l5 = lane & 31;
@@ -209,9 +238,9 @@ k_fir_ols_chain_f32(const float *__restrict__ in, float *__restrict__ out, const
             const int sn[2] = {s[0] + ols_sb_request(jj + 1), s[1] + ols_sb_request(jj + 1)};
             if (jj + 1 < OLS_SB_FULL_JOBS) ols_sb_load<24>(raw, row, sn, live, whole, g, G.n);
             else ols_sb_load<16>(raw, row, sn, live, whole, g, G.n);
-            ols_filter(v, u, S.buf, S.tw, S.h, l5, g.col);
+            ols_filter<K>(v, u, S.buf, S.tw, S.h, l5, g.col);
             const int w[2] = {s[0] + ols_sb_window(jj), s[1] + ols_sb_window(jj)};
-            ols_sb_store<8>(u, orow, w, live, whole, g, G.n);
+            ols_sb_store<8, K>(u, orow, w, live, whole, g, G.n);
         }
         {
             cf v[32], u[32];
@@ -224,9 +253,9 @@ k_fir_ols_chain_f32(const float *__restrict__ in, float *__restrict__ out, const
             ols_sb_load<24>(raw, nrow, sn, ln, ln[0] && ln[1] && ols_sb_whole(sn[0], G.n) && ols_sb_whole(sn[1], G.n), g, G.n);
             ols_sb_load_halo(halo, g.half ? nrow[1] : nrow[0], hist ? hist + (size_t)nown.c * G.keep : nullptr, g.half ? sn[1] : sn[0],
                              g.col, G.keep, G.n, nown.live);
-            ols_filter(v, u, S.buf, S.tw, S.h, l5, g.col);
+            ols_filter<K>(v, u, S.buf, S.tw, S.h, l5, g.col);
             const int w[2] = {s[0] + ols_sb_window(OLS_SB_FULL_JOBS), s[1] + ols_sb_window(OLS_SB_FULL_JOBS)};
-            ols_sb_store<16>(u, orow, w, live, whole, g, G.n);
+            ols_sb_store<16, K>(u, orow, w, live, whole, g, G.n);
         }
         cur[0] = nxt[0];
         cur[1] = nxt[1];
@@ -912,7 +941,7 @@ const ols_rung OLS_RUNGS[] = {
     // two workgroups per CU: 49 KB of LDS and ~240 registers per lane
     {1024, 1, "k_fir_ols_f32", OLS_THREADS, 2 * OLS_WAVES, 2, true, 1.0,
      2 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float), false, false,
-     1, {OLS_OVERLAP}, {kfn(k_fir_ols_seg_f32)}},
+     1, {OLS_OVERLAP}, {kfn(k_fir_ols_seg_f32<0>)}},
     {2048, 2, "k_fir_ols2k_chain_f32", OLS_THREADS, OLS_WAVES, 2, false, 1.0,
      4 * 1024 * sizeof(float2) + (size_t)OLS_WAVES * 2 * OLS_XBUF * sizeof(float), true, false,
      2, {512, 1024}, {kfn(k_fir_ols2k_chain_f32<512>), kfn(k_fir_ols2k_chain_f32<1024>)}},
@@ -954,6 +983,21 @@ void ols_sb_plan(ols_plan &p, int channels, int n)
     if (p.blocks > p.max_blocks) p.blocks = p.max_blocks;
 }
 
+// the 1024-point kernels by K (ols_filter): the segment walk and the super-block walk
+const void *const OLS_SEG_BY_K[5] = {kfn(k_fir_ols_seg_f32<0>), kfn(k_fir_ols_seg_f32<1>), kfn(k_fir_ols_seg_f32<2>),
+                                     kfn(k_fir_ols_seg_f32<3>), kfn(k_fir_ols_seg_f32<4>)};
+const void *const OLS_CHAIN_BY_K[5] = {kfn(k_fir_ols_chain_f32<0>), kfn(k_fir_ols_chain_f32<1>), kfn(k_fir_ols_chain_f32<2>),
+                                       kfn(k_fir_ols_chain_f32<3>), kfn(k_fir_ols_chain_f32<4>)};
+
+// The real spectrum product is taken where the handle's tables carry it (the host decides from the taps: llzs_ols_tables) and
+// the call's tap count is the one the table was centred for.  The ols_real_product tune: unset = this choice, 0 = the complex
+// product.
+int ols_real_rows(const llzs_ols_tables *t, int flt_len)
+{
+    if (!t->hreal || t->real_rows < 1 || t->real_rows > 4 || flt_len != 64 * t->real_rows + 1) return 0;
+    return llzs_tune(LLZS_TUNE_OLS_REAL_PRODUCT) == 0 ? 0 : t->real_rows;
+}
+
 } // namespace
 
 extern "C" int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float *in, float *out, const float *hist, int channels,
@@ -981,9 +1025,14 @@ extern "C" int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float 
     if (r->w4k) args[k++] = &w4;
     args[k] = &p.G;
     const void *kernel = r->kernel[p.instance];
-    if (r->nfft == 1024 && ols_sb_applies(p, in, out, in_pitch, out_pitch, n)) {
-        ols_sb_plan(p, channels, n);
-        kernel = kfn(k_fir_ols_chain_f32);
+    if (r->nfft == 1024) {
+        const int K = ols_real_rows(t, flt_len);
+        if (K > 0) hf = reinterpret_cast<const float2 *>(t->hreal);
+        kernel = OLS_SEG_BY_K[K];
+        if (ols_sb_applies(p, in, out, in_pitch, out_pitch, n)) {
+            ols_sb_plan(p, channels, n);
+            kernel = OLS_CHAIN_BY_K[K];
+        }
     }
     if (r->lds_bytes > 64 * 1024)
         LLZ_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
@@ -1000,6 +1049,11 @@ extern "C" int llzs_fir_ols_superblock(const float *in, const float *out, int ch
         return 0;
     const ols_plan p = ols_plan_of(r, channels, n, in_pitch, out_pitch, flt_len);
     return ols_sb_applies(p, in, out, in_pitch, out_pitch, n) ? 1 : 0;
+}
+
+extern "C" int llzs_fir_ols_real_rows(const llzs_ols_tables *t)
+{
+    return t ? ols_real_rows(t, 64 * t->real_rows + 1) : 0;
 }
 
 #ifdef O8K_TRACE

@@ -103,35 +103,54 @@ __device__ __forceinline__ void ols_load_halo(float (&halo)[8], const float *row
 // The transform pair around the spectrum product, all in registers + one LDS transpose each way.  `col` is the lane's column
 // n2 of the input / output decomposition n = 32 n1 + n2; between the transposes lane l5 owns bin row k1 = l5.
 // forward: pass 1 over n1 (in registers), twiddle W^(k1 n2) + transpose, pass 2 over n2
+// SKIP1: the twiddle row of ones is not multiplied with (transpose_twiddle)
+template <bool SKIP1 = false>
 __device__ __forceinline__ void ols_forward(cf (&v)[32], float *buf, const float2 *s_tw, int l5, int col)
 {
     fft32<false>(v);
-    transpose_twiddle<false>(v, buf, s_tw, col, l5);
+    transpose_twiddle<false, SKIP1>(v, buf, s_tw, col, l5);
     fft32<false>(v);                                        // v[r] = X[l5 + 32*brev5(r)]
 }
 
 // inverse, from bins in natural k2 order: pass over k2, conj twiddle + transpose, pass over k1
+template <bool SKIP1 = false>
 __device__ __forceinline__ void ols_inverse(cf (&u)[32], float *buf, const float2 *s_tw, int l5, int col)
 {
     fft32<true>(u);
-    transpose_twiddle<true>(u, buf, s_tw, l5, col);
+    transpose_twiddle<true, SKIP1>(u, buf, s_tw, l5, col);
     fft32<true>(u);                                         // u[r] = y[32*brev5(r) + col]
 }
 
 // FFT -> multiply by the filter spectrum s_h (1024 natural-order bins, the 1/1024 folded in) -> IFFT
+// K > 0 (the 1024-point rung alone): the taps are symmetric about tap 32 K and s_h holds 1024 FLOATS, the real spectrum of the
+// taps centred at index 0 (llz_shim.h, llzs_ols_tables) -- two multiplies per bin instead of a complex product, and the block
+// comes out 32 K samples early: register row m is sample row m + K (ols_store, ols_sb_store).  Such a call also skips the
+// product with the twiddle row of ones, which is the same bits on finite data.
+template <int K = 0>
 __device__ __forceinline__ void ols_filter(cf (&v)[32], cf (&u)[32], float *buf, const float2 *s_tw,
                                            const float2 *s_h, int l5, int col)
 {
-    ols_forward(v, buf, s_tw, l5, col);
+    ols_forward<(K > 0)>(v, buf, s_tw, l5, col);
+    if constexpr (K > 0) {
+        const float *s_g = reinterpret_cast<const float *>(s_h);
 #pragma unroll
-    for (int r = 0; r < 32; r++) {
-        const float2 h = s_h[l5 + 32 * brev5(r)];
-        u[brev5(r)] = cmul<false>(v[r], cf{h.x, h.y});     // back to natural k2 order: renaming only
+        for (int r = 0; r < 32; r++) {
+            const float g = s_g[l5 + 32 * brev5(r)];
+            u[brev5(r)] = cf{v[r].x * g, v[r].y * g};
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 32; r++) {
+            const float2 h = s_h[l5 + 32 * brev5(r)];
+            u[brev5(r)] = cmul<false>(v[r], cf{h.x, h.y});     // back to natural k2 order: renaming only
+        }
     }
-    ols_inverse(u, buf, s_tw, l5, col);
+    ols_inverse<(K > 0)>(u, buf, s_tw, l5, col);
 }
 
-// keep the 768 valid samples of each block: rows n1 = brev5(r) >= 8
+// keep the 768 valid samples of each block: sample rows n1 >= 8, in the order n1 = brev5(0), brev5(1), ...; sample row n1 is
+// register row n1 - K
+template <int K = 0>
 __device__ __forceinline__ void ols_store(const cf (&u)[32], float *const (&orow)[2], const int (&s)[2],
                                           const bool (&live)[2], const ols_lane &g, int n)
 {
@@ -144,8 +163,8 @@ __device__ __forceinline__ void ols_store(const cf (&u)[32], float *const (&orow
     const int ob = oa + OLS_VALID;
     if (whole) {
 #pragma unroll
-        for (int r = 0; r < 32; r++) {
-            const int n1 = brev5(r);
+        for (int i = 0; i < 32; i++) {
+            const int n1 = brev5(i), r = brev5((n1 - K) & 31);
             if (n1 >= 8) {
                 __builtin_nontemporal_store(u[r].x, &o[oa + 32 * n1]);
                 __builtin_nontemporal_store(u[r].y, &o[ob + 32 * n1]);
@@ -153,8 +172,8 @@ __device__ __forceinline__ void ols_store(const cf (&u)[32], float *const (&orow
         }
     } else {
 #pragma unroll
-        for (int r = 0; r < 32; r++) {
-            const int n1 = brev5(r);
+        for (int i = 0; i < 32; i++) {
+            const int n1 = brev5(i), r = brev5((n1 - K) & 31);
             if (n1 >= 8) {
                 if (oa + 32 * n1 < n) o[oa + 32 * n1] = u[r].x;
                 if (ob + 32 * n1 < n) o[ob + 32 * n1] = u[r].y;
@@ -192,11 +211,22 @@ __device__ __forceinline__ void ols_sb_load(ols_raw &raw, const float *const (&r
     const int so = g.half ? s[1] : s[0];
     const bool lv = g.half ? live[1] : live[0];
     if (whole) {
+        // one 64-bit address per sub-stream; the rows are 128 B apart and ride in the instructions' offsets (an int index per
+        // request costs a sign extension and a 64-bit add every second load: LLZ_OLS_SB_INT_INDEX, the A/B form)
+#ifdef LLZ_OLS_SB_INT_INDEX
 #pragma unroll
         for (int i = 0; i < ROWS; i++) {
             raw.a[i] = __builtin_nontemporal_load(&r[so + OLS_SB_ROW * i + g.col]);
             raw.b[i] = __builtin_nontemporal_load(&r[so + OLS_SB_REGION + OLS_SB_ROW * i + g.col]);
         }
+#else
+        const float *const pa = r + (so + g.col), *const pb = pa + OLS_SB_REGION;
+#pragma unroll
+        for (int i = 0; i < ROWS; i++) {
+            raw.a[i] = __builtin_nontemporal_load(&pa[OLS_SB_ROW * i]);
+            raw.b[i] = __builtin_nontemporal_load(&pb[OLS_SB_ROW * i]);
+        }
+#endif
     } else {
         // a ragged last super-block (region 1 short or absent) or an idle half
 #pragma unroll
@@ -229,8 +259,9 @@ __device__ __forceinline__ void ols_sb_load_halo(float (&halo)[16], const float 
     }
 }
 
-// keep the rows >= CARRY of both blocks; w[h] = the first sample of half h's block of region 0 (region 1's is OLS_SB_REGION on)
-template <int CARRY>
+// keep the sample rows >= CARRY of both blocks (register rows >= CARRY - K: ols_filter); w[h] = the first sample of half h's
+// block of region 0 (region 1's is OLS_SB_REGION on)
+template <int CARRY, int K = 0>
 __device__ __forceinline__ void ols_sb_store(const cf (&u)[32], float *const (&orow)[2], const int (&w)[2], const bool (&live)[2],
                                              bool whole, const ols_lane &g, int n)
 {
@@ -240,18 +271,30 @@ __device__ __forceinline__ void ols_sb_store(const cf (&u)[32], float *const (&o
     const int oa = (g.half ? w[1] : w[0]) + g.col;        // + 32*n1
     const int ob = oa + OLS_SB_REGION;
     if (whole) {
+#ifdef LLZ_OLS_SB_INT_INDEX
 #pragma unroll
-        for (int r = 0; r < 32; r++) {
-            const int n1 = brev5(r);
+        for (int i = 0; i < 32; i++) {
+            const int n1 = brev5(i), r = brev5((n1 - K) & 31);
             if (n1 >= CARRY) {
                 __builtin_nontemporal_store(u[r].x, &o[oa + OLS_SB_ROW * n1]);
                 __builtin_nontemporal_store(u[r].y, &o[ob + OLS_SB_ROW * n1]);
             }
         }
+#else
+        float *const pa = o + oa, *const pb = pa + OLS_SB_REGION;          // as ols_sb_load: two addresses, the rows in the offsets
+#pragma unroll
+        for (int i = 0; i < 32; i++) {
+            const int n1 = brev5(i), r = brev5((n1 - K) & 31);
+            if (n1 >= CARRY) {
+                __builtin_nontemporal_store(u[r].x, &pa[OLS_SB_ROW * n1]);
+                __builtin_nontemporal_store(u[r].y, &pb[OLS_SB_ROW * n1]);
+            }
+        }
+#endif
     } else {
 #pragma unroll
-        for (int r = 0; r < 32; r++) {
-            const int n1 = brev5(r);
+        for (int i = 0; i < 32; i++) {
+            const int n1 = brev5(i), r = brev5((n1 - K) & 31);
             if (n1 >= CARRY) {
                 if (oa + OLS_SB_ROW * n1 < n) o[oa + OLS_SB_ROW * n1] = u[r].x;
                 if (ob + OLS_SB_ROW * n1 < n) o[ob + OLS_SB_ROW * n1] = u[r].y;

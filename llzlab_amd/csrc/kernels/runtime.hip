@@ -25,7 +25,7 @@ static const char *const g_tune_names[LLZS_TUNE_COUNT] = {
     "ols_wg_per_cu", "rs_generic", "rs_tiles", "rs_dec_valu", "rs_i16_path", "mfma_nacc",
     "mfma_wg_per_cu", "fft_generic", "iir_segs", "iir_unpacked", "iir_f64", "iir_pipe", "iir_wave_min_items",
     "shard_rccl", "rs_mfma_form", "ols_seg_len", "mdct_run", "mdctq_steps", "rs_i16_tiles", "rs_i16_walk", "acf_lds", "stft_full",
-    "lpc_split", "bank_global_h", "part_nfft", "part_scratch_mb", "ols_superblock", "csd_scratch_kb", "adapt_ppw",
+    "lpc_split", "bank_global_h", "part_nfft", "part_scratch_mb", "ols_superblock", "csd_scratch_kb", "ols_real_product", "adapt_ppw",
     "asrc_table_global", "pfb_global"};
 namespace {
 struct tune_init {

@@ -64,6 +64,9 @@ enum {
     LLZS_TUNE_OLS_SUPERBLOCK,       /* 1024-point overlap-save on large batches with 32 KB-aligned rows: 1 = the super-block walk
                                      * on small batches too (never without the alignment), 0 = the segment walk */
     LLZS_TUNE_CSD_SCRATCH_KB,       /* llz_csd_mc: cap of the run-partial scratch in KiB (the library's own: 256 MiB), read per call */
+    LLZS_TUNE_OLS_REAL_PRODUCT,     /* 1024-point overlap-save, tap sets that are symmetric about a centre tap at 32, 64, 96 or 128:
+                                     * 0 = the complex spectrum product all the same (unset: the real product of the centred
+                                     * taps), read at init and per call */
     LLZS_TUNE_ADAPT_PPW,            /* llz_adapt_mc, llz_adapt_matrix_mc: partitions per workgroup of the weight update (1..64), read per call; no bit
                                      * of the result depends on it */
     LLZS_TUNE_ASRC_TABLE_GLOBAL,    /* llz_asrc_mc: 1 = the table is read from global memory even where it fits the LDS form, read at init */
@@ -120,12 +123,20 @@ int llzs_fir_td_bank_f32(const float *in, float *out, const float *hist, const f
  * tw4k = [2048] W_4096^n (4096 and 8192 points, else NULL). */
 typedef struct {
     float *hfreq, *twid, *tw2k, *tw4k;
+    /* 1024 points only, else NULL / 0.  Taps that are bit for bit symmetric about tap c = 32 K, K = 1..4 (flt_len = 2 c + 1),
+     * have a REAL spectrum once they are centred at index 0: hreal = [1024] floats Re DFT_1024(g) / 1024, g[n] = taps[n + c]
+     * circularly, natural bin order, and real_rows = K: the product with it yields every output c samples = K rows of 32 early */
+    float *hreal;
+    int real_rows;
 } llzs_ols_tables;
 int llzs_fir_ols_f32(int nfft, const llzs_ols_tables *t, const float *in, float *out, const float *hist, int channels,
                      int n, long in_pitch, long out_pitch, int flt_len, void *stream);
 /* 1 when the 1024-point call of this shape takes the super-block walk (k_fir_ols_chain_f32), 0 for the segment walk: the
  * launcher's own decision under the tunes set now, for tests and measurement tools; nothing is launched */
 int llzs_fir_ols_superblock(const float *in, const float *out, int channels, int n, long in_pitch, long out_pitch, int flt_len);
+/* the K of the spectrum product a 1024-point call with these tables takes under the tunes set now: t->real_rows, or 0 (the
+ * complex product) without a real table or under ols_real_product = 0; nothing is launched */
+int llzs_fir_ols_real_rows(const llzs_ols_tables *t);
 /* 1024-point overlap-save with a spectrum per channel (fir_bank.hip), 1..257 taps: hbank = [channels][LLZS_BANK_PITCH] complex
  * floats, row c = bins 0..512 of DFT_1024(taps of channel c) / 1024 (the taps are real: the kernel mirrors the rest), the
  * row's tail unused; twid as above */

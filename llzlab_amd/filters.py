@@ -150,6 +150,11 @@ class FirFilterMC:
         check(self._L.llz_fir_filter_mc_partition_plan(self.handle, int(n), out), "llz_fir_filter_mc_partition_plan")
         return tuple(out)
 
+    def real_rows(self):
+        """FIR_ALGO_OVERLAP_SAVE: the K of the real spectrum product the next call takes under the tunes set now (taps symmetric
+        about tap 32 K, K = 1..4), 0 for the complex product (llz_fir_filter_mc_real_rows; nothing is launched)"""
+        return check(self._L.llz_fir_filter_mc_real_rows(self.handle), "llz_fir_filter_mc_real_rows")
+
     def filter(self, x, out):
         """x, out: [channels, frame_len] float32 (torch device tensors or numpy). Returns out."""
         count = self.channels * self.frame_len
