@@ -27,6 +27,8 @@ MDCT_SINE, MDCT_KBD = 0, 1
 PCM_F32, PCM_I16, PCM_I16_FAST = 0, 1, 2
 CSD_RUN = 32                          # llz_spectral.h: LLZ_CSD_RUN
 SPEC_PXX, SPEC_PYY, SPEC_CSD, SPEC_COHERENCE, SPEC_TF = 0, 1, 2, 3, 4
+TDE_CC, TDE_PHAT, TDE_SCOT = 0, 1, 2     # llz_tde.h: the weightings
+TDE_CURVE, TDE_STATE = 0, 1            # ... and what llz_tde_mc_read takes
 
 _lib = None
 
@@ -360,6 +362,16 @@ def lib():
     sig("llz_csd_mc_read_raw", i, ul, vp)
     sig("llz_csd_mc_reset", i, ul)
     sig("llz_csd_mc_plan", i, ul, lng, C.POINTER(C.c_int))
+    # llz_tde.h
+    sig("llz_tde_mc_init", ul, i, i, C.POINTER(C.c_int), i, i, i, i, i, i, i, C.c_float, C.c_float)
+    sig("llz_tde_mc_uninit", None, ul)
+    sig("llz_tde_mc_set_stream", i, ul, vp)
+    sig("llz_tde_mc_frames_for", lng, ul, lng)
+    sig("llz_tde_mc_process", lng, ul, vp, lng, vp, vp, lng)
+    sig("llz_tde_mc_frames", lng, ul)
+    sig("llz_tde_mc_read", i, ul, i, vp)
+    sig("llz_tde_mc_set_forget", i, ul, C.c_float)
+    sig("llz_tde_mc_reset", i, ul)
     sig("llz_levinson", None, dp, i, dp, dp, dp)
     sig("llz_levinson1", None, dp, i, dp, dp, dp)
     sig("llz_atlvs", i, dp, i, dp, dp, dp, dp)

@@ -514,6 +514,18 @@ int llzs_csd_fold_f64(const float *scratch, double *acc, int pairs, int bins, in
 int llzs_csd_read_f64(const double *acc, const float *carry, int pairs, int bins, int what, double ku, float *out, double *raw,
                       void *stream);
 
+/* ---- time-delay estimator (tde.hip; include/llz_tde.h) ----
+ * Framing as the cross-spectra's above: frame f covers samples [(f - hops0) hop, (f - hops0) hop + fft_len) of the call's x
+ * ([channels][x_pitch]), negative indices in hist ([channels][fft_len - hop]; may be NULL when hop == fft_len).  One launch, a
+ * workgroup per pair, walks frames [f_lo, f_hi) in order: state ([pairs][bins][4] = Re S, Im S, Gx, Gy) is read when f_lo > 0 and
+ * written back; frame 0 starts the recursion, lam == 0 takes S = P; delay: [pairs][delay_pitch], peak (may be NULL): [pairs][peak_pitch], element
+ * f - f_lo of each row; curve: [pairs][2 max_lag + 1], the curve of frame f_hi - 1 at lags -max_lag .. max_lag.  weight 0 CC,
+ * 1 PHAT, 2 SCOT over bins k_lo .. k_hi; g = (float)(1 - (double)lam).  pair_xy checked by the caller. */
+int llzs_tde_frames_f32(const float *x, const float *hist, const float *w, const float *cs, const int *pair_xy, float *state,
+                        float *curve, float *delay, float *peak, int pairs, int fft_len, int hop, long x_pitch, long hops0,
+                        long f_lo, long f_hi, long delay_pitch, long peak_pitch, int max_lag, int weight, int k_lo, int k_hi, float lam, float g,
+                        float delta, void *stream);
+
 /* ---- linear prediction (lpc.hip) ---- */
 /* LPC of frames x n float32 (0 <= p <= 32): the correlation of llzs_autocorr_mc_f32 (the same bits; on x*win when win is not
  * NULL) and the Levinson-Durbin recursion in double in one launch.  acof [frames][p+1]; kcof [frames][p], err, gain

@@ -1511,6 +1511,83 @@ class CsdMC:
     __del__ = close
 
 
+class TdeMC:
+    """llz_tde_mc_*: the delay between the two channels of each pair, per frame (include/llz_tde.h): generalised
+    cross-correlation on recursively averaged cross-spectra, weight capi.TDE_CC / TDE_PHAT / TDE_SCOT over the bins `band` =
+    (k_lo, k_hi) (None: 1 .. fft_len / 2 - 1).  pairs_xy: [(x, y), ...] channel indices; y[t] = x[t - D] reads a delay of +D.
+    process(x) takes planar [channels, n] float32 (n a multiple of hop; a device tensor or a numpy array) and returns
+    (delay, peak), each [pairs, frames written by the call]: new numpy arrays, or views of the `delay` / `peak` buffers when
+    given ([pairs, out_pitch] float32, device or host, out_pitch >= the call's frames; what lies behind the frames written
+    stays untouched).  curve(): [pairs, 2 max_lag + 1] of the last frame; state(): [pairs, bins, 4] = Re S, Im S, Gx, Gy."""
+
+    def __init__(self, channels, pairs_xy, fft_len, hop, max_lag, weight=capi.TDE_PHAT, lam=0.9, delta=0.0, band=None,
+                 win=HAMMING, stream=None):
+        self._L = capi.lib()
+        table = np.ascontiguousarray(pairs_xy, dtype=np.int32).reshape(-1, 2)
+        k_lo, k_hi = (1, fft_len // 2 - 1) if band is None else band
+        self.channels, self.pairs, self.fft_len, self.hop, self.max_lag = channels, len(table), fft_len, hop, max_lag
+        self.bins = fft_len // 2 + 1
+        self.handle = check_handle(self._L.llz_tde_mc_init(channels, self.pairs, table.ctypes.data_as(C.POINTER(C.c_int)),
+                                                           fft_len, hop, win, max_lag, weight, k_lo, k_hi, lam, delta),
+                                   "llz_tde_mc_init")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def set_stream(self, stream):
+        check(self._L.llz_tde_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_tde_mc_set_stream")
+
+    def frames_for(self, n):
+        return check(self._L.llz_tde_mc_frames_for(self.handle, n), "llz_tde_mc_frames_for")
+
+    def process(self, x, delay=None, peak=None):
+        size = x.numel() if hasattr(x, "numel") else x.size
+        n, rem = divmod(size, self.channels)
+        if rem:
+            raise LlzError(f"llz_tde_mc_process: {size} samples do not divide into {self.channels} channels")
+        frames = self.frames_for(n)
+        given = [buf.numel() if hasattr(buf, "numel") else buf.size for buf in (delay, peak) if buf is not None]
+        if given and (len(set(given)) != 1 or given[0] % self.pairs):
+            raise LlzError(f"llz_tde_mc_process: delay and peak are [pairs = {self.pairs}, out_pitch] with one out_pitch")
+        pitch = given[0] // self.pairs if given else frames
+        if delay is None:
+            delay = np.empty((self.pairs, pitch), dtype=np.float32)
+        if peak is None:
+            peak = np.empty((self.pairs, pitch), dtype=np.float32)
+        got = check(self._L.llz_tde_mc_process(self.handle, _typed(x, "float32", size, "x"), n,
+                                               _typed(delay, "float32", self.pairs * pitch, "delay"),
+                                               _typed(peak, "float32", self.pairs * pitch, "peak"), pitch),
+                    "llz_tde_mc_process")
+        return delay.reshape(self.pairs, pitch)[:, :got], peak.reshape(self.pairs, pitch)[:, :got]
+
+    def frames(self):
+        return check(self._L.llz_tde_mc_frames(self.handle), "llz_tde_mc_frames")
+
+    def _read(self, what, shape, out):
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        check(self._L.llz_tde_mc_read(self.handle, what, _typed(out, "float32", int(np.prod(shape)), "out")), "llz_tde_mc_read")
+        return out
+
+    def curve(self, out=None):
+        return self._read(capi.TDE_CURVE, (self.pairs, 2 * self.max_lag + 1), out)
+
+    def state(self, out=None):
+        return self._read(capi.TDE_STATE, (self.pairs, self.bins, 4), out)
+
+    def set_forget(self, lam):
+        check(self._L.llz_tde_mc_set_forget(self.handle, lam), "llz_tde_mc_set_forget")
+
+    def reset(self):
+        check(self._L.llz_tde_mc_reset(self.handle), "llz_tde_mc_reset")
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_tde_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
 # ------------------------------------------------------------------------------------------ linear prediction
 LEVINSON_ORDER_MAX = 64
 
