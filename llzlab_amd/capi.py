@@ -29,6 +29,7 @@ CSD_RUN = 32                          # llz_spectral.h: LLZ_CSD_RUN
 SPEC_PXX, SPEC_PYY, SPEC_CSD, SPEC_COHERENCE, SPEC_TF = 0, 1, 2, 3, 4
 TDE_CC, TDE_PHAT, TDE_SCOT = 0, 1, 2     # llz_tde.h: the weightings
 TDE_CURVE, TDE_STATE = 0, 1            # ... and what llz_tde_mc_read takes
+DFT_FUSED, DFT_COMPOSED = 0, 1         # llz_dft.h: the forms llz_dft_mc_plan reports
 
 _lib = None
 
@@ -372,6 +373,17 @@ def lib():
     sig("llz_tde_mc_read", i, ul, i, vp)
     sig("llz_tde_mc_set_forget", i, ul, C.c_float)
     sig("llz_tde_mc_reset", i, ul)
+    # llz_dft.h
+    sig("llz_dft_mc_init", ul, i)
+    sig("llz_czt_mc_init", ul, i, i, d, d)
+    sig("llz_dft_mc_uninit", None, ul)
+    sig("llz_dft_mc_set_stream", i, ul, vp)
+    sig("llz_dft_mc_set_window", i, ul, vp)
+    sig("llz_dft_mc_configure", i, ul, i, i)
+    sig("llz_dft_mc_plan", i, ul, i, C.POINTER(C.c_int))
+    for n in ("llz_dft_mc_forward", "llz_dft_mc_inverse", "llz_dft_mc_real_forward", "llz_dft_mc_real_inverse",
+              "llz_czt_mc_forward", "llz_czt_mc_real_forward"):
+        sig(n, i, ul, vp, lng, vp, lng, i)
     sig("llz_levinson", None, dp, i, dp, dp, dp)
     sig("llz_levinson1", None, dp, i, dp, dp, dp)
     sig("llz_atlvs", i, dp, i, dp, dp, dp, dp)

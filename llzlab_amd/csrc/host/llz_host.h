@@ -21,7 +21,7 @@ enum {
     LLZ_TAG_FIRX = 0x4c5a4658, LLZ_TAG_ADPT = 0x4c5a4144, LLZ_TAG_ADPX = 0x4c5a4158,
     LLZ_TAG_ASRC = 0x4c5a5352, LLZ_TAG_PFB = 0x4c5a5046, LLZ_TAG_ADPB = 0x4c5a4142,
     LLZ_TAG_ADBX = 0x4c5a4258, LLZ_TAG_KALB = 0x4c5a4b42,
-    LLZ_TAG_SUPB = 0x4c5a5342, LLZ_TAG_KALX = 0x4c5a4b58
+    LLZ_TAG_SUPB = 0x4c5a5342, LLZ_TAG_KALX = 0x4c5a4b58, LLZ_TAG_DFTM = 0x4c5a4446
 };
 
 #define LLZ_HANDLE_OK(h, type, tagv) ((h) != 0 && (h) != LLZ_BAD_HANDLE && ((type *)(h))->tag == (tagv))
@@ -76,11 +76,24 @@ int llz_host_mdct_sums_q15(int N, short **fwd, short **inv);
 /* the float pre-twiddles of the N/4-point form: cos and sin of -2 pi (k + 1/8) / N, k < N / 4 (llz_mdct.c:459-462) */
 int llz_host_mdct_pretwiddles_f32(int N, float **tc, float **ts);
 
+/* ---- llz_dft_host.c: the chirp tables of llz_dft_mc / llz_czt_mc (include/llz_dft.h has the algorithm) ----
+ * m: the transform length of n points in, k bins out.  The tables of one direction into HOST memory, each built in double and
+ * rounded to float once; a NULL table is skipped: pre [n] and post [k] complex with the window w (n floats, NULL: ones) folded
+ * into the forward pre and the inverse post; v [m] complex, FFT_m of the wrapped chirp -- natural == 0: divided by m, entry e =
+ * bin bitrev(e) (the fused kernel's); natural != 0: unscaled in natural order (the composed form's).  zoom == 0: the DFT
+ * (k == n; f0, df unused; inverse 0 or 1), else the zoom transform (inverse == 0).  LLZ_OK or LLZ_ERR_NOMEM with a message. */
+int llz_host_dft_m(int n, int k);
+int llz_host_dft_tables(int n, int k, int zoom, double f0, double df, int inverse, int natural, const float *w, float *pre,
+                        float *v, float *post);
+
 /* ---- llz_spectra.c: the tables of the frequency-domain FIR forms ---- */
 
 /* cs: 2 N doubles, cos then sin of 2 pi i / N, i < N, with exact quadrant values: the one table every FIR form's spectra and
  * twiddles come from */
 void llz_host_cs_table(double *cs, int N);
+/* z = DFT_N(z), N interleaved complex doubles, by radix-2 decimation in frequency in double, in place and left in that
+ * transform's output order: entry e is bin bitrev_N(e); cs: llz_host_cs_table(cs, N) */
+void llz_host_dif_f64(double *z, int N, const double *cs);
 
 /* the real spectrum product of the 1024-point overlap-save (llz_fir_host.c): K = c / 32 for float taps that mirror bit for bit
  * about tap c = (flt_len - 1) / 2 = 32, 64, 96 or 128, else 0 (also under the ols_real_product = 0 tune); and the table it

@@ -24,9 +24,8 @@ static int spectra_bitrev(int i, int bits)
     return r;
 }
 
-/* z = DFT_N(z) by radix-2 decimation in frequency in double, in place and left in that transform's output order: entry e is bin
- * bitrev_N(e) */
-static void spectra_dif(double *z, int N, const double *cs)
+/* entry e of the result is bin bitrev_N(e) (llz_host.h); also the chirp spectra of llz_dft_host.c */
+void llz_host_dif_f64(double *z, int N, const double *cs)
 {
     for (int span = N; span >= 2; span /= 2) {
         const int half = span / 2, step = N / span;
@@ -51,7 +50,7 @@ static void spectra_partition(double *z, const float *taps, int flt_len, int p, 
         z[2 * i] = (i < B && t < flt_len) ? (double)taps[t] : 0.0;
         z[2 * i + 1] = 0.0;
     }
-    spectra_dif(z, N, cs);
+    llz_host_dif_f64(z, N, cs);
 }
 
 /* Row p = the whole transform / N, rounded to float once: the device's forward transform leaves its bins in the same order, and
@@ -99,7 +98,7 @@ void llz_host_stream_taps(float *taps, int count, const float *row, int block, c
         z[2 * k] = (double)row[2 * i]; z[2 * k + 1] = -(double)row[2 * i + 1];
         z[2 * (N - k)] = (double)row[2 * i]; z[2 * (N - k) + 1] = (double)row[2 * i + 1];
     }
-    spectra_dif(z, N, cs);
+    llz_host_dif_f64(z, N, cs);
     for (int t = 0; t < count; t++) taps[t] = (float)(2.0 * z[2 * spectra_bitrev(t, bits + 1)]);
 }
 

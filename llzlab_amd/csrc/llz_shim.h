@@ -526,6 +526,25 @@ int llzs_tde_frames_f32(const float *x, const float *hist, const float *w, const
                         long f_lo, long f_hi, long delay_pitch, long peak_pitch, int max_lag, int weight, int k_lo, int k_hi, float lam, float g,
                         float delta, void *stream);
 
+/* ---- DFT of any length and zoom transform by the chirp-z algorithm (dft.hip; include/llz_dft.h) ----
+ * A row of n points becomes k outputs through two m-point transforms, m a power of two >= n + k - 1 (at least 8): a = x pre,
+ * zero-padded; A = FFT_m(a); B = A v; b = IFFT_m(B) unscaled; out[j] = b[j] post[j], j < k.  pre [n], v [m], post [k] complex
+ * floats, the host's tables (llz_dft_host.c); cs: cos then sin of 2 pi i / m.  in: count rows in_pitch >= 1 elements apart, out:
+ * out_pitch >= k apart, elements of the buffer's own kind.  mode 0: complex rows in and out; 1: real rows in; 2: bins 0 .. n / 2
+ * in, extended to the Hermitian row of n (the imaginary parts of the real bins dropped), and real rows out.
+ * fused: m <= 4096, one launch, v = FFT_m(.) / m in the ORDER OF A DECIMATION-IN-FREQUENCY TRANSFORM'S OUTPUT (entry i = bin
+ * bitrev(i)).  plan: out = {rows per workgroup, LDS bytes} of such a launch, nothing launched.
+ * pack, mul, extract: the composed form's steps around llzs_fft_f32 / llzs_fft_large_f32 (forward, then inverse, which divides
+ * by m) on z = [count][m] complex, m <= 2^21, v = FFT_m(.) in natural order. */
+int llzs_dft_plan(int m, int count, int *out);
+int llzs_dft_fused_f32(const float *in, float *out, const float *pre, const float *v, const float *post, const float *cs,
+                       int count, int n, int k, int m, long in_pitch, long out_pitch, int mode, void *stream);
+int llzs_dft_pack_f32(const float *in, float *z, const float *pre, int count, int n, int m, long in_pitch, int mode,
+                      void *stream);
+int llzs_dft_mul_f32(float *z, const float *v, int count, int m, void *stream);
+int llzs_dft_extract_f32(const float *z, float *out, const float *post, int count, int k, int m, long out_pitch, int mode,
+                         void *stream);
+
 /* ---- linear prediction (lpc.hip) ---- */
 /* LPC of frames x n float32 (0 <= p <= 32): the correlation of llzs_autocorr_mc_f32 (the same bits; on x*win when win is not
  * NULL) and the Levinson-Durbin recursion in double in one launch.  acof [frames][p+1]; kcof [frames][p], err, gain

@@ -1588,6 +1588,121 @@ class TdeMC:
     __del__ = close
 
 
+class _ChirpZ:
+    """what DftMC and CztMC share (include/llz_dft.h): rows a pitch apart in device tensors or numpy arrays.  A complex buffer
+    is complex64, or float32 pairs; pitches count elements of the buffer's own kind; `count` defaults to the rows a contiguous
+    input holds, the pitches to the row lengths, `out` to a new buffer where the input lives ([count, row] complex64 or
+    float32)."""
+
+    def _open(self, handle, what, window, stream):
+        self.handle = check_handle(handle, what)
+        if stream is not None:
+            self.set_stream(stream)
+        if window is not None:
+            self.set_window(window)
+
+    def set_stream(self, stream):
+        check(self._L.llz_dft_mc_set_stream(self.handle, _stream_ptr(stream)), "llz_dft_mc_set_stream")
+
+    def set_window(self, window):
+        """n float32 window values (host), None for all ones: folded into the tables, ordered on the stream"""
+        w = None if window is None else np.ascontiguousarray(window, dtype=np.float32)
+        if w is not None and w.size != self.n:
+            raise LlzError(f"llz_dft_mc_set_window: expected {self.n} window values, got {w.size}")
+        check(self._L.llz_dft_mc_set_window(self.handle, None if w is None else w.ctypes.data), "llz_dft_mc_set_window")
+
+    def configure(self, composed=False, scratch_mb=None):
+        """measurement and tests: the composed form even where the fused kernel would be taken, and the cap in MiB of the scratch
+        it walks `count` under (None: the library's 256)"""
+        check(self._L.llz_dft_mc_configure(self.handle, int(bool(composed)), -1 if scratch_mb is None else scratch_mb),
+              "llz_dft_mc_configure")
+
+    def plan(self, count):
+        """{form, M, rows per workgroup, LDS bytes, slabs} of a call of `count` rows"""
+        out = (C.c_int * 5)()
+        check(self._L.llz_dft_mc_plan(self.handle, count, out), "llz_dft_mc_plan")
+        return dict(zip(("form", "m", "tpw", "lds", "slabs"), (int(v) for v in out)))
+
+    @staticmethod
+    def _elems(buf, cplx, what):
+        name = str(buf.dtype).replace("torch.", "")
+        size = buf.numel() if hasattr(buf, "numel") else buf.size
+        if cplx and name == "float32" and size % 2 == 0:
+            return size // 2
+        if name != ("complex64" if cplx else "float32"):
+            raise LlzError(f"{what}: expected {'complex64 or pairs of float32' if cplx else 'float32'}, got {size} x {name}")
+        return size
+
+    def _run(self, name, x, out, count, in_pitch, out_pitch, in_len, out_len, in_cplx, out_cplx):
+        have = self._elems(x, in_cplx, name)
+        in_pitch = in_len if in_pitch is None else in_pitch
+        out_pitch = out_len if out_pitch is None else out_pitch
+        if count is None:
+            count = have // in_len if in_pitch == in_len else (have - in_len) // in_pitch + 1
+        if count < 1 or in_pitch < 1 or have != (count - 1) * in_pitch + in_len:
+            raise LlzError(f"{name}: {have} input elements are not {count} rows of {in_len}, {in_pitch} apart")
+        need = (count - 1) * max(out_pitch, 0) + out_len
+        if out is None:
+            if isinstance(x, np.ndarray):
+                out = np.empty(need, dtype=np.complex64 if out_cplx else np.float32)
+            else:
+                import torch
+                out = torch.empty(need, dtype=torch.complex64 if out_cplx else torch.float32, device=x.device)
+            if out_pitch == out_len:
+                out = out.reshape(count, out_len)
+        elif self._elems(out, out_cplx, name) != need:
+            raise LlzError(f"{name}: out holds {self._elems(out, out_cplx, name)} elements, {count} rows of {out_len}, "
+                           f"{out_pitch} apart, take {need}")
+        check(getattr(self._L, name)(self.handle, _ptr(x), in_pitch, _ptr(out), out_pitch, count), name)
+        return out
+
+    def close(self):
+        if getattr(self, "handle", 0):
+            self._L.llz_dft_mc_uninit(self.handle)
+            self.handle = 0
+
+    __del__ = close
+
+
+class DftMC(_ChirpZ):
+    """llz_dft_mc_*: batched DFT of any length n in 2 .. 1048576 by the chirp-z algorithm.  forward / inverse: rows of n
+    complex; rforward: n real -> n // 2 + 1 bins; rinverse: n // 2 + 1 bins -> n real.  The window multiplies the time side
+    (the input of forward transforms, the output of inverse ones)."""
+
+    def __init__(self, n, window=None, stream=None):
+        self._L = capi.lib()
+        self.n, self.bins = n, n // 2 + 1
+        self._open(self._L.llz_dft_mc_init(n), "llz_dft_mc_init", window, stream)
+
+    def forward(self, x, out=None, count=None, in_pitch=None, out_pitch=None):
+        return self._run("llz_dft_mc_forward", x, out, count, in_pitch, out_pitch, self.n, self.n, True, True)
+
+    def inverse(self, x, out=None, count=None, in_pitch=None, out_pitch=None):
+        return self._run("llz_dft_mc_inverse", x, out, count, in_pitch, out_pitch, self.n, self.n, True, True)
+
+    def rforward(self, x, out=None, count=None, in_pitch=None, out_pitch=None):
+        return self._run("llz_dft_mc_real_forward", x, out, count, in_pitch, out_pitch, self.n, self.bins, False, True)
+
+    def rinverse(self, x, out=None, count=None, in_pitch=None, out_pitch=None):
+        return self._run("llz_dft_mc_real_inverse", x, out, count, in_pitch, out_pitch, self.bins, self.n, True, False)
+
+
+class CztMC(_ChirpZ):
+    """llz_czt_mc_*: the zoom transform X[k] = sum_n w[n] x[n] exp(-2 pi i (f0 + k df) n), k < K, of rows of n complex
+    (forward) or real (rforward) samples; f0, df in cycles per sample, n + k - 1 <= 4096."""
+
+    def __init__(self, n, k, f0, df, window=None, stream=None):
+        self._L = capi.lib()
+        self.n, self.k = n, k
+        self._open(self._L.llz_czt_mc_init(n, k, f0, df), "llz_czt_mc_init", window, stream)
+
+    def forward(self, x, out=None, count=None, in_pitch=None, out_pitch=None):
+        return self._run("llz_czt_mc_forward", x, out, count, in_pitch, out_pitch, self.n, self.k, True, True)
+
+    def rforward(self, x, out=None, count=None, in_pitch=None, out_pitch=None):
+        return self._run("llz_czt_mc_real_forward", x, out, count, in_pitch, out_pitch, self.n, self.k, False, True)
+
+
 # ------------------------------------------------------------------------------------------ linear prediction
 LEVINSON_ORDER_MAX = 64
 
